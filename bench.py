@@ -7,7 +7,8 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps, writes the last timed step's
+outputs when --dump-outputs DIR is given, and prints the line; its sub-records are null.  With --full the line also carries
   step_ms      -- median / p10 / p90 of single steps (HIP events on the launch stream, a separate pass after the timed one)
   roofline     -- the dominant kernel class (3x3 MFMA direct conv, all its launches of a step): algorithmic
                   FLOPs / HIP-event time, against the dense bf16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md);
@@ -18,6 +19,12 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   parity_mode  -- the same workload in fp32 (exact-fp32 MFMA), the mode that meets the 1e-3 logit bar, timed here
   cpu_baseline -- the CPU oracle (a port of the reference's step, oracle/cdnet_ref.py) timed on this host
                   on a bounded sample (N = 1 only).
+and the secondary / forward_only / attention / ddp_rehearsal records of the other nets and step forms.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller, as float32 .npy files:
+  loss.npy (train step), logits.npy, params.npy / grads.npy (the flat fp32 parameter and gradient arenas after the update);
+an array above DUMP_MAX_ELEMS elements is written as the fixed sample DUMP_SEED picks (the same indices in every run).
+The inputs and the initial weights are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -48,6 +55,8 @@ ALG_MB_PER_PAIR_BY_NET = {NET: ALG_MB_PER_PAIR, "newUNetTrans": 200.0}      # SU
 # FlopCounterMode per module over the imported reference, tools/attn_flops.py (same counter and totals as BASELINE.md section 2):
 # (forward, forward + backward).  The token encoder is 0.001 - 0.004 GFLOP per pair and not part of the record.
 ATTN_GFLOP_PER_PAIR = {NET: (0.6716, 2.0148), "newUNetTrans": (8.2890, 25.2633)}
+DUMP_MAX_ELEMS = 1 << 22        # per array of --dump-outputs (16 MiB in float32; at most four arrays)
+DUMP_SEED = 20240601
 
 
 def _profile(suffix, net=NET):
@@ -224,7 +233,10 @@ def build(args, dtype, dev, local, rank, use_graph):
             return graphed()
         if xbd_mode:                                         # xBD_code/train.py:331-374
             net.zero_grad()
-            loss = xbd.xbd_loss(net(x6), msk)
+            logits = net(x6)
+            if args.dump_outputs:
+                step.logits = logits.detach()
+            loss = xbd.xbd_loss(logits, msk)
             loss.backward()
             scale = parallel.allreduce_net_grads_(net)
             if scale != 1.0:
@@ -233,6 +245,8 @@ def build(args, dtype, dev, local, rank, use_graph):
             opt.step()
             return loss
         logits = net(a, b)
+        if args.dump_outputs:
+            step.logits = logits.detach()
         opt.zero_grad()
         loss = losses.focal_loss(logits, lab)
         loss.backward()
@@ -242,6 +256,24 @@ def build(args, dtype, dev, local, rank, use_graph):
     step.graphed = graphed
     step.net = net
     return step, xbd_mode
+
+
+def dump_outputs(step, out, args):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float32 (module docstring)"""
+    import numpy as np
+    if args.fwd_only:
+        arrays = {"logits": out}
+    else:
+        params, grads = step.net.flat_params()
+        arrays = {"loss": out.reshape(1), "logits": step.graphed.logits if step.graphed is not None else step.logits,
+                  "params": params, "grads": grads}
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, t in arrays.items():
+        v = t.detach().float().cpu().numpy()
+        if v.size > DUMP_MAX_ELEMS:          # a fixed sample: the same flat indices for the same array size in every run
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, DUMP_MAX_ELEMS, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def roofline_records(step, args):
@@ -488,7 +520,16 @@ def main():
     ap.add_argument("--no-ddp-rehearsal", action="store_true",
                     help="skip the one-rank RCCL rehearsal of the data-parallel step (two graphs + two all-reduces)")
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-class event profiling (roofline / hbm blocks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the sub-records (step_ms, roofline / hbm, parity_mode, secondary, forward_only, attention, "
+                         "ddp_rehearsal, cpu_baseline; the --no-* switches drop single ones); without it the run times the "
+                         "headline step only and leaves them null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, logits, flat parameters and "
+                         "gradients after the update) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py --steps %d --warmup %d" % (args.steps, args.warmup))
 
     # --gpus N without a torchrun environment: this process has not touched the GPU yet (counting devices does not), so it
     # may still start N fresh ranks itself -- exactly the launch line of the docstring -- and pass their one JSON line through.
@@ -519,11 +560,10 @@ def main():
     # (never under a profiler: rocprofv3's preloaded library has initialised the GPU before this program starts, and a process
     # that holds the GPU must not start another program)
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-    if headline_run and not args.no_ddp_rehearsal and not profiled and os.environ.get("DAHITRA_FORCE_DIST", "0") != "1":
+    if args.full and headline_run and not args.no_ddp_rehearsal and not profiled and os.environ.get("DAHITRA_FORCE_DIST", "0") != "1":
         import socket
         import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "20", "--warmup", "5", "--batch", str(args.batch),
-               "--no-cpu-baseline", "--no-parity-mode", "--no-secondary", "--no-ddp-rehearsal", "--no-roofline"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "20", "--warmup", "5", "--batch", str(args.batch)]
 
         def child(overlap):
             with socket.socket() as sk:
@@ -591,10 +631,12 @@ def main():
         per_rank_ms = [round(float(v) / args.steps * 1e3, 3) for v in t.tolist()]
         dt = float(t.max().item())
     final = float(out.detach()) if not args.fwd_only else 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step, out, args)
 
     # ---- single-step distribution: HIP events on the launch stream, a separate pass (the timed region is untouched) ----
     step_ms = None
-    if True:                                     # every rank steps (the step holds a collective); rank 0 reports
+    if args.full:                                # every rank steps (the step holds a collective); rank 0 reports
         n = max(10, min(args.steps, 50))
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
         for e0, e1 in evs:
@@ -610,14 +652,14 @@ def main():
 
     # ---- per-class kernel times: HIP events around every profiled launch (1 + 3 extra EAGER steps, rank 0) ----
     roof = hbm = None
-    if rank == 0 and not args.fwd_only and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and not args.fwd_only and world == 1 and not args.no_roofline:
         roof, hbm = roofline_records(step, args)
 
     # ---- parity mode: the modes that meet the 1e-3 logit bar, timed by the same driver run.  "bf16x3" = the fp32 pipeline with
     # its matrix products on the 16-bit matrix cores as three split products (fp16 planes forward, bf16 planes backward: the same
     # test bounds as the exact mode, tests/test_model_gpu.py PARITY_MODES); "fp32" = exact fp32 MFMA, reported next to it ----
     parity = None
-    if rank == 0 and world == 1 and args.dtype == "bf16" and not args.no_parity_mode and not args.fwd_only \
+    if args.full and rank == 0 and world == 1 and args.dtype == "bf16" and not args.no_parity_mode and not args.fwd_only \
             and args.net == NET and args.img == SIZE:
         def timed(dtype, k):
             stp, _ = build(args, dtype, dev, local, rank, use_graph)
@@ -645,7 +687,7 @@ def main():
 
     # ---- secondary: DAHiTra proper (newUNetTrans), the model the reference is named after, timed by the same driver run ----
     secondary = None
-    if rank == 0 and world == 1 and headline_run and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and headline_run and not args.no_secondary:
         import copy
         a2 = copy.copy(args)
         a2.net = "newUNetTrans"
@@ -678,7 +720,7 @@ def main():
     # ---- forward_only: the evaluation forward (eval-mode BatchNorm, no gradient state; models/evaluator.py:156-164) of both nets,
     # SURVEY.md section 8d "also report fwd-only", timed by the same driver run ----
     forward_only = None
-    if rank == 0 and world == 1 and headline_run and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and headline_run and not args.no_secondary:
         import copy
         forward_only = {}
         for nname in (NET, "newUNetTrans"):
@@ -720,7 +762,8 @@ def main():
 
     attention = None
     # (not in profiler runs, --no-class-replay: its replays would be counted into the per-step kernel statistics and PMC sums)
-    if rank == 0 and world == 1 and not args.fwd_only and args.dtype == "bf16" and args.net in ATTN_GFLOP_PER_PAIR and not args.no_roofline \
+    if args.full and rank == 0 and world == 1 and not args.fwd_only and args.dtype == "bf16" and args.net in ATTN_GFLOP_PER_PAIR \
+            and not args.no_roofline \
             and not args.no_class_replay:
         try:
             attention = attention_record(step, args.net, args.batch, args.img, _profile("_pmc_mfma_util.json", args.net))
@@ -758,7 +801,7 @@ def main():
             "secondary": secondary,
             "ddp_rehearsal": None if rehearsal is None else dict(rehearsal, one_graph_ms_per_step=round(dt / args.steps * 1e3, 3)),
         }
-        if world == 1 and not args.no_cpu_baseline and args.net in ALG_MB_PER_PAIR_BY_NET and args.img == SIZE:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.net in ALG_MB_PER_PAIR_BY_NET and args.img == SIZE:
             res["cpu_baseline"] = cpu_baseline(args.net)
         os.write(json_fd, (json.dumps(res) + "\n").encode())
     if dist.is_initialized():

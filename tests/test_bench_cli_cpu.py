@@ -36,3 +36,13 @@ def test_profile_pointer_names_committed_files():
         rel = bench._profile(suffix)
         assert rel == os.path.join("profiles", tag + suffix) and os.path.exists(os.path.join(ROOT, rel))
     assert bench._profile("_pmc_step_traffic.json", "no_such_net") is None
+
+
+def test_plain_run_and_full_switches_are_offered():
+    """a plain run times the headline step only; --full brings back the sub-records, --dump-outputs DIR the last step's arrays"""
+    r = _run(["--help"])
+    assert r.returncode == 0
+    for flag in ("--full", "--dump-outputs", "--steps", "--warmup"):
+        assert flag in r.stdout, flag
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and not r.stdout.strip() and "--steps 0" in r.stderr

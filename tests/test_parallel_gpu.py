@@ -229,14 +229,14 @@ def test_two_ranks_reduced_gradient_is_the_mean_of_the_per_shard_oracle_gradient
     assert worst <= 6e-2 and cos_min >= 0.995          # the fp32 noise floor of these gradients (tests/test_model_gpu.py)
 
 
-def _run_bench(extra_env, launcher):
+def _run_bench(extra_env, launcher, extra_args=()):
     import json
     import subprocess
     env = dict(os.environ)
     env.update(extra_env)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable] + launcher + ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4",
-                                           "--no-cpu-baseline", "--no-parity-mode"]
+                                           "--no-cpu-baseline", "--no-parity-mode"] + list(extra_args)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -259,6 +259,31 @@ def test_bench_multi_gpu_code_path_runs_over_rccl_with_one_rank():
     assert dist_line["config"]["hip_graph"] is True
     a, b = dist_line["config"]["final_loss"], plain["config"]["final_loss"]
     assert abs(a - b) <= 1e-6 * max(1.0, abs(b)), (a, b)
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """a plain run (no --full) times exactly --steps steps, leaves the sub-records null and, with --dump-outputs, writes the
+    last timed step's loss, logits and flat parameter / gradient arenas as float32 .npy files: the loss is the line's
+    final_loss, and a second run with the same arguments starts from the same inputs (seeded synthetic batch and
+    weights) and writes the same outputs"""
+    import numpy as np
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        lines.append(_run_bench({}, [], ["--dump-outputs", str(d)]))
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("loss", "logits", "params", "grads")})
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert line["step_ms"] is None and line["roofline"] is None and line["secondary"] is None and "cpu_baseline" not in line
+    out = dumps[0]
+    assert all(v.dtype == np.float32 for v in out.values())
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    assert out["logits"].shape == (4, 2, 256, 256) and np.isfinite(out["logits"]).all()
+    assert out["params"].size == out["grads"].size and np.abs(out["grads"]).max() > 0
+    assert abs(float(out["loss"][0]) - line["config"]["final_loss"]) <= 1e-6 * max(1.0, abs(line["config"]["final_loss"]))
+    for n in out:
+        assert out[n].shape == dumps[1][n].shape, n
+        assert np.allclose(out[n], dumps[1][n], rtol=1e-4, atol=1e-4 * float(np.abs(out[n]).max())), n
 
 
 def test_bench_refuses_more_gpus_than_the_box_has():
