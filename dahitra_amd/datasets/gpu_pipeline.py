@@ -66,8 +66,8 @@ class GpuPairPipeline:
         out_a = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
         out_b = torch.empty_like(out_a)
         out_l = torch.empty(n, 1, h, w, dtype=torch.uint8, device=dev)
-        ops._call("dh_augment_pairs_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params),
-                  ops._ci(n), ops._ci(H), ops._ci(W), ops._ci(h), ops._ci(w), ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
+        ops._call("dh_augment_pairs_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params), n, H, W, h, w,
+                  ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
         return {'A': out_a, 'B': out_b, 'L': out_l, 'name': [self.names[i] for i in indices]}
 
     def batches(self, batch_size, img_size, train=True, generator=None, patch=None, drop_last=False):

@@ -1195,7 +1195,7 @@ class Engine:
         ops.absdiff_halves(tk3, dtk)
         ddtk = self._zeros_like(dtk) if self.need_grad else None
         yield                       # cat and dtk are valid from here on
-        dxc, b_cd = self.conv_act(cat, "conv_decode_%d.weight" % l, None, 3, 1, NONE)
+        dxc, b_cdec = self.conv_act(cat, "conv_decode_%d.weight" % l, None, 3, 1, NONE)
         xin3 = ops.add_pos(dxc, pos)        # (recorded: a round issues the element-wise jobs before its decoder stacks)
         out, b_dec3 = yield from self._decoder_gen(xin3.view(B * hw, DIM), B, dtk.view(B * L, DIM), L * DIM, 0, B, ddtk, dp,
                                                    lv["dec_depth"], lv["heads"], lv["dim_head"], L)
@@ -1207,7 +1207,7 @@ class Engine:
         def bwd(dout4):
             dxin3 = (yield from b_dec3(dout4.reshape(B * hw, DIM))).view(B, fh, fw, DIM)
             ops.add_pos_bwd(dxin3, gpos, accumulate=True)
-            dcat = b_cd(dxin3)
+            dcat = b_cdec(dxin3)
             ops.absdiff_halves_bwd(tk3, ddtk, dtok)                    # accumulates into both token halves
             ddec = ops.split_halves(dcat)      # (these three may only be recorded: issued before the round's decoder stacks)
             dxin = (yield from b_dec(ddec.view(S2 * hw, DIM))).view(S2, fh, fw, DIM)
@@ -1240,7 +1240,7 @@ class Engine:
         ops.absdiff_halves(tk3, dtk)
         ddtk = self._zeros_like(dtk) if self.need_grad else None
         cat = ops.cat_halves(sq)
-        dxc, b_cd = self.conv_act(cat, "conv_decode_%d.weight" % l, None, 3, 1, NONE)
+        dxc, b_cdec = self.conv_act(cat, "conv_decode_%d.weight" % l, None, 3, 1, NONE)
         pos = self.p["pos_embedding_decoder_3"] if (with_pos and self.cfg["decoder_pos"]) else None
         xin = ops.add_pos(dxc, pos) if pos is not None else dxc
         out, b_dec = yield from self._decoder_gen(xin.view(B * hw, DIM), B, dtk.view(B * L, DIM), L * DIM, 0, B, ddtk,
@@ -1253,7 +1253,7 @@ class Engine:
             dxin = (yield from b_dec(dout4.reshape(B * hw, DIM))).view(B, fh, fw, DIM)
             if pos is not None:
                 ops.add_pos_bwd(dxin, self.g["pos_embedding_decoder_3"], accumulate=True)
-            dcat = b_cd(dxin)
+            dcat = b_cdec(dxin)
             dtok = torch.zeros_like(tok2d)
             ops.absdiff_halves_bwd(tk3, ddtk, dtok)
             dtok_cat = b_enc(dtok)

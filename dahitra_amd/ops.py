@@ -14,10 +14,6 @@ from . import _lib
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 _vp = ctypes.c_void_p
-_ci = ctypes.c_int
-_cl = ctypes.c_long
-_cf = ctypes.c_float
-_cd = ctypes.c_double
 
 
 def dt(t):
@@ -151,8 +147,7 @@ def pack_weight(w, dtype, want_dgrad=True, dgrad_inner=0, out_scale=None, want_f
         dg = out_dgrad
     else:
         dg = torch.empty(ks * ks, IPad, OK, dtype=dtype, device=w.device) if want_dgrad else None
-    _call("dh_pack_weight", _ci(_DT[dtype]), P(w), P(out_scale), _ci(O), _ci(I), _ci(ks), _ci(OPad), P(fwd), _ci(IPad), _ci(OK),
-          P(dg), S())
+    _call("dh_pack_weight", _DT[dtype], P(w), P(out_scale), O, I, ks, OPad, P(fwd), IPad, OK, P(dg), S())
     return fwd, dg
 
 
@@ -206,7 +201,7 @@ class PackPlan:
             assert ctypes.sizeof(self._Job) == _lib.lib().dh_pack_job_size()
             raw = b"".join(bytes(j) for j in self.jobs)
             self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-        _call("dh_pack_weights_multi", P(self.table), _ci(len(self.jobs)), _ci(self.blocks), S())
+        _call("dh_pack_weights_multi", P(self.table), len(self.jobs), self.blocks, S())
 
 
 class WgradPlan:
@@ -307,7 +302,7 @@ class WgradPlan:
                 _PINNED.append(self.tables[self.phase])
             self.tables[self.phase] = torch.frombuffer(bytearray(sig), dtype=torch.uint8).to(self.device)
             self.sigs[self.phase] = sig
-        _call("dh_wgrad_reduce_multi", P(self.tables[self.phase]), _ci(len(self.jobs)), _ci(self.blocks), S())
+        _call("dh_wgrad_reduce_multi", P(self.tables[self.phase]), len(self.jobs), self.blocks, S())
 
 
 _WGRAD_PLAN = None
@@ -383,15 +378,15 @@ def _nb(*tensors):
 
 def _bn_in_args(b):
     if b is None:
-        return _vp(0), _vp(0), _ci(0)
-    return P(b.scale), P(b.shift), _ci(b.groups)
+        return _vp(0), _vp(0), 0
+    return P(b.scale), P(b.shift), b.groups
 
 
 def _gate_args(gate):
     if gate is None:
-        return _vp(0), _vp(0), _vp(0), _vp(0), _ci(0)
+        return _vp(0), _vp(0), _vp(0), _vp(0), 0
     out_relu, y, mean, invstd, groups = gate
-    return P(out_relu), P(y), P(mean), P(invstd), _ci(groups)
+    return P(out_relu), P(y), P(mean), P(invstd), groups
 
 
 class BnInput:
@@ -444,9 +439,8 @@ def conv2d(x, wp, cout, ks=3, stride=1, pad=1, bias=None, residual=None, act=ACT
     nt_ = 64 if cpad % 64 == 0 else (32 if cpad % 32 == 0 else 16)
     key = "conv_mfma<%s,ks%d,s%d,nt%d>" % ("bf16" if x.dtype == torch.bfloat16 else "f32", ks, stride, nt_)
     flops = alg_flops if alg_flops else 2.0 * N * OH * OW * cout * Cin * ks * ks
-    fixed = (_ci(dt(x)), P(x), P(wp), P(y), P(bias), P(residual), P(stats), _ci(N), _ci(H), _ci(W),
-             _ci(Cin), _ci(OH), _ci(OW), _ci(cout), _ci(cpad), _ci(ks), _ci(stride), _ci(pad), _ci(act), _ci(npix_valid),
-             _cl(w_image_stride), P(pre), _ci(dilation), *_gate_args(gate), *_bn_in_args(bn_in), _ci(0), P(w_frag))
+    fixed = (dt(x), P(x), P(wp), P(y), P(bias), P(residual), P(stats), N, H, W, Cin, OH, OW, cout, cpad, ks, stride, pad, act,
+             npix_valid, w_image_stride, P(pre), dilation, *_gate_args(gate), *_bn_in_args(bn_in), 0, P(w_frag))
     with _Prof(key, flops, _nb(x, y, wp, residual, pre)):
         _call("dh_conv2d_fwd", *fixed, S())
     if REPLAY is not None and key == REPLAY["key"]:
@@ -488,7 +482,7 @@ def _conv3x3_up4(u, wp, cout, bias, act, want_stats):
     if want_stats:
         stats = torch.empty(2, 32, _lib.lib().dh_conv2d_fwd_num_tiles(_DT[torch.bfloat16], N, H, W, 32, 3, 1), dtype=torch.float32, device=y.device)
     key, flops = "conv_mfma<bf16,ks3,s1,nt32>", 2.0 * N * H * W * 32 * 32 * 9
-    fixed = (P(u.a), P(u.b), P(wp), P(bias), _ci(act), P(y), P(stats), _ci(N), _ci(H), _ci(W))
+    fixed = (P(u.a), P(u.b), P(wp), P(bias), act, P(y), P(stats), N, H, W)
     with _Prof(key, flops, _nb(u.a, u.b, y, wp)):
         _call("dh_conv3x3_up4_fwd", *fixed, S())
     if REPLAY is not None and key == REPLAY["key"]:
@@ -523,7 +517,7 @@ def conv3x3_split_supported(B, H, W, cin, cout, dtype):
     """can the 3x3 / stride 1 / pad 1 layer cin -> cout on B x H x W pixels run with a SplitCat input (forward and weight
     gradient) and a split data-gradient output?  (bf16, register-resident-weights + wave-specialised kernels; dahitra_hip.h)"""
     return dtype == torch.bfloat16 and os.environ.get("DAHITRA_NO_SPLIT_CAT", "0") != "1" and \
-        bool(_lib.lib().dh_conv3x3_split_supported(_ci(B), _ci(H), _ci(W), _ci(cin), _ci(cout)))
+        bool(_lib.lib().dh_conv3x3_split_supported(B, H, W, cin, cout))
 
 
 def conv3x3_split(x, wp, w_frag, cout, want_stats=False, split_out=False, alg_flops=0):
@@ -544,8 +538,7 @@ def conv3x3_split(x, wp, w_frag, cout, want_stats=False, split_out=False, alg_fl
         nt = _lib.lib().dh_conv2d_fwd_num_tiles(_DT[xt.dtype], N, H, W, Cin, 3, 1)
         stats = torch.empty(2, cout, nt, dtype=torch.float32, device=xt.device)
     flops = alg_flops if alg_flops else 2.0 * N * H * W * cout * Cin * 9
-    fixed = (P(xt), _cl(xs.split_bytes if xs is not None else 0), P(wp), P(w_frag), P(y), _cl(ysplit), P(stats), _ci(N), _ci(H),
-             _ci(W), _ci(Cin), _ci(cout))
+    fixed = (P(xt), xs.split_bytes if xs is not None else 0, P(wp), P(w_frag), P(y), ysplit, P(stats), N, H, W, Cin, cout)
     key = "conv_mfma<bf16,ks3,s1,nt64>"
     with _Prof(key, flops, _nb(xt, y, wp)):
         _call("dh_conv3x3_split_fwd", *fixed, S())
@@ -571,12 +564,11 @@ def conv3x3_head(x, wp, ncls, bias, w_oihw=None):
             (x.dtype == torch.bfloat16 or (x.dtype == torch.float32 and get_f32_mma_mode() == 3)):
         assert w_oihw.shape == (ncls, 32, 3, 3) and w_oihw.dtype == torch.float32
         with _Prof("head_fwd", 2.0 * N * H * W * ncls * Cin * 9, _nb(x, out)):
-            _call("dh_head_fwd", _ci(dt(x)), P(x), P(w_oihw), P(bias), _ci(ncls), *_bn_in_args(bn_in), P(out), _ci(N), _ci(H), _ci(W), S())
+            _call("dh_head_fwd", dt(x), P(x), P(w_oihw), P(bias), ncls, *_bn_in_args(bn_in), P(out), N, H, W, S())
         return out
     key = "conv_mfma<%s,ks3,s1,nt16>" % ("bf16" if x.dtype == torch.bfloat16 else "f32")
     with _Prof(key, 2.0 * N * H * W * ncls * Cin * 9, _nb(x, out, wp)):
-        _call("dh_conv3x3_head_fwd", _ci(dt(x)), P(x), P(wp), P(bias), _ci(N), _ci(H), _ci(W), _ci(Cin), _ci(ncls),
-              *_bn_in_args(bn_in), P(out), S())
+        _call("dh_conv3x3_head_fwd", dt(x), P(x), P(wp), P(bias), N, H, W, Cin, ncls, *_bn_in_args(bn_in), P(out), S())
     return out
 
 
@@ -595,9 +587,8 @@ def linear(x2d, wp, cout, bias=None, residual=None, act=ACT_NONE, want_preact=Fa
     cpad = wp.shape[-2]
     y = torch.empty(rows, cout, dtype=x2d.dtype, device=x2d.device)
     pre = torch.empty_like(y) if want_preact else None
-    _call("dh_conv2d_fwd", _ci(dt(x2d)), P(x2d), P(wp), P(y), P(bias), P(residual), _vp(0), _ci(images), _ci(Hh),
-          _ci(16), _ci(Cin), _ci(Hh), _ci(16), _ci(cout), _ci(cpad), _ci(1), _ci(1), _ci(0), _ci(act), _ci(rpi),
-          _cl(w_image_stride), P(pre), _ci(1), *_gate_args(None), *_bn_in_args(None), _ci(0), _vp(0), S())
+    _call("dh_conv2d_fwd", dt(x2d), P(x2d), P(wp), P(y), P(bias), P(residual), _vp(0), images, Hh, 16, Cin, Hh, 16, cout, cpad, 1,
+          1, 0, act, rpi, w_image_stride, P(pre), 1, *_gate_args(None), *_bn_in_args(None), 0, _vp(0), S())
     # note: with rows_per_image % 16 != 0 the image stride used by the kernel (Hh*16 rows) would differ
     # from rpi; callers guarantee rpi % 16 == 0 whenever images > 1.
     assert images == 1 or rpi % 16 == 0
@@ -626,20 +617,18 @@ def conv2d_wgrad(x, dy, dw, ks, stride, pad, accumulate=False, groups=1, use_tr=
     if plan is not None and groups == 1 and defer:      # defer=False: the caller reads dw right after this call
         # deferred: partial slabs into this layer's persistent workspace, summed later by plan.run()
         ws = plan.slab(nbytes)
-        sk = ctypes.c_int(0)
+        sk = (ctypes.c_int * 1)()       # int* splitk_out
         with _Prof("conv_wgrad<%s,ks%d,s%d>" % ("bf16" if x.dtype == torch.bfloat16 else "f32", ks, stride),
                    2.0 * N * OH * OW * Cout * Cin * ks * ks, _nb(x, dy)):
-            _call("dh_conv2d_wgrad_partial", _ci(dt(x)), P(x), P(dy), P(dw), _ci(int(accumulate)), _ci(N), _ci(H), _ci(W),
-                  _ci(Cin), _ci(OH), _ci(OW), _ci(Cout), _ci(ks), _ci(stride), _ci(pad), _ci(1), _ci(0), _ci(int(use_tr)),
-                  _ci(cout_real), _ci(pitch), _ci(dilation), P(ws), ctypes.byref(sk), S())
+            _call("dh_conv2d_wgrad_partial", dt(x), P(x), P(dy), P(dw), accumulate, N, H, W, Cin, OH, OW, Cout, ks, stride, pad,
+                  1, 0, use_tr, cout_real, pitch, dilation, P(ws), sk, S())
         plan.hold(x, dy)
-        if sk.value > 0:
-            plan.add(ws, dw, sk.value, ks * ks, Cout, cout_real if cout_real else Cout, Cin, accumulate)
+        if sk[0] > 0:
+            plan.add(ws, dw, sk[0], ks * ks, Cout, cout_real if cout_real else Cout, Cin, accumulate)
         return
     ws = workspace(nbytes, x.device)
-    _call("dh_conv2d_wgrad", _ci(dt(x)), P(x), P(dy), P(dw), _ci(int(accumulate)), _ci(N), _ci(H), _ci(W), _ci(Cin),
-          _ci(OH), _ci(OW), _ci(Cout), _ci(ks), _ci(stride), _ci(pad), _ci(groups), _ci(0), _ci(int(use_tr)),
-          _ci(cout_real), _ci(pitch), _ci(dilation), P(ws), S())
+    _call("dh_conv2d_wgrad", dt(x), P(x), P(dy), P(dw), accumulate, N, H, W, Cin, OH, OW, Cout, ks, stride, pad, groups, 0,
+          use_tr, cout_real, pitch, dilation, P(ws), S())
 
 
 def _conv2d_wgrad_split(xs, dy, dw, ks, stride, pad, accumulate, defer):
@@ -654,12 +643,11 @@ def _conv2d_wgrad_split(xs, dy, dw, ks, stride, pad, accumulate, defer):
         plan.__enter__()
     try:
         ws = plan.slab(nbytes)
-        sk = ctypes.c_int(0)
+        sk = (ctypes.c_int * 1)()       # int* splitk_out
         with _Prof("conv_wgrad<bf16,ks3,s1>", 2.0 * N * H * W * Cout * Cin * 9, _nb(xs.t, dy)):
-            _call("dh_conv2d_wgrad_split", P(xs.t), _cl(xs.split_bytes), P(dy), P(dw), _ci(int(accumulate)), _ci(N), _ci(H), _ci(W),
-                  _ci(Cin), _ci(Cout), P(ws), ctypes.byref(sk), S())
+            _call("dh_conv2d_wgrad_split", P(xs.t), xs.split_bytes, P(dy), P(dw), accumulate, N, H, W, Cin, Cout, P(ws), sk, S())
         plan.hold(xs.t, dy)
-        plan.add(ws, dw, sk.value, 9, Cout, Cout, Cin, accumulate)
+        plan.add(ws, dw, sk[0], 9, Cout, Cout, Cin, accumulate)
         if own:
             plan.run()
     finally:
@@ -674,16 +662,15 @@ def _conv2d_wgrad_bn_in(b, dy, dw, ks, stride, pad, accumulate, use_tr, cout_rea
     nbytes = _lib.lib().dh_conv2d_wgrad_workspace_size(N, OH, OW, Cin, Cout, ks, 1)
     plan = _WGRAD_PLAN if defer else None
     ws = plan.slab(nbytes) if plan is not None else workspace(nbytes, x.device)
-    sk = ctypes.c_int(0)
+    sk = (ctypes.c_int * 1)()       # int* splitk_out
     with _Prof("conv_wgrad<%s,ks%d,s%d>" % ("bf16" if x.dtype == torch.bfloat16 else "f32", ks, stride),
                2.0 * N * OH * OW * Cout * Cin * ks * ks, _nb(x, dy)):
-        _call("dh_conv2d_wgrad_bn_in", _ci(dt(x)), P(x), P(dy), P(dw), _ci(int(accumulate)), _ci(N), _ci(H), _ci(W), _ci(Cin),
-              _ci(OH), _ci(OW), _ci(Cout), _ci(ks), _ci(stride), _ci(pad), _ci(int(use_tr)), _ci(cout_real), _ci(dilation),
-              P(b.scale), P(b.shift), _ci(b.groups), P(ws), ctypes.byref(sk) if plan is not None else None, S())
+        _call("dh_conv2d_wgrad_bn_in", dt(x), P(x), P(dy), P(dw), accumulate, N, H, W, Cin, OH, OW, Cout, ks, stride, pad, use_tr,
+              cout_real, dilation, P(b.scale), P(b.shift), b.groups, P(ws), sk if plan is not None else None, S())
     if plan is not None:
         plan.hold(x, dy, b.scale, b.shift)
-    if plan is not None and sk.value > 0:
-        plan.add(ws, dw, sk.value, ks * ks, Cout, cout_real if cout_real else Cout, Cin, accumulate)
+    if plan is not None and sk[0] > 0:
+        plan.add(ws, dw, sk[0], ks * ks, Cout, cout_real if cout_real else Cout, Cin, accumulate)
 
 
 # ---- conv3x3(nearest-upsample-x2(x)) with 32 output channels as four 2x2 phase convolutions (models/networks.py:251-256) ----
@@ -694,7 +681,7 @@ def pack_phase_weights(w, bias, dtype):
     fwd = torch.empty(4, 128, I, dtype=dtype, device=w.device)
     dg = torch.empty(4, I, 128, dtype=dtype, device=w.device)
     b4 = torch.empty(128, dtype=torch.float32, device=w.device)
-    _call("dh_pack_phase_weights", _ci(_DT[dtype]), P(w), P(bias), _ci(I), P(fwd), P(dg), P(b4), S())
+    _call("dh_pack_phase_weights", _DT[dtype], P(w), P(bias), I, P(fwd), P(dg), P(b4), S())
     return fwd, dg, b4
 
 
@@ -704,9 +691,8 @@ def conv_up2_fwd(x, wfwd, bias4, act=ACT_NONE):
     y = torch.empty(N, 2 * H, 2 * W, 32, dtype=x.dtype, device=x.device)
     key = "conv_phase<%s,up2_fwd>" % ("bf16" if x.dtype == torch.bfloat16 else "f32")         # its own class: KS = 2 launches
     with _Prof(key, 2.0 * N * 4 * H * W * 32 * Cin * 9, _nb(x, y, wfwd)):                       # algorithmic FLOPs (of the 3x3)
-        _call("dh_conv2d_fwd", _ci(dt(x)), P(x), P(wfwd), P(y), P(bias4), _vp(0), _vp(0), _ci(N), _ci(H), _ci(W), _ci(Cin),
-              _ci(H), _ci(W), _ci(128), _ci(128), _ci(2), _ci(1), _ci(1), _ci(act), _ci(0), _cl(0), _vp(0), _ci(1),
-              *_gate_args(None), *_bn_in_args(None), _ci(1), _vp(0), S())
+        _call("dh_conv2d_fwd", dt(x), P(x), P(wfwd), P(y), P(bias4), _vp(0), _vp(0), N, H, W, Cin, H, W, 128, 128, 2, 1, 1, act,
+              0, 0, _vp(0), 1, *_gate_args(None), *_bn_in_args(None), 1, _vp(0), S())
     return y
 
 
@@ -714,7 +700,7 @@ def pack_s2_dgrad_phase_weights(w, dtype):
     """OIHW fp32 [Co, Ci, 3, 3] of a stride-2 conv -> [4, 4 * Ci, Co] phase weights of its data gradient"""
     Co, Ci = w.shape[0], w.shape[1]
     out = torch.empty(4, 4 * Ci, Co, dtype=dtype, device=w.device)
-    _call("dh_pack_s2_dgrad_phase_weights", _ci(_DT[dtype]), P(w), _ci(Co), _ci(Ci), P(out), S())
+    _call("dh_pack_s2_dgrad_phase_weights", _DT[dtype], P(w), Co, Ci, P(out), S())
     return out
 
 
@@ -726,9 +712,8 @@ def conv3x3s2_dgrad(dy, wphase, cin, coarse_residual=None, alg_flops=0):
     dx = torch.empty(N, 2 * OH, 2 * OW, cin, dtype=dy.dtype, device=dy.device)
     key = "conv_phase<%s,s2_dgrad>" % ("bf16" if dy.dtype == torch.bfloat16 else "f32")
     with _Prof(key, alg_flops if alg_flops else 2.0 * N * OH * OW * Co * cin * 9, _nb(dy, dx, wphase, coarse_residual)):
-        _call("dh_conv2d_fwd", _ci(dt(dy)), P(dy), P(wphase), P(dx), _vp(0), P(coarse_residual), _vp(0), _ci(N), _ci(OH),
-              _ci(OW), _ci(Co), _ci(OH), _ci(OW), _ci(4 * cin), _ci(4 * cin), _ci(2), _ci(1), _ci(1), _ci(ACT_NONE), _ci(0),
-              _cl(0), _vp(0), _ci(1), *_gate_args(None), *_bn_in_args(None), _ci(1), _vp(0), S())
+        _call("dh_conv2d_fwd", dt(dy), P(dy), P(wphase), P(dx), _vp(0), P(coarse_residual), _vp(0), N, OH, OW, Co, OH, OW,
+              4 * cin, 4 * cin, 2, 1, 1, ACT_NONE, 0, 0, _vp(0), 1, *_gate_args(None), *_bn_in_args(None), 1, _vp(0), S())
     return dx
 
 
@@ -740,9 +725,8 @@ def conv_up2_dgrad(dy, wdgrad, cin):
     dx = torch.empty(N, H, W, cin, dtype=dy.dtype, device=dy.device)
     key = "conv_phase<%s,up2_dgrad>" % ("bf16" if dy.dtype == torch.bfloat16 else "f32")
     with _Prof(key, 2.0 * N * H2 * W2 * 32 * cin * 9, _nb(dy, dx, wdgrad)):
-        _call("dh_conv2d_fwd", _ci(dt(dy)), P(dy), P(wdgrad), P(dx), _vp(0), _vp(0), _vp(0), _ci(N), _ci(H), _ci(W), _ci(128),
-              _ci(H), _ci(W), _ci(cin), _ci(cin), _ci(2), _ci(1), _ci(1), _ci(ACT_NONE), _ci(0), _cl(0), _vp(0), _ci(1),
-              *_gate_args(None), *_bn_in_args(None), _ci(2), _vp(0), S())
+        _call("dh_conv2d_fwd", dt(dy), P(dy), P(wdgrad), P(dx), _vp(0), _vp(0), _vp(0), N, H, W, 128, H, W, cin, cin, 2, 1, 1,
+              ACT_NONE, 0, 0, _vp(0), 1, *_gate_args(None), *_bn_in_args(None), 2, _vp(0), S())
     return dx
 
 
@@ -758,15 +742,14 @@ def conv_up2_wgrad(x, dy, dw, accumulate=True, use_tr=True):
     try:
         ws = plan.slab(L.dh_conv2d_wgrad_phase_workspace_size(N, H, W, Cin))
         dwab = plan.slab(4 * 32 * Cin * 4 * 4).view(torch.float32)
-        sk = ctypes.c_int(0)
+        sk = (ctypes.c_int * 1)()       # int* splitk_out
         with _Prof("conv_wgrad<%s,ks3,s1>" % ("bf16" if x.dtype == torch.bfloat16 else "f32"),
                    2.0 * N * 4 * H * W * 32 * Cin * 9, _nb(x, dy)):
-            _call("dh_conv2d_wgrad_phase", _ci(dt(x)), P(x), P(dy), _ci(N), _ci(H), _ci(W), _ci(Cin), _ci(int(use_tr)), P(ws),
-                  ctypes.byref(sk), S())
-        per = sk.value * 4 * 32 * Cin * 4            # bytes of one phase's slabs
+            _call("dh_conv2d_wgrad_phase", dt(x), P(x), P(dy), N, H, W, Cin, use_tr, P(ws), sk, S())
+        per = sk[0] * 4 * 32 * Cin * 4            # bytes of one phase's slabs
         for ph in range(4):
-            plan.add(ws[ph * per:], dwab[ph * 32 * Cin * 4:], sk.value, 4, 32, 32, Cin, False)
-        plan.post.append(lambda: _call("dh_phase_wgrad_combine", P(dwab), P(dw), _ci(Cin), _ci(int(accumulate)), S()))
+            plan.add(ws[ph * per:], dwab[ph * 32 * Cin * 4:], sk[0], 4, 32, 32, Cin, False)
+        plan.post.append(lambda: _call("dh_phase_wgrad_combine", P(dwab), P(dw), Cin, accumulate, S()))
         if own:
             plan.run()
     finally:
@@ -784,9 +767,8 @@ def linear_wgrad(x2d, dy2d, dw, accumulate=False, images=1, per_image=False, use
     nbytes = L.dh_conv2d_wgrad_workspace_size(images, Hh, 16, Cin, Cout, 1, groups)
     ws = workspace(nbytes, x2d.device)
     assert images == 1 or rpi % 16 == 0
-    _call("dh_conv2d_wgrad", _ci(dt(x2d)), P(x2d), P(dy2d), P(dw), _ci(int(accumulate)), _ci(images), _ci(Hh), _ci(16),
-          _ci(Cin), _ci(Hh), _ci(16), _ci(Cout), _ci(1), _ci(1), _ci(0), _ci(groups), _ci(rpi), _ci(int(use_tr)),
-          _ci(0), _ci(0), _ci(1), P(ws), S())
+    _call("dh_conv2d_wgrad", dt(x2d), P(x2d), P(dy2d), P(dw), accumulate, images, Hh, 16, Cin, Hh, 16, Cout, 1, 1, 0, groups, rpi,
+          use_tr, 0, 0, 1, P(ws), S())
 
 
 def add_coarse_(x, coarse):
@@ -794,14 +776,14 @@ def add_coarse_(x, coarse):
     N, H, W, C = x.shape
     n2, OH, OW, c2 = coarse.shape
     assert n2 == N and c2 == C and x.dtype == coarse.dtype and x.is_contiguous() and coarse.is_contiguous()
-    _call("dh_add_coarse", _ci(dt(x)), P(x), P(coarse), _ci(N), _ci(OH), _ci(OW), _ci(H), _ci(W), _ci(C), S())
+    _call("dh_add_coarse", dt(x), P(x), P(coarse), N, OH, OW, H, W, C, S())
     return x
 
 
 def zero_insert2(dy, H, W):
     N, OH, OW, C = dy.shape
     z = torch.empty(N, H, W, C, dtype=dy.dtype, device=dy.device)
-    _call("dh_zero_insert2", _ci(dt(dy)), P(dy), P(z), _ci(N), _ci(OH), _ci(OW), _ci(H), _ci(W), _ci(C), S())
+    _call("dh_zero_insert2", dt(dy), P(dy), P(z), N, OH, OW, H, W, C, S())
     return z
 
 
@@ -811,7 +793,7 @@ def stem_space_to_depth(x_nchw, dtype):
     assert C == 3
     cp = chunk_channels(dtype)
     y = torch.empty(N, H // 2, W // 2, cp, dtype=dtype, device=x_nchw.device)
-    _call("dh_stem_space_to_depth", _ci(_DT[dtype]), P(x_nchw), P(y), _ci(N), _ci(H), _ci(W), _ci(cp), S())
+    _call("dh_stem_space_to_depth", _DT[dtype], P(x_nchw), P(y), N, H, W, cp, S())
     return y
 
 
@@ -819,7 +801,7 @@ def stem_pack_weight(w, dtype, out_scale=None):
     O = w.shape[0]
     cp = chunk_channels(dtype)
     out = torch.empty(16, O, cp, dtype=dtype, device=w.device)
-    _call("dh_stem_pack_weight", _ci(_DT[dtype]), P(w), P(out_scale), P(out), _ci(O), _ci(cp), S())
+    _call("dh_stem_pack_weight", _DT[dtype], P(w), P(out_scale), P(out), O, cp, S())
     return out
 
 
@@ -833,8 +815,7 @@ def stem7_fwd(x1, x2, w, out_scale=None, bias=None, relu=False, want_stats=False
     stats = torch.empty(2, 64, nt, dtype=torch.float32, device=x1.device) if want_stats else None
     xs = torch.empty(N, H // 2, W // 2, 16, dtype=torch.bfloat16, device=x1.device) if want_xs else None
     with _Prof("stem7_fwd", 2.0 * N * (H // 2) * (W // 2) * 64 * 147, _nb(x1, x2, y, xs)):
-        _call("dh_stem7_fwd", P(x1), P(x2), _ci(B), _ci(N), _ci(H), _ci(W), P(w), P(out_scale), P(bias), _ci(int(relu)), P(y),
-              P(stats), _ci(groups), P(xs), S())
+        _call("dh_stem7_fwd", P(x1), P(x2), B, N, H, W, P(w), P(out_scale), P(bias), relu, P(y), P(stats), groups, P(xs), S())
     return y, stats, xs
 
 
@@ -848,8 +829,8 @@ def stem_pool_bn_bwd(arg, dpool, y, scale, shift, mean, invstd, gamma, dgamma, d
     ws = workspace(L.dh_stem_pool_bn_bwd_workspace_size(C, groups), y.device)
     assert extra is None or (extra.shape == y.shape and extra.dtype == y.dtype)
     with _Prof("bn_bwd", 0, _nb(arg, dpool, y, d, extra)):
-        _call("dh_stem_pool_bn_bwd_plus", P(arg), P(dpool), P(extra), P(y), P(scale), P(shift), P(mean), P(invstd), P(gamma), _ci(N), _ci(H),
-              _ci(W), _ci(C), _ci(groups), P(d), P(coef), P(dgamma), P(dbeta), _ci(int(accumulate)), P(ws), S())
+        _call("dh_stem_pool_bn_bwd_plus", P(arg), P(dpool), P(extra), P(y), P(scale), P(shift), P(mean), P(invstd), P(gamma), N,
+              H, W, C, groups, P(d), P(coef), P(dgamma), P(dbeta), accumulate, P(ws), S())
     return d, coef
 
 
@@ -864,11 +845,10 @@ def stem_wgrad(x_s2d, dy, dw, accumulate=False, use_tr=True, bn=None):
         L = _lib.lib()
         ws = workspace(L.dh_conv2d_wgrad_workspace_size(N, H2, W2, 16, O, 4, 1), dy.device)
         with _Prof("conv_wgrad<bf16,ks4,s1>", 2.0 * N * H2 * W2 * O * 16 * 16, _nb(x_s2d, dy, y)):
-            _call("dh_stem_wgrad_bn", P(x_s2d), P(dy), P(y), P(coef), _ci(groups), _ci(N), _ci(H2), _ci(W2), P(dw2),
-                  _ci(int(use_tr)), P(ws), S())
+            _call("dh_stem_wgrad_bn", P(x_s2d), P(dy), P(y), P(coef), groups, N, H2, W2, P(dw2), use_tr, P(ws), S())
     else:
         conv2d_wgrad(x_s2d, dy, dw2, ks=4, stride=1, pad=2, use_tr=use_tr, cin=16, defer=False)     # dw2 is unpacked next
-    _call("dh_stem_unpack_grad", P(dw2), P(dw), _ci(O), _ci(16), _ci(int(accumulate)), S())
+    _call("dh_stem_unpack_grad", P(dw2), P(dw), O, 16, accumulate, S())
 
 
 # ---- normalisation -------------------------------------------------------------------------------
@@ -878,8 +858,8 @@ def bn_finalize(stats, C, groups, count, gamma, beta, running_mean, running_var,
     dev = stats.device
     mean = torch.empty(groups, C, dtype=torch.float32, device=dev)
     invstd, scale, shift = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-    _call("dh_bn_finalize", P(stats), _ci(nt), _ci(cp), _ci(C), _ci(groups), _cd(float(count)), P(gamma), P(beta),
-          P(running_mean), P(running_var), _cf(momentum), _cf(eps), P(mean), P(invstd), P(scale), P(shift), P(nbt), S())
+    _call("dh_bn_finalize", P(stats), nt, cp, C, groups, float(count), P(gamma), P(beta), P(running_mean), P(running_var),
+          momentum, eps, P(mean), P(invstd), P(scale), P(shift), P(nbt), S())
     return mean, invstd, scale, shift
 
 
@@ -887,7 +867,7 @@ def bn_eval_params(gamma, beta, rm, rv, eps=1e-5):
     C = gamma.numel()
     scale = torch.empty(1, C, dtype=torch.float32, device=gamma.device)
     shift = torch.empty_like(scale)
-    _call("dh_bn_eval_params", P(gamma), P(beta), P(rm), P(rv), _cf(eps), _ci(C), P(scale), P(shift), S())
+    _call("dh_bn_eval_params", P(gamma), P(beta), P(rm), P(rv), eps, C, P(scale), P(shift), S())
     return scale, shift
 
 
@@ -906,11 +886,9 @@ def bn_apply(x, scale, shift, groups=1, act=ACT_NONE, residual=None, want_bits=F
         bits = torch.empty(x.numel() // v, dtype=torch.uint8, device=x.device)
     with _Prof("bn_apply", 0, _nb(x, residual, y)):
         if bits is not None:
-            _call("dh_bn_apply_bits", _ci(dt(x)), P(x), P(residual), P(y), P(scale), P(shift), _cl(npix), _ci(C), _ci(groups),
-                  _ci(act), P(bits), S())
+            _call("dh_bn_apply_bits", dt(x), P(x), P(residual), P(y), P(scale), P(shift), npix, C, groups, act, P(bits), S())
         else:
-            _call("dh_bn_apply", _ci(dt(x)), P(x), P(residual), P(y), P(scale), P(shift), _cl(npix), _ci(C), _ci(groups),
-                  _ci(act), S())
+            _call("dh_bn_apply", dt(x), P(x), P(residual), P(y), P(scale), P(shift), npix, C, groups, act, S())
     return (y, bits) if want_bits else y
 
 
@@ -973,30 +951,28 @@ def bn_bwd(dout, out_relu, x, mean, invstd, gamma, dgamma, dbeta, groups=1, accu
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
     L = _lib.lib()
-    ws = workspace(L.dh_bn_bwd_workspace_size(_cl(npix), C, groups), x.device)
+    ws = workspace(L.dh_bn_bwd_workspace_size(npix, C, groups), x.device)
     if BN_BWD_PERSIST and not _PERSIST_BLOCK and \
-            (L.dh_bn_bwd_persist_preferred if BN_BWD_PERSIST is True else L.dh_bn_bwd_persist_supported)(
-            _ci(dt(x)), _cl(npix), C, groups):
+            (L.dh_bn_bwd_persist_preferred if BN_BWD_PERSIST is True else L.dh_bn_bwd_persist_supported)(dt(x), npix, C, groups):
         # one persistent launch, tensors held on chip across a device-wide barrier: every tensor is read once
         global BN_PERSIST_LAUNCHES
         BN_PERSIST_LAUNCHES += 1
         with _Prof("bn_bwd", 0, _nb(dout, bits if bits is not None else out_relu, x) + _nb(dx, dres)):
             if bits is not None:
-                _call("dh_bn_bwd_persist_bits", P(dout), P(bits), P(x), P(mean), P(invstd), P(gamma), _cl(npix), _ci(C),
-                      _ci(groups), P(dx), P(dres), P(dgamma), P(dbeta), _ci(int(accumulate)), P(ws), P(bn_sync_words(x.device)), S())
+                _call("dh_bn_bwd_persist_bits", P(dout), P(bits), P(x), P(mean), P(invstd), P(gamma), npix, C, groups, P(dx),
+                      P(dres), P(dgamma), P(dbeta), accumulate, P(ws), P(bn_sync_words(x.device)), S())
             else:
-                _call("dh_bn_bwd_persist", P(dout), P(out_relu), P(x), P(mean), P(invstd), P(gamma), _cl(npix), _ci(C),
-                      _ci(groups), P(dx), P(dres), P(dgamma), P(dbeta), _ci(int(accumulate)), P(mask_scale), P(mask_shift),
-                      P(ws), P(bn_sync_words(x.device)), S())
+                _call("dh_bn_bwd_persist", P(dout), P(out_relu), P(x), P(mean), P(invstd), P(gamma), npix, C, groups, P(dx),
+                      P(dres), P(dgamma), P(dbeta), accumulate, P(mask_scale), P(mask_shift), P(ws), P(bn_sync_words(x.device)), S())
         return (dx, dres) if want_dres else dx
     # two passes (reduce, apply): dout / x (/ out) are read twice, dx (/ dres) written once
     with _Prof("bn_bwd", 0, 2 * _nb(dout, bits if bits is not None else out_relu, x) + _nb(dx, dres)):
         if bits is not None:
-            _call("dh_bn_bwd_bits", _ci(dt(x)), P(dout), P(bits), P(x), P(mean), P(invstd), P(gamma), _cl(npix), _ci(C),
-                  _ci(groups), P(dx), P(dres), P(dgamma), P(dbeta), _ci(int(accumulate)), P(ws), S())
+            _call("dh_bn_bwd_bits", dt(x), P(dout), P(bits), P(x), P(mean), P(invstd), P(gamma), npix, C, groups, P(dx), P(dres),
+                  P(dgamma), P(dbeta), accumulate, P(ws), S())
         else:
-            _call("dh_bn_bwd", _ci(dt(x)), P(dout), P(out_relu), P(x), P(mean), P(invstd), P(gamma), _cl(npix), _ci(C),
-                  _ci(groups), P(dx), P(dres), P(dgamma), P(dbeta), _ci(int(accumulate)), P(mask_scale), P(mask_shift), P(ws), S())
+            _call("dh_bn_bwd", dt(x), P(dout), P(out_relu), P(x), P(mean), P(invstd), P(gamma), npix, C, groups, P(dx), P(dres),
+                  P(dgamma), P(dbeta), accumulate, P(mask_scale), P(mask_shift), P(ws), S())
     return (dx, dres) if want_dres else dx
 
 
@@ -1008,8 +984,8 @@ def bn_bwd_from_partials(g, x, partial, mean, invstd, gamma, dgamma, dbeta, grou
     assert cp == C and g.shape == x.shape
     dx = torch.empty_like(x)
     ws = workspace(groups * 2 * C * 4, x.device)
-    _call("dh_bn_bwd_from_partials", _ci(dt(x)), P(g), P(x), P(partial), _ci(nt), P(mean), P(invstd), P(gamma), _cl(npix),
-          _ci(C), _ci(groups), P(dx), P(dgamma), P(dbeta), _ci(int(accumulate)), P(ws), S())
+    _call("dh_bn_bwd_from_partials", dt(x), P(g), P(x), P(partial), nt, P(mean), P(invstd), P(gamma), npix, C, groups, P(dx),
+          P(dgamma), P(dbeta), accumulate, P(ws), S())
     return dx
 
 
@@ -1017,7 +993,7 @@ def layernorm(x2d, gamma, beta, eps=1e-5, want_stats=True):
     rows, C = x2d.shape
     y = torch.empty_like(x2d)
     stats = torch.empty(rows, 2, dtype=torch.float32, device=x2d.device) if want_stats else None
-    _call("dh_layernorm_fwd", _ci(dt(x2d)), P(x2d), P(gamma), P(beta), P(y), P(stats), _cl(rows), _ci(C), _cf(eps), S())
+    _call("dh_layernorm_fwd", dt(x2d), P(x2d), P(gamma), P(beta), P(y), P(stats), rows, C, eps, S())
     return (y, stats) if want_stats else y
 
 
@@ -1025,9 +1001,9 @@ def layernorm_bwd(dy, x2d, stats, gamma, dgamma, dbeta, dx_add=None, accumulate=
     rows, C = x2d.shape
     dx = torch.empty_like(x2d)
     L = _lib.lib()
-    ws = workspace(L.dh_layernorm_bwd_workspace_size(_cl(rows)), x2d.device)
-    _call("dh_layernorm_bwd", _ci(dt(x2d)), P(dy), P(x2d), P(stats), P(gamma), P(dx), P(dx_add), P(dgamma), P(dbeta),
-          _ci(int(accumulate)), _cl(rows), _ci(C), P(ws), S())
+    ws = workspace(L.dh_layernorm_bwd_workspace_size(rows), x2d.device)
+    _call("dh_layernorm_bwd", dt(x2d), P(dy), P(x2d), P(stats), P(gamma), P(dx), P(dx_add), P(dgamma), P(dbeta), accumulate, rows,
+          C, P(ws), S())
     return dx
 
 
@@ -1036,7 +1012,7 @@ def nchw_to_nhwc(x, dtype, cpad=0):
     N, C, H, W = x.shape
     cp = max(C, cpad)
     y = torch.empty(N, H, W, cp, dtype=dtype, device=x.device)
-    _call("dh_nchw_to_nhwc", _ci(_DT[dtype]), P(x), P(y), _ci(N), _ci(C), _cl(H * W), _ci(cp), S())
+    _call("dh_nchw_to_nhwc", _DT[dtype], P(x), P(y), N, C, H * W, cp, S())
     return y
 
 
@@ -1048,10 +1024,10 @@ def head_dgrad3x3(dy, w_oihw, ncls, relu_out=None):
     dx = torch.empty(N, H, W, 32, dtype=dy.dtype, device=dy.device)
     if relu_out is not None:
         if dy.dtype == torch.bfloat16 and CP == 8 and ncls <= 2:
-            _call("dh_head_dgrad3x3_relu", P(dy), P(w_oihw), _ci(ncls), P(relu_out), P(dx), _ci(N), _ci(H), _ci(W), S())
+            _call("dh_head_dgrad3x3_relu", P(dy), P(w_oihw), ncls, P(relu_out), P(dx), N, H, W, S())
             return dx
         return act_bwd(head_dgrad3x3(dy, w_oihw, ncls), relu_out, ACT_RELU)
-    _call("dh_head_dgrad3x3", _ci(dt(dy)), P(dy), _ci(CP), P(w_oihw), _ci(ncls), P(dx), _ci(N), _ci(H), _ci(W), S())
+    _call("dh_head_dgrad3x3", dt(dy), P(dy), CP, P(w_oihw), ncls, P(dx), N, H, W, S())
     return dx
 
 
@@ -1064,8 +1040,8 @@ def head_dgrad3x3_bn(dy, w_oihw, ncls, y, scale, shift, mean, invstd, groups):
     nb = _lib.lib().dh_head_dgrad3x3_bn_blocks(N, H, W, groups)
     partial = torch.empty(2, 32, nb, dtype=torch.float32, device=dy.device)
     with _Prof("bn_bwd", 0, _nb(dy, y, g)):
-        _call("dh_head_dgrad3x3_bn", P(dy), P(w_oihw), _ci(ncls), P(y), P(scale), P(shift), P(mean), P(invstd), _ci(groups), P(g),
-              P(partial), _ci(N), _ci(H), _ci(W), S())
+        _call("dh_head_dgrad3x3_bn", P(dy), P(w_oihw), ncls, P(y), P(scale), P(shift), P(mean), P(invstd), groups, P(g),
+              P(partial), N, H, W, S())
     return g, partial
 
 
@@ -1075,7 +1051,7 @@ def head_dlogits_pack(dl_nchw, dtype=torch.bfloat16):
     N, C, H, W = dl_nchw.shape
     assert C <= 8 and dl_nchw.dtype == torch.float32 and dl_nchw.is_contiguous()
     dlp = torch.empty(_head_dlp_shape(N, H, W, C, dtype), dtype=torch.int32, device=dl_nchw.device)
-    _call("dh_head_dlogits_pack", _ci(_DT[dtype]), P(dl_nchw), _ci(N), _ci(C), _ci(H), _ci(W), P(dlp), S())
+    _call("dh_head_dlogits_pack", _DT[dtype], P(dl_nchw), N, C, H, W, P(dlp), S())
     return dlp
 
 
@@ -1103,8 +1079,8 @@ def head_bn_bwd(dlp, w_oihw, ncls, y, scale, shift, mean, invstd, gamma, dgamma,
     dx = torch.empty_like(y)
     ws = workspace(_lib.lib().dh_head_bn_bwd_workspace_size(N, H, W, groups), y.device)
     with _Prof("bn_bwd", 0, _nb(y, y, dx)):
-        _call("dh_head_bn_bwd", _ci(dt(y)), P(dlp), P(w_oihw), _ci(ncls), P(y), P(scale), P(shift), P(mean), P(invstd), P(gamma),
-              _ci(groups), P(dx), P(dgamma), P(dbeta), P(dw), P(db), _ci(1 if accumulate else 0), _ci(N), _ci(H), _ci(W), P(ws), S())
+        _call("dh_head_bn_bwd", dt(y), P(dlp), P(w_oihw), ncls, P(y), P(scale), P(shift), P(mean), P(invstd), P(gamma), groups,
+              P(dx), P(dgamma), P(dbeta), P(dw), P(db), 1 if accumulate else 0, N, H, W, P(ws), S())
     return dx
 
 
@@ -1117,22 +1093,22 @@ def head_relu_bwd(dlp, w_oihw, ncls, relu_out, dw, db, accumulate=True):
     dx = torch.empty_like(relu_out)
     ws = workspace(_lib.lib().dh_head_bn_bwd_workspace_size(N, H, W, 1), dlp.device)
     with _Prof("act_bwd", 0, _nb(relu_out, dx)):
-        _call("dh_head_relu_bwd", _ci(dt(relu_out)), P(dlp), P(w_oihw), _ci(ncls), P(relu_out), P(dx), P(dw), P(db),
-              _ci(1 if accumulate else 0), _ci(N), _ci(H), _ci(W), P(ws), S())
+        _call("dh_head_relu_bwd", dt(relu_out), P(dlp), P(w_oihw), ncls, P(relu_out), P(dx), P(dw), P(db), 1 if accumulate else 0,
+              N, H, W, P(ws), S())
     return dx
 
 
 def nhwc_to_nchw(x):
     N, H, W, C = x.shape
     y = torch.empty(N, C, H, W, dtype=torch.float32, device=x.device)
-    _call("dh_nhwc_to_nchw", _ci(dt(x)), P(x), P(y), _ci(N), _ci(C), _cl(H * W), S())
+    _call("dh_nhwc_to_nchw", dt(x), P(x), P(y), N, C, H * W, S())
     return y
 
 
 def copy_channels(src, sc0, dst, dc0, cn):
     Cs, Cd = src.shape[-1], dst.shape[-1]
     Pn = src.numel() // Cs
-    _call("dh_copy_channels", _ci(dt(src)), P(src), _ci(Cs), _ci(sc0), P(dst), _ci(Cd), _ci(dc0), _ci(cn), _cl(Pn), S())
+    _call("dh_copy_channels", dt(src), P(src), Cs, sc0, P(dst), Cd, dc0, cn, Pn, S())
 
 
 # ---- small element-wise launches of independent levels, recorded and issued as one job-table launch (dh_ew_multi) ----
@@ -1164,7 +1140,7 @@ def ew_flush():
     i0 = (ctypes.c_int * n)(*[j[4] for j in _EW_BATCH])
     i1 = (ctypes.c_int * n)(*[j[5] for j in _EW_BATCH])
     l0 = (ctypes.c_long * n)(*[j[6] for j in _EW_BATCH])
-    _call("dh_ew_multi", _ci(n), ops_, a, b, c, i0, i1, l0, S())
+    _call("dh_ew_multi", n, ops_, a, b, c, i0, i1, l0, S())
     del _EW_BATCH[:]
 
 
@@ -1175,7 +1151,7 @@ def cat_halves(t):
     assert t.is_contiguous()
     if t.dtype == torch.bfloat16 and c % 8 == 0 and _ew_record(EW_CAT_HALVES, t, None, cat, c, 0, (n // 2) * h * w):
         return cat
-    _call("dh_cat_halves", _ci(dt(t)), P(t), P(cat), _ci(c), _cl((n // 2) * h * w), _ci(0), S())
+    _call("dh_cat_halves", dt(t), P(t), P(cat), c, (n // 2) * h * w, 0, S())
     return cat
 
 
@@ -1186,13 +1162,13 @@ def split_halves(cat):
     assert cat.is_contiguous()
     if cat.dtype == torch.bfloat16 and (c2 // 2) % 8 == 0 and _ew_record(EW_SPLIT_HALVES, cat, None, t, c2 // 2, 0, n * h * w):
         return t
-    _call("dh_cat_halves", _ci(dt(cat)), P(t), P(cat), _ci(c2 // 2), _cl(n * h * w), _ci(1), S())
+    _call("dh_cat_halves", dt(cat), P(t), P(cat), c2 // 2, n * h * w, 1, S())
     return t
 
 
 def add(a, b):
     y = torch.empty_like(a)
-    _call("dh_add", _ci(dt(a)), P(a), P(b), P(y), _cl(a.numel()), S())
+    _call("dh_add", dt(a), P(a), P(b), P(y), a.numel(), S())
     return y
 
 
@@ -1202,7 +1178,7 @@ def add_pos(x, pos):
     assert x.is_contiguous() and pos.is_contiguous()
     if x.dtype == torch.bfloat16 and C % 8 == 0 and _ew_record(EW_ADD_POS, x, pos, y, N, C, H * W):
         return y
-    _call("dh_add_pos", _ci(dt(x)), P(x), P(pos), P(y), _ci(N), _cl(H * W), _ci(C), S())
+    _call("dh_add_pos", dt(x), P(x), P(pos), P(y), N, H * W, C, S())
     return y
 
 
@@ -1211,12 +1187,12 @@ def add_pos_bwd(dy, dpos, accumulate=False):
     assert dy.is_contiguous() and dpos.is_contiguous()
     if dy.dtype == torch.bfloat16 and C == 32 and _ew_record(EW_ADD_POS_BWD, dy, None, dpos, N, int(accumulate), H * W):
         return
-    _call("dh_add_pos_bwd", _ci(dt(dy)), P(dy), P(dpos), _ci(N), _cl(H * W), _ci(C), _ci(int(accumulate)), S())
+    _call("dh_add_pos_bwd", dt(dy), P(dy), P(dpos), N, H * W, C, accumulate, S())
 
 
 def act_bwd(dy, ref, act):
     dx = torch.empty_like(dy)
-    _call("dh_act_bwd", _ci(dt(dy)), P(dy), P(ref), P(dx), _cl(dy.numel()), _ci(act), S())
+    _call("dh_act_bwd", dt(dy), P(dy), P(ref), P(dx), dy.numel(), act, S())
     return dx
 
 
@@ -1226,43 +1202,42 @@ def maxpool(x, want_arg=False, bn=None):
     y = torch.empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=x.dtype, device=x.device)
     arg = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if want_arg else None
     sc, sh, groups = bn if bn is not None else (None, None, 0)
-    _call("dh_maxpool3x3s2_fwd", _ci(dt(x)), P(x), P(y), P(arg), _ci(N), _ci(H), _ci(W), _ci(C), P(sc), P(sh), _ci(groups),
-          S())
+    _call("dh_maxpool3x3s2_fwd", dt(x), P(x), P(y), P(arg), N, H, W, C, P(sc), P(sh), groups, S())
     return (y, arg) if want_arg else y
 
 
 def maxpool_bwd(arg, dy, in_shape):
     N, H, W, C = in_shape
     dx = torch.empty(N, H, W, C, dtype=dy.dtype, device=dy.device)
-    _call("dh_maxpool3x3s2_bwd", _ci(dt(dy)), P(arg), P(dy), P(dx), _ci(N), _ci(H), _ci(W), _ci(C), S())
+    _call("dh_maxpool3x3s2_bwd", dt(dy), P(arg), P(dy), P(dx), N, H, W, C, S())
     return dx
 
 
 def upsample2(x):
     N, H, W, C = x.shape
     y = torch.empty(N, 2 * H, 2 * W, C, dtype=x.dtype, device=x.device)
-    _call("dh_upsample2_nearest_fwd", _ci(dt(x)), P(x), P(y), _ci(N), _ci(H), _ci(W), _ci(C), S())
+    _call("dh_upsample2_nearest_fwd", dt(x), P(x), P(y), N, H, W, C, S())
     return y
 
 
 def upsample2_bwd(dy):
     N, H2, W2, C = dy.shape
     dx = torch.empty(N, H2 // 2, W2 // 2, C, dtype=dy.dtype, device=dy.device)
-    _call("dh_upsample2_nearest_bwd", _ci(dt(dy)), P(dy), P(dx), _ci(N), _ci(H2 // 2), _ci(W2 // 2), _ci(C), S())
+    _call("dh_upsample2_nearest_bwd", dt(dy), P(dy), P(dx), N, H2 // 2, W2 // 2, C, S())
     return dx
 
 
 def absdiff_upsample4(a, b):
     N, H, W, C = a.shape
     y = torch.empty(N, 4 * H, 4 * W, C, dtype=a.dtype, device=a.device)
-    _call("dh_absdiff_upsample4_fwd", _ci(dt(a)), P(a), P(b), P(y), _ci(N), _ci(H), _ci(W), _ci(C), S())
+    _call("dh_absdiff_upsample4_fwd", dt(a), P(a), P(b), P(y), N, H, W, C, S())
     return y
 
 
 def absdiff_upsample4_bwd(a, b, dy):
     N, H, W, C = a.shape
     da, db = torch.empty_like(a), torch.empty_like(b)
-    _call("dh_absdiff_upsample4_bwd", _ci(dt(a)), P(a), P(b), P(dy), P(da), P(db), _ci(N), _ci(H), _ci(W), _ci(C), S())
+    _call("dh_absdiff_upsample4_bwd", dt(a), P(a), P(b), P(dy), P(da), P(db), N, H, W, C, S())
     return da, db
 
 
@@ -1276,40 +1251,40 @@ def conv3x3_dgrad_through_up4(dy, wdgrad, a, b, da=None, db=None):
     L = _lib.lib()
     partial = torch.empty(L.dh_conv3x3_dgrad_up4_partial_floats(N, 4 * H, 4 * W), dtype=torch.float32, device=a.device)
     with _Prof("conv_mfma<bf16,ks3,s1,nt32>", 2.0 * N * 16 * H * W * 32 * dy.shape[-1] * 9, _nb(dy, wdgrad, partial)):
-        _call("dh_conv3x3_dgrad_up4", _ci(dt(dy)), P(dy), P(wdgrad), _ci(N), _ci(4 * H), _ci(4 * W), _ci(dy.shape[-1]), P(partial), S())
+        _call("dh_conv3x3_dgrad_up4", dt(dy), P(dy), P(wdgrad), N, 4 * H, 4 * W, dy.shape[-1], P(partial), S())
     da = torch.empty_like(a) if da is None else da
     db = torch.empty_like(b) if db is None else db
-    _call("dh_absdiff_up4_combine", P(partial), P(a), P(b), P(da), P(db), _ci(N), _ci(H), _ci(W), S())
+    _call("dh_absdiff_up4_combine", P(partial), P(a), P(b), P(da), P(db), N, H, W, S())
     return da, db
 
 
 def absdiff(a, b):
     y = torch.empty_like(a)
-    _call("dh_absdiff", _ci(dt(a)), P(a), P(b), P(y), _cl(a.numel()), S())
+    _call("dh_absdiff", dt(a), P(a), P(b), P(y), a.numel(), S())
     return y
 
 
 def absdiff_bwd(a, b, dy, da, db, accumulate=True):
-    _call("dh_absdiff_bwd", _ci(dt(a)), P(a), P(b), P(dy), P(da), P(db), _cl(a.numel()), _ci(int(accumulate)), S())
+    _call("dh_absdiff_bwd", dt(a), P(a), P(b), P(dy), P(da), P(db), a.numel(), accumulate, S())
 
 
 def colsum(x2d, out, accumulate=False):
     C = x2d.shape[-1]
     Pn = x2d.numel() // C
     ws = workspace(1024 * C * 4 + 1024, x2d.device)          # up to 1024 partial rows
-    _call("dh_colsum", _ci(dt(x2d)), P(x2d), _cl(Pn), _ci(C), P(out), _ci(int(accumulate)), P(ws), S())
+    _call("dh_colsum", dt(x2d), P(x2d), Pn, C, P(out), accumulate, P(ws), S())
 
 
 def cast_from_f32(src, dtype):
     dst = torch.empty(src.shape, dtype=dtype, device=src.device)
-    _call("dh_cast_from_f32", _ci(_DT[dtype]), P(src), P(dst), _cl(src.numel()), S())
+    _call("dh_cast_from_f32", _DT[dtype], P(src), P(dst), src.numel(), S())
     return dst
 
 
 def cast_to_f32(src, dst=None, accumulate=False):
     if dst is None:
         dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
-    _call("dh_cast_to_f32", _ci(dt(src)), P(src), P(dst), _cl(src.numel()), _ci(int(accumulate)), S())
+    _call("dh_cast_to_f32", dt(src), P(src), P(dst), src.numel(), accumulate, S())
     return dst
 
 
@@ -1325,8 +1300,7 @@ def tokenizer_fwd(x, wa, pos, B, L):
     pooled = torch.empty(Sn, L, 32, dtype=torch.float32, device=dev)
     tok = torch.empty(B, 2 * L, 32, dtype=torch.float32, device=dev)
     nws = _lib.lib().dh_tokenizer_fwd_workspace_size(Sn, HW, L)
-    args = lambda ws: (_ci(dt(x)), P(x), P(wa), P(pos), _ci(Sn), _ci(B), _ci(HW), _ci(L), P(logits), P(stats), P(pooled),
-                       P(tok), P(ws), S())
+    args = lambda ws: (dt(x), P(x), P(wa), P(pos), Sn, B, HW, L, P(logits), P(stats), P(pooled), P(tok), P(ws), S())
     if _XPREP_BATCH is not None and _ENC_BATCH is not None:
         # recorded (EncoderBatch): issued with the other levels' tokenizers, right before the recorded encoder stacks that read
         # the tokens -- scratch of its own until then.  (A caller that reads `tok` with an immediate launch instead calls
@@ -1359,12 +1333,12 @@ def tokenizer_bwd(x, wa, saved, dtok_cat, dx_accum, dwa, dpos, B, L, accumulate=
     else:
         ws = workspace(nws, x.device)
     assert dtok_cat.dtype == torch.float32
-    _call("dh_tokenizer_bwd", _ci(dt(x)), P(x), P(wa), _ci(Sn), _ci(B), _ci(HW), _ci(L), P(logits), P(stats), P(pooled),
-          P(dtok_cat), P(dx_accum), P(dwa), P(dpos), _ci(int(accumulate)), P(ws), S())
+    _call("dh_tokenizer_bwd", dt(x), P(x), P(wa), Sn, B, HW, L, P(logits), P(stats), P(pooled), P(dtok_cat), P(dx_accum), P(dwa),
+          P(dpos), accumulate, P(ws), S())
 
 
 def prep_mfma_supported(dtype, Sn, L, heads, dim_head, HLP):
-    return bool(_lib.lib().dh_xattn_prep_mfma_supported(_ci(_DT[dtype]), _ci(Sn), _ci(L), _ci(heads), _ci(dim_head), _ci(HLP)))
+    return bool(_lib.lib().dh_xattn_prep_mfma_supported(_DT[dtype], Sn, L, heads, dim_head, HLP))
 
 
 DEC_RECORD = None    # set to [] by bench.py for ONE eager step: every fused-decoder call (layer / stack, forward / backward /
@@ -1413,15 +1387,13 @@ class XattnPrep:
         if self.mfma:
             wk, wv, wo, wqT = masters
             with _XprepPaused():
-                _call("dh_xattn_prep_fwd_stack_mfma", P(tok), _cl(bstride), _cl(sstride), _ci(B), _ci(Sn), _ci(heads),
-                      _ci(dim_head), _ci(self.HLP), _cf(scale), _cf(eps), _ci(1), _cl(0), P(ln_g), P(ln_b), P(wk), P(wv), P(wo),
-                      P(wqT), P(self.mn), P(self.mstats), P(self.k), P(self.v), P(self.kq), P(self.kqT), P(self.vo),
-                      P(self.voT), S())
+                _call("dh_xattn_prep_fwd_stack_mfma", P(tok), bstride, sstride, B, Sn, heads, dim_head, self.HLP, scale, eps, 1,
+                      0, P(ln_g), P(ln_b), P(wk), P(wv), P(wo), P(wqT), P(self.mn), P(self.mstats), P(self.k), P(self.v),
+                      P(self.kq), P(self.kqT), P(self.vo), P(self.voT), S())
             return
-        _call("dh_xattn_prep_fwd", _ci(_DT[dtype]), P(tok), _cl(bstride), _cl(sstride), _ci(B), _ci(Sn), _ci(L),
-              _ci(heads), _ci(dim_head), _ci(self.HLP), _cf(scale), _cf(eps), P(ln_g), P(ln_b), P(wq), P(wkT), P(wvT),
-              P(woT), P(self.mn), P(self.mstats), P(self.k), P(self.v), P(self.kq), P(self.kqT), P(self.vo),
-              P(self.voT), S())
+        _call("dh_xattn_prep_fwd", _DT[dtype], P(tok), bstride, sstride, B, Sn, L, heads, dim_head, self.HLP, scale, eps, P(ln_g),
+              P(ln_b), P(wq), P(wkT), P(wvT), P(woT), P(self.mn), P(self.mstats), P(self.k), P(self.v), P(self.kq), P(self.kqT),
+              P(self.vo), P(self.voT), S())
 
 
 class _PrepView:
@@ -1464,20 +1436,18 @@ class XattnPrepStack:
             if _XPREP_BATCH is not None and not record:
                 _lib.lib().dh_xprep_batch_pause(1)
             try:
-                _call("dh_xattn_prep_fwd_stack_mfma", P(tok), _cl(bstride), _cl(sstride), _ci(B), _ci(Sn), _ci(heads),
-                      _ci(dim_head), _ci(self.HLP), _cf(scale), _cf(eps), _ci(layers), _cl(param_stride), P(ln_g0), P(ln_b0),
-                      P(wk0), P(wv0), P(wo0), P(wqT), P(self.mn), P(self.mstats), P(self.k), P(self.v), P(self.kq), P(self.kqT),
-                      P(self.vo), P(self.voT), S())
+                _call("dh_xattn_prep_fwd_stack_mfma", P(tok), bstride, sstride, B, Sn, heads, dim_head, self.HLP, scale, eps,
+                      layers, param_stride, P(ln_g0), P(ln_b0), P(wk0), P(wv0), P(wo0), P(wqT), P(self.mn), P(self.mstats),
+                      P(self.k), P(self.v), P(self.kq), P(self.kqT), P(self.vo), P(self.voT), S())
             finally:
                 if _XPREP_BATCH is not None and not record:
                     _lib.lib().dh_xprep_batch_pause(0)
             if _XPREP_BATCH is not None and record:
                 _XPREP_BATCH.append(tok)
             return
-        _call("dh_xattn_prep_fwd_stack", _ci(_DT[dtype]), P(tok), _cl(bstride), _cl(sstride), _ci(B), _ci(Sn), _ci(L),
-              _ci(heads), _ci(dim_head), _ci(self.HLP), _cf(scale), _cf(eps), _ci(layers), _cl(param_stride), P(ln_g0),
-              P(ln_b0), P(wq0), P(wkT), P(wvT), P(woT), P(self.mn), P(self.mstats), P(self.k), P(self.v), P(self.kq),
-              P(self.kqT), P(self.vo), P(self.voT), S())
+        _call("dh_xattn_prep_fwd_stack", _DT[dtype], P(tok), bstride, sstride, B, Sn, L, heads, dim_head, self.HLP, scale, eps,
+              layers, param_stride, P(ln_g0), P(ln_b0), P(wq0), P(wkT), P(wvT), P(woT), P(self.mn), P(self.mstats), P(self.k),
+              P(self.v), P(self.kq), P(self.kqT), P(self.vo), P(self.voT), S())
 
     def layer(self, i):
         v = _PrepView()
@@ -1503,16 +1473,15 @@ class XattnPrepStack:
                 _call("dh_decoder_batch_launch", S())
         if self.mfma:
             wq0, woT, wkT, wvT = self._bwd_ops
-            _call("dh_xattn_prep_bwd_stack_mfma", P(tok), P(dtok_accum), _cl(bstride), _cl(sstride), _ci(B), _ci(Sn),
-                  _ci(heads), _ci(dim_head), _ci(self.HLP), _cf(self.scale), _ci(self.layers), _cl(self.param_stride),
-                  P(ln_g0), P(wq0), P(woT), P(wkT), P(wvT), P(self.mn), P(self.mstats), P(self.k), P(self.v), P(self.dkq),
-                  P(self.dvoT), P(dk), P(dv), P(dln_g0), P(dln_b0), P(dwq0), P(dwk0), P(dwv0), P(dwo0), _ci(1), P(ws), S())
+            _call("dh_xattn_prep_bwd_stack_mfma", P(tok), P(dtok_accum), bstride, sstride, B, Sn, heads, dim_head, self.HLP,
+                  self.scale, self.layers, self.param_stride, P(ln_g0), P(wq0), P(woT), P(wkT), P(wvT), P(self.mn),
+                  P(self.mstats), P(self.k), P(self.v), P(self.dkq), P(self.dvoT), P(dk), P(dv), P(dln_g0), P(dln_b0), P(dwq0),
+                  P(dwk0), P(dwv0), P(dwo0), 1, P(ws), S())
             return
-        _call("dh_xattn_prep_bwd_stack", _ci(_DT[self.dtype]), P(tok), P(dtok_accum), _cl(bstride), _cl(sstride), _ci(B),
-              _ci(Sn), _ci(L), _ci(heads), _ci(dim_head), _ci(self.HLP), _cf(self.scale), _ci(self.layers),
-              _cl(self.param_stride), P(ln_g0), P(wqT), P(wk0), P(wv0), P(wo0), P(self.mn), P(self.mstats), P(self.k),
-              P(self.v), P(self.dkq), P(self.dvoT), P(dk), P(dv), P(dln_g0), P(dln_b0), P(dwq0), P(dwk0), P(dwv0),
-              P(dwo0), _ci(1), P(ws), S())
+        _call("dh_xattn_prep_bwd_stack", _DT[self.dtype], P(tok), P(dtok_accum), bstride, sstride, B, Sn, L, heads, dim_head,
+              self.HLP, self.scale, self.layers, self.param_stride, P(ln_g0), P(wqT), P(wk0), P(wv0), P(wo0), P(self.mn),
+              P(self.mstats), P(self.k), P(self.v), P(self.dkq), P(self.dvoT), P(dk), P(dv), P(dln_g0), P(dln_b0), P(dwq0),
+              P(dwk0), P(dwv0), P(dwo0), 1, P(ws), S())
 
 
 def xattn_prep_bwd(prep, tok, dtok_accum, ln_g, wqT, wk, wv, wo, dkq, dvoT, dln_g, dln_b, dwq, dwk, dwv, dwo,
@@ -1525,16 +1494,14 @@ def xattn_prep_bwd(prep, tok, dtok_accum, ln_g, wqT, wk, wv, wo, dkq, dvoT, dln_
         wq0, woT, wkT, wvT = prep._bwd_ops
         ws = workspace(Lb.dh_xattn_prep_bwd_stack_workspace_size(Sn, L, 1), tok.device)
         with _XprepPaused():
-            _call("dh_xattn_prep_bwd_stack_mfma", P(tok), P(dtok_accum), _cl(bstride), _cl(sstride), _ci(B), _ci(Sn), _ci(heads),
-                  _ci(dim_head), _ci(prep.HLP), _cf(prep.scale), _ci(1), _cl(0), P(ln_g), P(wq0), P(woT), P(wkT), P(wvT),
-                  P(prep.mn), P(prep.mstats), P(prep.k), P(prep.v), P(dkq), P(dvoT), P(dk), P(dv), P(dln_g), P(dln_b), P(dwq),
-                  P(dwk), P(dwv), P(dwo), _ci(int(accumulate)), P(ws), S())
+            _call("dh_xattn_prep_bwd_stack_mfma", P(tok), P(dtok_accum), bstride, sstride, B, Sn, heads, dim_head, prep.HLP,
+                  prep.scale, 1, 0, P(ln_g), P(wq0), P(woT), P(wkT), P(wvT), P(prep.mn), P(prep.mstats), P(prep.k), P(prep.v),
+                  P(dkq), P(dvoT), P(dk), P(dv), P(dln_g), P(dln_b), P(dwq), P(dwk), P(dwv), P(dwo), accumulate, P(ws), S())
         return
     ws = workspace(Lb.dh_xattn_prep_bwd_workspace_size(Sn), tok.device)
-    _call("dh_xattn_prep_bwd", _ci(_DT[dtype]), P(tok), P(dtok_accum), _cl(bstride), _cl(sstride), _ci(B), _ci(Sn),
-          _ci(L), _ci(heads), _ci(dim_head), _ci(prep.HLP), _cf(prep.scale), P(ln_g), P(wqT), P(wk), P(wv), P(wo),
-          P(prep.mn), P(prep.mstats), P(prep.k), P(prep.v), P(dkq), P(dvoT), P(dk), P(dv), P(dln_g), P(dln_b), P(dwq),
-          P(dwk), P(dwv), P(dwo), _ci(int(accumulate)), P(ws), S())
+    _call("dh_xattn_prep_bwd", _DT[dtype], P(tok), P(dtok_accum), bstride, sstride, B, Sn, L, heads, dim_head, prep.HLP,
+          prep.scale, P(ln_g), P(wqT), P(wk), P(wv), P(wo), P(prep.mn), P(prep.mstats), P(prep.k), P(prep.v), P(dkq), P(dvoT),
+          P(dk), P(dv), P(dln_g), P(dln_b), P(dwq), P(dwk), P(dwv), P(dwo), accumulate, P(ws), S())
 
 
 @_dec_recorded("fwd", lambda a: a[0].shape[0], lambda a: 1, lambda a, k: a[12])
@@ -1543,8 +1510,8 @@ def decoder_layer_fwd(x2d, prep, rows_per_image, ln1_g, ln1_b, bo, ln2_g, ln2_b,
     fp8=True: the four MFMA products on OCP e4m3 operands (csrc/decoder_fp8.hip)"""
     y = torch.empty_like(x2d)
     with _Prof("decoder_layer_fwd", 0, _nb(x2d, y)):
-        _call("dh_decoder_layer_fwd_fp8" if fp8 else "dh_decoder_layer_fwd", P(x2d), P(y), P(prep.kq), P(prep.voT), P(ln1_g), P(ln1_b), P(bo), P(ln2_g), P(ln2_b),
-              P(w1), P(b1), P(w2), P(b2), _cl(x2d.shape[0]), _ci(rows_per_image), _ci(mlp), _cf(eps), S())
+        _call("dh_decoder_layer_fwd_fp8" if fp8 else "dh_decoder_layer_fwd", P(x2d), P(y), P(prep.kq), P(prep.voT), P(ln1_g),
+              P(ln1_b), P(bo), P(ln2_g), P(ln2_b), P(w1), P(b1), P(w2), P(b2), x2d.shape[0], rows_per_image, mlp, eps, S())
     if _DEC_BATCH is not None and not fp8:        # recorded: operands alive until the batch is issued
         _DEC_BATCH.extend((x2d, y, prep.kq, prep.voT))
     return y
@@ -1565,12 +1532,12 @@ def decoder_layer_bwd(x2d, dy, prep, rows_per_image, ln1_g, ln1_b, bo, ln2_g, ln
     if partial is not None:
         ws, gp = partial, [_vp(0)] * 9
     else:
-        ws = workspace(_lib.lib().dh_decoder_layer_bwd_workspace_size(_cl(rows), rows_per_image, mlp), x2d.device)
+        ws = workspace(_lib.lib().dh_decoder_layer_bwd_workspace_size(rows, rows_per_image, mlp), x2d.device)
         gp = [P(t) for t in grads]
     with _Prof("decoder_layer_bwd", 0, _nb(x2d, dy, dx)):
-        _call("dh_decoder_layer_bwd", P(x2d), P(dy), P(dx), P(prep.kq), P(prep.voT), P(prep.vo), P(prep.kqT), P(ln1_g),
-              P(ln1_b), P(bo), P(ln2_g), P(ln2_b), P(w1), P(w1T), P(b1), P(w2), P(w2T), P(b2), *gp,
-              P(dkq), P(dvoT), _cl(rows), _ci(rows_per_image), _ci(mlp), _cf(eps), P(ws), S())
+        _call("dh_decoder_layer_bwd", P(x2d), P(dy), P(dx), P(prep.kq), P(prep.voT), P(prep.vo), P(prep.kqT), P(ln1_g), P(ln1_b),
+              P(bo), P(ln2_g), P(ln2_b), P(w1), P(w1T), P(b1), P(w2), P(w2T), P(b2), *gp, P(dkq), P(dvoT), rows, rows_per_image,
+              mlp, eps, P(ws), S())
     if _DEC_BATCH is not None and partial is not None:
         _DEC_BATCH.extend((x2d, dy, dx, ws, prep.kq, prep.voT, prep.vo, prep.kqT))
     return dx, dkq, dvoT
@@ -1586,9 +1553,8 @@ def decoder_stack_fwd(x2d, stack, rows_per_image, params0, w1s, w2s, par_stride,
     ys = torch.empty(depth, rows, 32, dtype=x2d.dtype, device=x2d.device)
     g1, b1_, bo, g2, b2_, fb1, fb2 = params0
     with _Prof("decoder_layer_fwd", 0, depth * _nb(x2d, x2d)):
-        _call("dh_decoder_stack_fwd", P(x2d), P(ys), P(stack.kq), P(stack.voT), P(g1), P(b1_), P(bo), P(g2), P(b2_), P(w1s), P(fb1),
-              P(w2s), P(fb2), _ci(depth), _cl(stack.kq[0].numel()), _cl(w1s[0].numel()), _cl(par_stride), _cl(rows),
-              _ci(rows_per_image), _ci(mlp), _cf(eps), S())
+        _call("dh_decoder_stack_fwd", P(x2d), P(ys), P(stack.kq), P(stack.voT), P(g1), P(b1_), P(bo), P(g2), P(b2_), P(w1s),
+              P(fb1), P(w2s), P(fb2), depth, stack.kq[0].numel(), w1s[0].numel(), par_stride, rows, rows_per_image, mlp, eps, S())
     if _DEC_BATCH is not None:
         _DEC_BATCH.extend((x2d, ys, stack.kq, stack.voT, w1s, w2s))
     return ys
@@ -1604,24 +1570,23 @@ def decoder_stack_bwd(x2d, ys, dy, stack, rows_per_image, params0, w1s, w1Ts, w2
     assert partials.shape[0] == depth and partials.is_contiguous()
     with _Prof("decoder_layer_bwd", 0, depth * _nb(x2d, dy, dx)):
         _call("dh_decoder_stack_bwd", P(x2d), P(ys), P(dy), P(dx), P(dwork), P(stack.kq), P(stack.voT), P(stack.vo), P(stack.kqT),
-              P(g1), P(b1_), P(bo), P(g2), P(b2_), P(w1s), P(w1Ts), P(fb1), P(w2s), P(w2Ts), P(fb2), _ci(depth),
-              _cl(stack.kq[0].numel()), _cl(w1s[0].numel()), _cl(par_stride), _cl(rows), _ci(rows_per_image), _ci(mlp), _cf(eps),
-              P(partials), S())
+              P(g1), P(b1_), P(bo), P(g2), P(b2_), P(w1s), P(w1Ts), P(fb1), P(w2s), P(w2Ts), P(fb2), depth, stack.kq[0].numel(),
+              w1s[0].numel(), par_stride, rows, rows_per_image, mlp, eps, P(partials), S())
     if _DEC_BATCH is not None:
         _DEC_BATCH.extend((x2d, ys, dy, dx, dwork, partials, stack.kq, stack.voT, stack.vo, stack.kqT, w1s, w1Ts, w2s, w2Ts))
     return dx
 
 
 def decoder_layer_bwd_partial_floats(rows, rows_per_image, mlp):
-    return _lib.lib().dh_decoder_layer_bwd_workspace_size(_cl(rows), rows_per_image, mlp) // 4
+    return _lib.lib().dh_decoder_layer_bwd_workspace_size(rows, rows_per_image, mlp) // 4
 
 
 @_dec_recorded("fin", lambda a: a[1], lambda a: a[0].shape[0], lambda a, k: a[3])
 def decoder_stack_bwd_finalize(partials, rows, rows_per_image, mlp, grads0, grad_stride, dkq, dvoT):
     """one launch for the parameter gradients of all layers of a decoder stack: partials [depth, floats], grads0 = the nine
     gradient tensors of layer 0 (layer l's sit grad_stride floats further), dkq / dvoT [depth, images, 32, 32]"""
-    _call("dh_decoder_stack_bwd_finalize", P(partials), _ci(partials.shape[0]), _cl(rows), _ci(rows_per_image), _ci(mlp),
-          *(P(t) for t in grads0), _cl(grad_stride), P(dkq), P(dvoT), S())
+    _call("dh_decoder_stack_bwd_finalize", P(partials), partials.shape[0], rows, rows_per_image, mlp, *(P(t) for t in grads0),
+          grad_stride, P(dkq), P(dvoT), S())
 
 
 def encoder_supported(n, heads, dim_head, mlp):
@@ -1635,8 +1600,7 @@ def encoder_fwd(tok2d, B, n, depth, heads, dim_head, mlp, pstride, params, save,
     y = torch.empty_like(tok2d)
     xs = torch.empty(_lib.lib().dh_encoder_saved_floats(B, n, depth, heads, dim_head, mlp), dtype=torch.float32,
                      device=tok2d.device) if save else None          # [depth][B][forward image]
-    _call("dh_encoder_fwd", P(tok2d), P(y), P(xs), _ci(B), _ci(n), _ci(depth), _ci(heads), _ci(dim_head), _ci(mlp),
-          _cf(scale), _cf(eps), _cl(pstride), *(P(t) for t in params), S())
+    _call("dh_encoder_fwd", P(tok2d), P(y), P(xs), B, n, depth, heads, dim_head, mlp, scale, eps, pstride, *(P(t) for t in params), S())
     if _ENC_BATCH is not None:
         _ENC_BATCH.extend((tok2d, y, xs))
     return y, xs
@@ -1651,8 +1615,8 @@ def encoder_bwd(dy, xs, B, n, depth, heads, dim_head, mlp, pstride, params, grad
         _ENC_BATCH.extend((dy, dx, xs, ws))
     else:
         ws = workspace(nbytes, dy.device)
-    _call("dh_encoder_bwd", P(dy), P(dx), P(xs), _ci(B), _ci(n), _ci(depth), _ci(heads), _ci(dim_head), _ci(mlp),
-          _cf(scale), _cf(eps), _cl(pstride), *(P(t) for t in params), *(P(t) for t in grads), P(ws), S())
+    _call("dh_encoder_bwd", P(dy), P(dx), P(xs), B, n, depth, heads, dim_head, mlp, scale, eps, pstride, *(P(t) for t in params),
+          *(P(t) for t in grads), P(ws), S())
     return dx
 
 
@@ -1768,14 +1732,14 @@ class EncoderBatch:
 def softmax_groups(x2d, heads, L):
     rows, HLP = x2d.shape
     y = torch.empty_like(x2d)
-    _call("dh_softmax_groups_fwd", _ci(dt(x2d)), P(x2d), P(y), _cl(rows), _ci(heads), _ci(L), _ci(HLP), S())
+    _call("dh_softmax_groups_fwd", dt(x2d), P(x2d), P(y), rows, heads, L, HLP, S())
     return y
 
 
 def softmax_groups_bwd(y, dy, heads, L):
     rows, HLP = y.shape
     dx = torch.empty_like(y)
-    _call("dh_softmax_groups_bwd", _ci(dt(y)), P(y), P(dy), P(dx), _cl(rows), _ci(heads), _ci(L), _ci(HLP), S())
+    _call("dh_softmax_groups_bwd", dt(y), P(y), P(dy), P(dx), rows, heads, L, HLP, S())
     return dx
 
 
@@ -1783,15 +1747,13 @@ def self_attn(qkv, B, n, heads, dim_head, scale=32 ** -0.5):
     inner = heads * dim_head
     o = torch.empty(B * n, inner, dtype=qkv.dtype, device=qkv.device)
     attn = torch.empty(B, heads, n, n, dtype=torch.float32, device=qkv.device)
-    _call("dh_self_attn_fwd", _ci(dt(qkv)), P(qkv), P(o), P(attn), _ci(B), _ci(n), _ci(heads), _ci(dim_head),
-          _cf(scale), S())
+    _call("dh_self_attn_fwd", dt(qkv), P(qkv), P(o), P(attn), B, n, heads, dim_head, scale, S())
     return o, attn
 
 
 def self_attn_bwd(qkv, attn, dout, B, n, heads, dim_head, scale=32 ** -0.5):
     dqkv = torch.empty_like(qkv)
-    _call("dh_self_attn_bwd", _ci(dt(qkv)), P(qkv), P(attn), P(dout), P(dqkv), _ci(B), _ci(n), _ci(heads),
-          _ci(dim_head), _cf(scale), S())
+    _call("dh_self_attn_bwd", dt(qkv), P(qkv), P(attn), P(dout), P(dqkv), B, n, heads, dim_head, scale, S())
     return dqkv
 
 
@@ -1801,8 +1763,7 @@ def focal_loss(logits_nchw, target, want_grad=True, grad_scale=1.0, alpha=0.5):
     loss = torch.empty((), dtype=torch.float32, device=logits_nchw.device)
     dl = torch.empty_like(logits_nchw) if want_grad else None
     ws = workspace(4096, logits_nchw.device)
-    _call("dh_focal_loss", P(logits_nchw), P(target), _ci(B), _ci(C), _cl(H * W), _cf(alpha), _cf(grad_scale), P(loss),
-          P(dl), P(ws), S())
+    _call("dh_focal_loss", P(logits_nchw), P(target), B, C, H * W, alpha, grad_scale, P(loss), P(dl), P(ws), S())
     return loss, dl
 
 
@@ -1811,15 +1772,14 @@ def cross_entropy_fwd(logits_nchw, target, ignore_index=255):
     B, C, H, W = logits_nchw.shape
     out = torch.empty(2, dtype=torch.float32, device=logits_nchw.device)
     ws = workspace(16384, logits_nchw.device)
-    _call("dh_cross_entropy_fwd", P(logits_nchw), P(target), _ci(B), _ci(C), _cl(H * W), _ci(ignore_index), P(out), P(ws), S())
+    _call("dh_cross_entropy_fwd", P(logits_nchw), P(target), B, C, H * W, ignore_index, P(out), P(ws), S())
     return out
 
 
 def cross_entropy_bwd(logits_nchw, target, fwd_out, upstream, ignore_index=255):
     B, C, H, W = logits_nchw.shape
     dl = torch.empty_like(logits_nchw)
-    _call("dh_cross_entropy_bwd", P(logits_nchw), P(target), _ci(B), _ci(C), _cl(H * W), _ci(ignore_index), P(fwd_out),
-          P(upstream), P(dl), S())
+    _call("dh_cross_entropy_bwd", P(logits_nchw), P(target), B, C, H * W, ignore_index, P(fwd_out), P(upstream), P(dl), S())
     return dl
 
 
@@ -1827,7 +1787,7 @@ def dice_argmax_constant(logits_nchw, target, eps=1e-7):
     B, C, H, W = logits_nchw.shape
     loss = torch.empty((), dtype=torch.float32, device=logits_nchw.device)
     ws = workspace(24576, logits_nchw.device)
-    _call("dh_dice_argmax_constant", P(logits_nchw), P(target), _ci(B), _ci(C), _cl(H * W), _cf(eps), P(loss), P(ws), S())
+    _call("dh_dice_argmax_constant", P(logits_nchw), P(target), B, C, H * W, eps, P(loss), P(ws), S())
     return loss
 
 
@@ -1835,20 +1795,20 @@ def confusion_matrix(logits_nchw, target, counts, want_mask=False):
     """counts [C, C] int64 (device) += confusion of argmax(logits) against target; optionally returns the mask"""
     B, C, H, W = logits_nchw.shape
     mask = torch.empty(B, H, W, dtype=torch.int64, device=logits_nchw.device) if want_mask else None
-    _call("dh_confusion_matrix", P(logits_nchw), P(target), _ci(B), _ci(C), _cl(H * W), P(mask), P(counts), S())
+    _call("dh_confusion_matrix", P(logits_nchw), P(target), B, C, H * W, P(mask), P(counts), S())
     return mask
 
 
 def argmax_nchw(logits_nchw):
     B, C, H, W = logits_nchw.shape
     mask = torch.empty(B, H, W, dtype=torch.int64, device=logits_nchw.device)
-    _call("dh_argmax_nchw", P(logits_nchw), P(mask), _ci(B), _ci(C), _cl(H * W), S())
+    _call("dh_argmax_nchw", P(logits_nchw), P(mask), B, C, H * W, S())
     return mask
 
 
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
-    _call("dh_adamw_step", P(param), P(grad), P(exp_avg), P(exp_avg_sq), _cl(param.numel()), _cf(lr), _cf(beta1),
-          _cf(beta2), _cf(eps), _cf(weight_decay), _ci(step), _cf(grad_scale), S())
+    _call("dh_adamw_step", P(param), P(grad), P(exp_avg), P(exp_avg_sq), param.numel(), lr, beta1, beta2, eps, weight_decay, step,
+          grad_scale, S())
 
 
 # ---- xBD train step (csrc/xbd_step.hip) ---------------------------------------------------------------
@@ -1860,49 +1820,49 @@ def combo_loss_fwd(logits, masks, weights_dev, dice_weight=1.0, focal_weight=8.0
     ch = torch.empty(C, dtype=torch.float32, device=dev)
     sums = torch.empty(C, 4, dtype=torch.float32, device=dev)
     ws = workspace(_lib.lib().dh_combo_loss_workspace_size(C), dev)
-    _call("dh_combo_loss_fwd", P(logits), P(masks), _ci(B), _ci(C), _cl(H * W), P(weights_dev), _cf(dice_weight),
-          _cf(focal_weight), P(sums), P(ch), P(loss), P(ws), S())
+    _call("dh_combo_loss_fwd", P(logits), P(masks), B, C, H * W, P(weights_dev), dice_weight, focal_weight, P(sums), P(ch),
+          P(loss), P(ws), S())
     return loss, ch, sums
 
 
 def combo_loss_bwd(logits, masks, sums, weights_dev, upstream, dice_weight=1.0, focal_weight=8.0):
     B, C, H, W = logits.shape
     dl = torch.empty_like(logits)
-    _call("dh_combo_loss_bwd", P(logits), P(masks), P(sums), P(weights_dev), P(upstream), _cf(dice_weight),
-          _cf(focal_weight), _ci(B), _ci(C), _cl(H * W), P(dl), S())
+    _call("dh_combo_loss_bwd", P(logits), P(masks), P(sums), P(weights_dev), P(upstream), dice_weight, focal_weight, B, C, H * W,
+          P(dl), S())
     return dl
 
 
 def grad_norm_clip_coef(grad_flat, max_norm, out):
     """out [2] fp32 (device): total L2 norm of the flat gradient arena, clip_grad_norm_ coefficient"""
     ws = workspace(_lib.lib().dh_grad_norm_workspace_size(), grad_flat.device)
-    _call("dh_grad_norm_clip_coef", P(grad_flat), _cl(grad_flat.numel()), _cf(max_norm), P(out), P(ws), S())
+    _call("dh_grad_norm_clip_coef", P(grad_flat), grad_flat.numel(), max_norm, P(out), P(ws), S())
 
 
 def adamw_xbd_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev=None):
-    _call("dh_adamw_xbd_step", P(param), P(grad), P(exp_avg), P(exp_avg_sq), _cl(param.numel()), _cf(lr), _cf(beta1),
-          _cf(beta2), _cf(eps), _cf(weight_decay), _ci(step), P(grad_scale_dev), S())
+    _call("dh_adamw_xbd_step", P(param), P(grad), P(exp_avg), P(exp_avg_sq), param.numel(), lr, beta1, beta2, eps, weight_decay,
+          step, P(grad_scale_dev), S())
 
 
 # ---- variants writing into caller-provided (contiguous) buffers ------------------------------------
 def stem_space_to_depth_into(x_nchw, out):
     N, C, H, W = x_nchw.shape
     assert C == 3 and out.is_contiguous()
-    _call("dh_stem_space_to_depth", _ci(dt(out)), P(x_nchw), P(out), _ci(N), _ci(H), _ci(W), _ci(out.shape[-1]), S())
+    _call("dh_stem_space_to_depth", dt(out), P(x_nchw), P(out), N, H, W, out.shape[-1], S())
 
 
 def absdiff_upsample4_bwd_into(a, b, dy, da, db):
     N, H, W, C = a.shape
-    _call("dh_absdiff_upsample4_bwd", _ci(dt(a)), P(a), P(b), P(dy), P(da), P(db), _ci(N), _ci(H), _ci(W), _ci(C), S())
+    _call("dh_absdiff_upsample4_bwd", dt(a), P(a), P(b), P(dy), P(da), P(db), N, H, W, C, S())
 
 
 def reduce_rows(partial, nt, n, out, accumulate=False, scale=1.0):
-    _call("dh_reduce_partials", P(partial), _cl(nt), _cl(n), _cf(scale), P(out), _ci(int(accumulate)), S())
+    _call("dh_reduce_partials", P(partial), nt, n, scale, P(out), accumulate, S())
 
 
 def scale_into(src, scalar_dev, dst):
     """dst = src * scalar (a 0-d / 1-element device tensor), no host sync"""
-    _call("dh_scale_by_scalar", P(src), P(scalar_dev.reshape(1).float().contiguous()), P(dst), _cl(src.numel()), S())
+    _call("dh_scale_by_scalar", P(src), P(scalar_dev.reshape(1).float().contiguous()), P(dst), src.numel(), S())
 
 
 def absdiff_halves(tok3, out):
@@ -1912,7 +1872,7 @@ def absdiff_halves(tok3, out):
     assert tok3.is_contiguous() and out.is_contiguous()
     if tok3.dtype == torch.float32 and _ew_record(EW_ABSDIFF_HALVES, tok3, None, out, B, 0, n):
         return
-    _call("dh_absdiff_halves", _ci(dt(tok3)), P(tok3), P(out), _ci(B), _cl(n), S())
+    _call("dh_absdiff_halves", dt(tok3), P(tok3), P(out), B, n, S())
 
 
 def absdiff_halves_bwd(tok3, dout, dtok3):
@@ -1921,4 +1881,4 @@ def absdiff_halves_bwd(tok3, dout, dtok3):
     assert tok3.is_contiguous() and dout.is_contiguous() and dtok3.is_contiguous()
     if tok3.dtype == torch.float32 and _ew_record(EW_ABSDIFF_HALVES_BWD, tok3, dout, dtok3, B, 0, n):
         return
-    _call("dh_absdiff_halves_bwd", _ci(dt(tok3)), P(tok3), P(dout), P(dtok3), _ci(B), _cl(n), S())
+    _call("dh_absdiff_halves_bwd", dt(tok3), P(tok3), P(dout), P(dtok3), B, n, S())

@@ -9,7 +9,6 @@ load_state_dict() interchange with torch.optim.AdamW's per-parameter {step, exp_
 arenas and the step counter are filled from a loaded state and written back on save.
 `capturable=True` keeps lr / step count / bias corrections in device memory so that the step can be
 recorded in a HIP graph (dahitra_amd.graph) and replayed."""
-import ctypes
 
 import torch
 
@@ -187,11 +186,11 @@ class AdamW(torch.optim.Optimizer):
                     # change; sync_hyper raises there if it did.
                     self.sync_hyper(grad_scale)
                     if self._rule == "xbd":
-                        ops._call("dh_adamw_xbd_step_graph", ops.P(param), ops.P(grad), ops.P(st.m), ops.P(st.v),
-                                  ctypes.c_long(param.numel()), ops.P(st.hyper), ops.P(st.step), ops.P(None), ops.S())
+                        ops._call("dh_adamw_xbd_step_graph", ops.P(param), ops.P(grad), ops.P(st.m), ops.P(st.v), param.numel(),
+                                  ops.P(st.hyper), ops.P(st.step), ops.P(None), ops.S())
                     else:
-                        ops._call("dh_adamw_step_graph", ops.P(param), ops.P(grad), ops.P(st.m), ops.P(st.v),
-                                  ctypes.c_long(param.numel()), ops.P(st.hyper), ops.P(st.step), ops.S())
+                        ops._call("dh_adamw_step_graph", ops.P(param), ops.P(grad), ops.P(st.m), ops.P(st.v), param.numel(),
+                                  ops.P(st.hyper), ops.P(st.step), ops.S())
                 else:
                     st.step += 1
                     self._launch(param, grad, st.m, st.v, group, st.step, 1.0 if grad_scale is None else grad_scale)

@@ -160,7 +160,7 @@ int dh_conv2d_wgrad_split(const void* x, long x_split_bytes, const void* dy, flo
 /* classifier.0 on nn.Upsample(4, 'bilinear')(abs(x1 - x2)) WITHOUT that map (models/networks.py:383-389, models/help_funcs.py:9;
  * bf16): a, b [N][H / 4][W / 4][32] are the two streams' decoder outputs, H x W the fine size (multiples of 4).
  *   dh_conv3x3_up4_fwd   y [N][H][W][32] = act(conv3x3(upsample4(|a - b|)) + bias), act 0 / ReLU; w_packed [9][32][32]
- *                        (dh_pack_weight forward form); stats_partial as dh_conv2d_fwd, dh_conv2d_fwd_num_tiles(N, H, W, 32, 3, 1)
+ *                        (dh_pack_weight forward form); stats_partial as dh_conv2d_fwd, dh_conv2d_fwd_num_tiles(DH_BF16, N, H, W, 32, 3, 1)
  *                        rows.  The 8 x 16-pixel tile's haloed input is interpolated from its 4 x 6 coarse footprint with the
  *                        terms and order of dh_absdiff_upsample4_fwd: equal to dh_conv2d_fwd on that kernel's output, bit for bit.
  * (the data gradient through the upsample is dh_conv3x3_dgrad_up4; the weight gradient still reads the materialised map:

@@ -31,6 +31,85 @@ def test_library_exports_every_declared_symbol(built):
     assert lib.dh_abi_version() == 1
 
 
+def test_every_declared_function_is_bound_with_its_prototype(built):
+    """the header drives the binding: argtypes of the declared length on every function, c_long results exactly where the
+    header says `long`, and a declaration the parser does not understand is an error, never a guess"""
+    import ctypes
+    import re
+    from dahitra_amd import _lib
+    lib = _lib.lib()
+    protos = _lib.prototypes()
+    assert sorted(protos) == _lib.declared_symbols()
+    code = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    assert set(protos) == set(re.findall(r"\b(dh_[a-z0-9_]+)\s*\(", code))
+    for name, params in re.findall(r"\b(dh_[a-z0-9_]+)\s*\(([^()]*)\)", code):
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), name
+        assert list(fn.argtypes) == protos[name][1] and fn.restype is protos[name][0], name
+    long_ret = set(re.findall(r"^long\s+(dh_[a-z0-9_]+)\s*\(", code, flags=re.M))
+    assert len(long_ret) == 16
+    assert {n for n in protos if getattr(lib, n).restype is ctypes.c_long} == long_ret
+    assert lib.dh_last_error.restype is ctypes.c_char_p and lib.dh_set_error.restype is None
+    assert lib.dh_bn_finalize.argtypes[5] is ctypes.c_double and lib.dh_bn_finalize.argtypes[10] is ctypes.c_float
+    assert lib.dh_conv2d_fwd.argtypes[20] is ctypes.c_long and lib.dh_ew_multi.argtypes[2] is ctypes.c_void_p
+    assert _lib.parse_prototypes("int dh_ok(int a, const float* b, long n);") == \
+        {"dh_ok": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_long])}
+    for bad in ("int dh_bad(size_t n);", "int dh_bad(int a, long long b);", "int dh_bad(int);", "char dh_bad(int a);",
+                "float* dh_bad(void);", "int dh_bad(int (*fn)(int));", "int dh_bad(int a;"):
+        with pytest.raises(ValueError):
+            _lib.parse_prototypes(bad)
+
+
+def _dh_call_sites():
+    """(file, line, function name, positional argument count) of every dh_* call of the package whose name is a literal and
+    whose arguments are not starred: `_call("dh_x", ...)` and `<library>.dh_x(...)`"""
+    import ast
+    sites = []
+    for dp, _, fns in os.walk(os.path.join(ROOT, "dahitra_amd")):
+        for fn in fns:
+            if not fn.endswith(".py"):
+                continue
+            path = os.path.join(dp, fn)
+            for node in ast.walk(ast.parse(open(path).read(), path)):
+                if not isinstance(node, ast.Call):
+                    continue
+                f, args = node.func, node.args
+                if isinstance(f, ast.Attribute) and f.attr.startswith("dh_"):
+                    name = f.attr
+                elif (isinstance(f, ast.Name) and f.id == "_call") or (isinstance(f, ast.Attribute) and f.attr == "_call"):
+                    if not (args and isinstance(args[0], ast.Constant) and isinstance(args[0].value, str)):
+                        continue
+                    name, args = args[0].value, args[1:]
+                else:
+                    continue
+                if any(isinstance(a, ast.Starred) for a in args) or node.keywords:
+                    continue
+                sites.append((os.path.relpath(path, ROOT), node.lineno, name, len(args)))
+    return sites
+
+
+def test_call_sites_pass_the_declared_number_of_arguments():
+    """static: every checkable dh_* call of the package has as many arguments as its prototype"""
+    from dahitra_amd import _lib
+    protos = _lib.prototypes()
+    sites = _dh_call_sites()
+    assert len(sites) >= 150, len(sites)
+    bad = [s for s in sites if s[2] not in protos or s[3] != len(protos[s[2]][1])]
+    assert not bad, bad
+
+
+def test_a_miscounted_call_is_refused(built):
+    """one argument too few, or a float for an int, never reaches the callee (ctypes lets a cdecl call carry EXTRA arguments,
+    which the callee ignores: that direction is what the static check above is for)"""
+    import ctypes
+    from dahitra_amd import _lib
+    lib = _lib.lib()
+    assert lib.dh_conv2d_fwd_num_tiles(1, 2, 64, 64, 64, 3, 1) > 0           # pure host arithmetic
+    for args in ((1, 2, 64, 64, 64, 3), (1, 2, 64, 64, 64, 3, 1.0)):
+        with pytest.raises((TypeError, ctypes.ArgumentError)):
+            lib.dh_conv2d_fwd_num_tiles(*args)
+
+
 def test_header_has_no_torch_types():
     txt = open(os.path.join(ROOT, "include", "dahitra_hip.h")).read()
     import re
