@@ -212,7 +212,7 @@ extern "C" int dh_conv3x3_dgrad_up4(int dtype, const void* dy, const void* w_pac
 
 // classifier.0 on the bilinear-x4 upsampled |A - B| map WITHOUT that map (ConvArgs::up4_a; models/networks.py:383-389,
 // models/help_funcs.py:9): a, b [N][H / 4][W / 4][32] bf16 (the two streams' decoder outputs), y [N][H][W][32] bf16 =
-// act(conv3x3(upsample4(|a - b|)) + bias); stats_partial as dh_conv2d_fwd with dh_conv2d_fwd_num_tiles(DH_BF16, N, H, W, 32, 3, 1) rows.
+// act(conv3x3(upsample4(|a - b|)) + bias); stats_partial as dh_conv2d_fwd with dh_conv2d_fwd_num_tiles(DH_DTYPE_BF16, N, H, W, 32, 3, 1) rows.
 // The interpolation is dh_absdiff_upsample4_fwd's (same terms, same order, rounded to bf16 as that kernel's output is), so the
 // result equals dh_conv2d_fwd on its output bit for bit.
 extern "C" int dh_conv3x3_up4_fwd(const void* a, const void* b, const void* w_packed, const float* bias, int act, void* y,

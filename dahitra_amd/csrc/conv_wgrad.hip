@@ -893,183 +893,131 @@ __global__ __launch_bounds__(512) void conv_wgrad_ws_multi_kernel(WsMulti m) {
 #ifdef DH_WS_TIMING
 extern "C" int dh_debug_ws(long long* host, int n) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ws), (size_t)n * 8); }
 #endif
-template <int DIL>
-int launch_ws(const WgArgs& a, hipStream_t st) {
-    constexpr int HH = (TH - 1) + 2 * DIL + 1, HWD = (TW - 1) + 2 * DIL + 1;
-    const size_t lds = 2 * ((size_t)HH * HWD * lds_pitch(128) + (size_t)TH * TW * lds_pitch(128)) +
-                       (a.in_scale ? (size_t)a.in_groups * 128 * sizeof(float) : 0);
-    static bool attr_done = false;
-    if (!attr_done) {
-        attr_done = true;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_ws_kernel<DIL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds + 4096) != hipSuccess) {
-            (void)hipGetLastError();
-            DH_FAIL("conv_wgrad_ws: cannot raise dynamic LDS to %zu", lds);
-        }
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+// A launch is planned once (wg_plan: every decision, from the value-initialised WgArgs and the WgLaunch beside it) and then issued
+// by a switch on the plan's family; the public shape queries and dh_conv2d_wgrad_describe read the same plan.  Families --
+// W1: wgrad1x1_kernel; WS: conv_wgrad_ws_kernel<DIL>; WS_BATCH / C32_BATCH: recorded for conv_wgrad_ws_multi_kernel /
+// conv_wgrad_multi_kernel<bf16, 3, 1, 32, true, 1, 32, 1>; GENERIC: conv_wgrad_kernel<T, ks, stride, it / cig, tr, dil, ct, cig>; PHASE: its 2x2 phase form
+enum WgFamily { WG_W1 = 0, WG_WS, WG_WS_BATCH, WG_C32_BATCH, WG_GENERIC, WG_PHASE };
+enum WgPrec { WG_BF16, WG_F32, WG_X3 };
+struct WgLaunch {                // what WgArgs does not say about a launch
+    int prec;                    // WgPrec
+    bool tr;                     // LDS transpose reads
+    int ks, stride, accumulate;
+    bool batch;                  // a batch is open and this launch may be recorded into it
+};
+struct WgPlan {
+    int family;                  // WgFamily
+    int it, ct, cig, ci_tiles;   // ci / co channels per workgroup, ci wave groups (kernel IT = it / cig), ceil(Cin / it)
+    int splitk, direct, threads;
+    dim3 grid;                   // of the launch; a batched layer: its (blocks, K slices) share of the job-table launch
+    size_t lds;                  // dynamic LDS bytes
+};
+
+// dynamic LDS of ws_body<DIL>: two stages of (halo + dY tile) at 64 bf16 channels, then the BatchNorm-on-load table
+constexpr size_t ws_lds(int dil, int in_groups) {
+    return 2 * ((size_t)((TH - 1) + 2 * dil + 1) * ((TW - 1) + 2 * dil + 1) * lds_pitch(128) + (size_t)TH * TW * lds_pitch(128)) +
+           (size_t)in_groups * 128 * sizeof(float);
+}
+// dynamic LDS of wg_body<T, KS, STRIDE, IT, ., DIL, CT, CIG>: `npl` planes of `le`-byte elements (halo + dY tile), the on-load
+// tables; the forms with a narrow co tile park their accumulators there for the end-of-kernel wave-group combine
+constexpr size_t wg_lds(int ks, int stride, int dil, int it, int ct, int cig, int le, int npl, int in_groups, int dyt_groups) {
+    const int hh = (TH - 1) * stride + (ks - 1) * dil + 1, hw = (TW - 1) * stride + (ks - 1) * dil + 1;
+    const size_t lds = npl * ((size_t)hh * hw * lds_pitch(it * cig * le) + (size_t)TH * TW * lds_pitch(ct * le)) +
+                       (size_t)in_groups * 2 * it * cig * sizeof(float) + (size_t)dyt_groups * 3 * ct * sizeof(float);
+    const size_t red = ct < 64 ? (size_t)(ct / 16) * ks * ks * (it / 16) * 64 * 16 : 0;
+    return lds < red ? red : lds;
+}
+// Raises a kernel's dynamic-LDS limit to `bytes` where it is below (`raised`: the call site's static high-water mark, 64 KB to
+// begin with): at the first launch that asks -- the warm-up pass, never inside a graph capture
+template <typename K>
+int raise_dynamic_lds(K kern, size_t bytes, size_t& raised, const char* name) {
+    if (bytes <= raised) return 0;
+    raised = bytes;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        (void)hipGetLastError();      // do not leave a sticky error for the next launch check
+        DH_FAIL("%s: cannot raise dynamic LDS to %zu", name, bytes);
     }
-    dim3 grid((a.Cout / 64) * a.ci_tiles, a.splitk, 1);
-    hipLaunchKernelGGL(conv_wgrad_ws_kernel<DIL>, grid, dim3(512), lds, st, a);
+    return 0;
+}
+
+template <int DIL>
+int launch_ws(const WgArgs& a, const WgPlan& p, hipStream_t st) {
+    static size_t raised = 0;         // for the largest form (ws_eligible: at most 8 BatchNorm groups)
+    if (const int rc = raise_dynamic_lds(conv_wgrad_ws_kernel<DIL>, ws_lds(DIL, 8), raised, "conv_wgrad_ws")) return rc;
+    hipLaunchKernelGGL(conv_wgrad_ws_kernel<DIL>, p.grid, dim3(p.threads), p.lds, st, a);
     DH_CHECK_LAUNCH("conv_wgrad_ws");
     return 0;
 }
-// eligibility of the wave-specialised form (DAHITRA_WGRAD_NO_WS=1: A/B switch back to conv_wgrad_kernel)
-static inline bool ws_eligible(const WgArgs& a, int ks, int stride, bool bf16, bool tr) {
-    static const bool off = getenv("DAHITRA_WGRAD_NO_WS") != nullptr;
-    return !off && bf16 && tr && ks == 3 && stride == 1 && a.groups == 1 && !a.phase_mode && !a.dyt_y && a.Cin % 64 == 0 &&
-           a.Cout % 64 == 0 && a.CoutUse == a.Cout && a.npix == a.OH * a.OW && a.in_npix == a.H * a.W &&
-           (a.x_split ? (a.CinPitch * 2 == a.Cin && a.Cin % 128 == 0 && a.in_scale == nullptr) : a.CinPitch == a.Cin) &&
-           (a.in_scale == nullptr || a.in_groups <= 8);
-}
 
-// ---- batched form (dh_wgrad_batch_begin / _launch / _end): eligible layers are collected, one conv_wgrad_ws_multi_kernel serves them
+// ---- batched form (dh_wgrad_batch_begin / _launch / _end): eligible layers are collected, one job-table launch serves them
 struct WsBatch {
-    bool on = false;
-    int n = 0;
-    size_t lds = 0;
+    int ct, n;         // co tile of its kernel; layers recorded, the largest dynamic LDS among them
+    size_t lds;
+    bool on;
     WsMulti m;
 };
-static thread_local WsBatch g_wsb;       // wave-specialised 64co x 64ci layers (`on` = a batch is open, for both)
-static thread_local WsBatch g_c32b;      // 3x3 stride-1 bf16 layers with a 32-wide co tile (conv_wgrad_kernel<bf16, 3, 1, 32, true, 1, 32, 1>)
-// K slices of a layer inside a batch: ~32 pixel tiles per workgroup (DAHITRA_WGRAD_TPW), 64 for the layers of >= 16 blocks
-// (DAHITRA_WGRAD_TPW_BIG: they come first in a backward pass, the shorter workgroups of the later layers fill the tail; measured
-// 32 / 32: 9017 + 5620 pairs/s (s4 + newUNetTrans), 32 / 64: 9085 + 5621, 32 / 128: 9117 + 5565, 64 / 64: 9018 + 5553, 16 / 16:
-// 8923), never more slices than the layer's own launch would take, a multiple of 8 from 8 on (XCD-aware order)
-static int ws_batch_splitk(const WgArgs& a) {
-    static const int tpw = getenv("DAHITRA_WGRAD_TPW") ? atoi(getenv("DAHITRA_WGRAD_TPW")) : 32;
-    static const int tpw_big = getenv("DAHITRA_WGRAD_TPW_BIG") ? atoi(getenv("DAHITRA_WGRAD_TPW_BIG")) : 2 * tpw;
-    const long tiles = (long)a.N * a.tilesX * a.tilesY;
-    const int t = (a.Cout / 64) * a.ci_tiles >= 16 ? tpw_big : tpw;
-    long sk = tiles / (t > 0 ? t : 32);
-    if (sk > a.splitk) sk = a.splitk;
+static thread_local WsBatch g_wsb{64, 0, 0, false};       // wave-specialised 64co x 64ci layers (`on` = a batch is open, for both)
+static thread_local WsBatch g_c32b{32, 0, 0, false};      // 3x3 stride-1 bf16 layers with a 32-wide co tile
+// K slices of a layer inside a batch: ~`tpw` pixel tiles per workgroup, never more slices than the layer's own launch would
+// take (`cap`), a multiple of 8 from 8 on (XCD-aware order)
+static int batch_splitk(long tiles, int tpw, int cap) {
+    long sk = tiles / (tpw > 0 ? tpw : 32);
+    if (sk > cap) sk = cap;
     if (sk >= 8) sk &= ~7L;
     return (int)(sk < 1 ? 1 : sk);
 }
-// longest workgroups first (the dispatcher hands out workgroups in index order: the short ones then fill the tail of the launch)
-static void batch_sort(WsBatch& b, int co_tile_) {
-    if (getenv("DAHITRA_WGRAD_NO_SORT")) return;
+// tiles per workgroup of the wave-specialised batch: ~32 (DAHITRA_WGRAD_TPW), 64 for the layers of >= 16 blocks
+// (DAHITRA_WGRAD_TPW_BIG: they come first in a backward pass, the shorter workgroups of the later layers fill the tail; measured
+// 32 / 32: 9017 + 5620 pairs/s (s4 + newUNetTrans), 32 / 64: 9085 + 5621, 32 / 128: 9117 + 5565, 64 / 64: 9018 + 5553, 16 / 16:
+// 8923); the 32-wide co tile's: DAHITRA_WGRAD_TPW32
+static int batch_tpw(int ct, int blocks) {
+    static const int tpw = getenv("DAHITRA_WGRAD_TPW") ? atoi(getenv("DAHITRA_WGRAD_TPW")) : 32;
+    static const int tpw_big = getenv("DAHITRA_WGRAD_TPW_BIG") ? atoi(getenv("DAHITRA_WGRAD_TPW_BIG")) : 2 * tpw;
+    static const int tpw32 = getenv("DAHITRA_WGRAD_TPW32") ? atoi(getenv("DAHITRA_WGRAD_TPW32")) : 32;
+    return ct == 32 ? tpw32 : (blocks >= 16 ? tpw_big : tpw);
+}
+// longest workgroups first (the dispatcher hands out workgroups in index order: the short ones fill the tail), then their offsets
+static void batch_sort(WsBatch& b) {
     auto tpw = [](const WgArgs& a) { return ((long)a.N * a.tilesX * a.tilesY + a.splitk - 1) / a.splitk; };
-    for (int i = 1; i < b.n; ++i)                  // insertion sort, stable: at most 16 entries
+    const int n = getenv("DAHITRA_WGRAD_NO_SORT") ? 0 : b.n;
+    for (int i = 1; i < n; ++i)                    // insertion sort, stable: at most 16 entries
         for (int j = i; j > 0 && tpw(b.m.a[j]) > tpw(b.m.a[j - 1]); --j) { const WgArgs t = b.m.a[j]; b.m.a[j] = b.m.a[j - 1]; b.m.a[j - 1] = t; }
     b.m.first[0] = 0;
     for (int i = 0; i < b.n; ++i) {
-        const int nblocks = dh_cdiv(b.m.a[i].CoutUse, co_tile_) * b.m.a[i].ci_tiles * b.m.a[i].splitk;
+        const int nblocks = dh_cdiv(b.m.a[i].CoutUse, b.ct) * b.m.a[i].ci_tiles * b.m.a[i].splitk;
         b.m.first[i + 1] = b.m.first[i] + ((nblocks + 7) & ~7);
     }
 }
-static int ws_batch_flush(hipStream_t st) {
-    WsBatch& b = g_wsb;
+static int batch_flush(WsBatch& b, hipStream_t st) {
     if (b.n == 0) return 0;
     b.m.njobs = b.n;
-    batch_sort(b, 64);
-    const int total = b.m.first[b.n];
-    static bool attr_done = false;      // once, for the largest form (ws_eligible: at most 8 BatchNorm groups): never inside a capture
-    if (!attr_done) {
-        attr_done = true;
-        constexpr int HH = (TH - 1) + 2 + 1, HWD = (TW - 1) + 2 + 1;
-        const size_t max_lds = 2 * ((size_t)HH * HWD * lds_pitch(128) + (size_t)TH * TW * lds_pitch(128)) + 8 * 128 * sizeof(float);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_ws_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)max_lds + 4096) != hipSuccess) {
-            (void)hipGetLastError();
-            DH_FAIL("conv_wgrad_ws_multi: cannot raise dynamic LDS to %zu", max_lds);
-        }
-    }
-    hipLaunchKernelGGL(conv_wgrad_ws_multi_kernel, dim3(total), dim3(512), b.lds, st, b.m);
+    batch_sort(b);
+    const bool ws = b.ct == 64;
+    static size_t raised_ws = 0, raised_c32 = 64 * 1024;
+    const char* name = ws ? "conv_wgrad_ws_multi" : "conv_wgrad_multi";
+    auto kern = ws ? conv_wgrad_ws_multi_kernel : conv_wgrad_multi_kernel<bf16, 3, 1, 32, true, 1, 32, 1>;
+    if (const int rc = raise_dynamic_lds(kern, ws ? ws_lds(1, 8) : b.lds, ws ? raised_ws : raised_c32, name)) return rc;
+    hipLaunchKernelGGL(kern, dim3(b.m.first[b.n]), dim3(ws ? 512 : 256), b.lds, st, b.m);
     b.n = 0; b.lds = 0;
-    DH_CHECK_LAUNCH("conv_wgrad_ws_multi");
+    DH_CHECK_LAUNCH(name);
     return 0;
 }
-// takes the layer into the open batch (a.splitk becomes its in-batch slice count); a full batch is launched first
-static int ws_batch_add(WgArgs& a, hipStream_t st) {
-    WsBatch& b = g_wsb;
-    if (b.n == WS_MAXJ) { const int rc = ws_batch_flush(st); if (rc) return rc; }
-    a.splitk = ws_batch_splitk(a);
-    if (b.n == 0) b.m.first[0] = 0;
-    const int nblocks = (a.Cout / 64) * a.ci_tiles * a.splitk;
-    b.m.a[b.n] = a;
-    b.m.first[b.n + 1] = b.m.first[b.n] + ((nblocks + 7) & ~7);
-    constexpr int HH = (TH - 1) + 2 + 1, HWD = (TW - 1) + 2 + 1;
-    const size_t lds = 2 * ((size_t)HH * HWD * lds_pitch(128) + (size_t)TH * TW * lds_pitch(128)) +
-                       (a.in_scale ? (size_t)a.in_groups * 128 * sizeof(float) : 0);
+// takes the layer into the open batch (a.splitk is its in-batch slice count: the plan's); a full batch is launched first
+static int batch_add(WsBatch& b, const WgArgs& a, size_t lds, hipStream_t st) {
+    if (b.n == WS_MAXJ) { const int rc = batch_flush(b, st); if (rc) return rc; }
+    b.m.a[b.n++] = a;
     if (lds > b.lds) b.lds = lds;
-    ++b.n;
-    return 0;
-}
-
-static inline bool c32_batch_on() { static const bool off = getenv("DAHITRA_WGRAD_BATCH32") && atoi(getenv("DAHITRA_WGRAD_BATCH32")) == 0; return !off; }
-// the second family a batch takes: the 32-channel 3x3 layers (DAHiTra's top-down path: seven launches of ~32 us per step)
-static inline bool c32_eligible(const WgArgs& a, int ks, int stride, bool bf16, bool tr) {
-    return bf16 && tr && ks == 3 && stride == 1 && a.dil == 1 && a.groups == 1 && !a.phase_mode && !a.dyt_y && !a.direct &&
-           co_tile(a.CoutUse) == 32 && a.npix == a.OH * a.OW && a.in_npix == a.H * a.W;
-}
-static size_t c32_lds(const WgArgs& a) {
-    constexpr int HH = (TH - 1) + 2 + 1, HWD = (TW - 1) + 2 + 1;
-    size_t lds = (size_t)HH * HWD * lds_pitch(32 * 2) + (size_t)TH * TW * lds_pitch(32 * 2) +
-                 (a.in_scale ? (size_t)a.in_groups * 2 * 32 * sizeof(float) : 0);
-    const size_t red = (size_t)(32 / 16) * 9 * (32 / 16) * 64 * 16;      // the end-of-kernel wave-group combine (launch_ct)
-    return lds < red ? red : lds;
-}
-static int c32_batch_flush(hipStream_t st) {
-    WsBatch& b = g_c32b;
-    if (b.n == 0) return 0;
-    b.m.njobs = b.n;
-    batch_sort(b, 32);
-    const int total = b.m.first[b.n];
-    auto kern = conv_wgrad_multi_kernel<bf16, 3, 1, 32, true, 1, 32, 1>;
-    static size_t attr_lds = 64 * 1024;
-    if (b.lds > attr_lds) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.lds) != hipSuccess) {
-            (void)hipGetLastError();
-            DH_FAIL("conv_wgrad_multi: cannot raise dynamic LDS to %zu", b.lds);
-        }
-        attr_lds = b.lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(total), dim3(256), b.lds, st, b.m);
-    b.n = 0; b.lds = 0;
-    DH_CHECK_LAUNCH("conv_wgrad_multi");
-    return 0;
-}
-static int c32_batch_add(WgArgs& a, hipStream_t st) {
-    WsBatch& b = g_c32b;
-    if (b.n == WS_MAXJ) { const int rc = c32_batch_flush(st); if (rc) return rc; }
-    static const int tpw = getenv("DAHITRA_WGRAD_TPW32") ? atoi(getenv("DAHITRA_WGRAD_TPW32")) : 32;
-    long sk = ((long)a.N * a.tilesX * a.tilesY) / (tpw > 0 ? tpw : 32);
-    if (sk > a.splitk) sk = a.splitk;
-    if (sk >= 8) sk &= ~7L;
-    a.splitk = (int)(sk < 1 ? 1 : sk);
-    if (b.n == 0) b.m.first[0] = 0;
-    const int nblocks = dh_cdiv(a.CoutUse, 32) * a.ci_tiles * a.splitk;
-    b.m.a[b.n] = a;
-    b.m.first[b.n + 1] = b.m.first[b.n] + ((nblocks + 7) & ~7);
-    const size_t lds = c32_lds(a);
-    if (lds > b.lds) b.lds = lds;
-    ++b.n;
     return 0;
 }
 
 template <typename T, int KS, int STRIDE, int IT, int DIL, int CT, int CIG = 1>
-int launch_ct(const WgArgs& a, bool tr, hipStream_t st) {
-    constexpr int HH = (TH - 1) * STRIDE + (KS - 1) * DIL + 1, HWD = (TW - 1) * STRIDE + (KS - 1) * DIL + 1;
-    constexpr int LE = Prec<T>::X3 ? 2 : (int)sizeof(T), NPL = Prec<T>::X3 ? 2 : 1;      // LDS element bytes, planes (wg_body)
-    size_t lds = NPL * ((size_t)HH * HWD * lds_pitch(IT * CIG * LE) + (size_t)TH * TW * lds_pitch(CT * LE)) +
-                 (a.in_scale ? (size_t)a.in_groups * 2 * IT * CIG * sizeof(float) : 0) +
-                 (a.dyt_y ? (size_t)a.dyt_groups * 3 * CT * sizeof(float) : 0);
-    if (CT < 64) {                                     // the end-of-kernel wave-group combine parks accumulators here
-        const size_t red = (size_t)(CT / 16) * KS * KS * (IT / 16) * 64 * 16;
-        if (lds < red) lds = red;
-    }
-    dim3 grid(dh_cdiv(a.CoutUse, CT) * a.ci_tiles, a.splitk, a.phase_mode ? 4 : a.groups);
+int launch_ct(const WgArgs& a, const WgPlan& p, bool tr, hipStream_t st) {
     auto go = [&](auto kern) -> int {
-        static bool attr_done = false;      // once per instantiation (and never inside a graph capture)
-        if (lds > 64 * 1024 && !attr_done) {
-            attr_done = true;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();      // do not leave a sticky error for the next launch check
-                DH_FAIL("conv_wgrad: cannot raise dynamic LDS to %zu", lds);
-            }
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(256 * CIG), lds, st, a);
+        static size_t raised = 64 * 1024;      // per instantiation
+        if (const int rc = raise_dynamic_lds(kern, p.lds, raised, "conv_wgrad")) return rc;
+        hipLaunchKernelGGL(kern, p.grid, dim3(p.threads), p.lds, st, a);
         DH_CHECK_LAUNCH("conv_wgrad");
         return 0;
     };
@@ -1086,19 +1034,15 @@ int launch_ct(const WgArgs& a, bool tr, hipStream_t st) {
         return go(conv_wgrad_kernel<T, KS, STRIDE, IT, false, DIL, CT, CIG>);
     }
 }
-// 3x3 layers with >= 64 input channels and a 64-wide co tile run the 512-thread, 64co x 64ci variant (CIG = 2)
-static inline bool wide_ci3x3(int Cin, int CoutUse, int ks) {
-    static const bool off = getenv("DAHITRA_WGRAD_CIG1") != nullptr;       // A/B switch for tools/kbench.py
-    return !off && ks == 3 && Cin >= 64 && co_tile(CoutUse) == 64;
-}
+// the co tile and, for the 3x3 stride-1 forms, the 512-thread 64co x 64ci variant (CIG = 2), as planned
 template <typename T, int KS, int STRIDE, int IT, int DIL = 1>
-int launch(const WgArgs& a, bool tr, hipStream_t st) {
-    if (co_tile(a.CoutUse) == 16) return launch_ct<T, KS, STRIDE, IT, DIL, 16>(a, tr, st);
-    if (co_tile(a.CoutUse) == 32) return launch_ct<T, KS, STRIDE, IT, DIL, 32>(a, tr, st);
+int launch(const WgArgs& a, const WgPlan& p, bool tr, hipStream_t st) {
+    if (p.ct == 16) return launch_ct<T, KS, STRIDE, IT, DIL, 16>(a, p, tr, st);
+    if (p.ct == 32) return launch_ct<T, KS, STRIDE, IT, DIL, 32>(a, p, tr, st);
     if constexpr (KS == 3 && IT == 32 && STRIDE == 1) {      // (stride 2: the 64-channel halo does not fit / is slower)
-        if (wide_ci3x3(a.Cin, a.CoutUse, KS)) return launch_ct<T, KS, STRIDE, IT, DIL, 64, 2>(a, tr, st);
+        if (p.cig == 2) return launch_ct<T, KS, STRIDE, IT, DIL, 64, 2>(a, p, tr, st);
     }
-    return launch_ct<T, KS, STRIDE, IT, DIL, 64>(a, tr, st);
+    return launch_ct<T, KS, STRIDE, IT, DIL, 64>(a, p, tr, st);
 }
 
 // ---- 1x1 / stride 1, bf16, large layers: a workgroup owns a CT x IT block of dW (256 x 128 and its relatives) -----------------
@@ -1223,7 +1167,48 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(W1Args p) {
         }
 }
 
-// block shape by operand traffic: dY is read once per ci tile, X once per co tile
+static int launch_w1(const WgArgs& a, const WgPlan& p, hipStream_t st) {
+    W1Args w;
+    w.x = reinterpret_cast<const bf16*>(a.x); w.dy = reinterpret_cast<const bf16*>(a.dy); w.part = a.part;
+    w.P = (long)a.N * a.OH * a.OW; w.stride = (a.H == a.OH && a.W == a.OW) ? 1 : 2; w.OW = a.OW; w.OHW = a.OH * a.OW; w.W = a.W; w.HW = a.H * a.W;
+    w.Cin = a.Cin; w.CinPitch = a.CinPitch; w.Cout = a.Cout; w.CoutUse = a.CoutUse;
+    w.splitk = a.splitk; w.ci_tiles = p.ci_tiles; w.no_xcd_remap = a.no_xcd_remap;
+    if (p.ct == 256 && p.it == 128) hipLaunchKernelGGL((wgrad1x1_kernel<256, 128>), p.grid, dim3(p.threads), 0, st, w);
+    else if (p.ct == 128) hipLaunchKernelGGL((wgrad1x1_kernel<128, 256>), p.grid, dim3(p.threads), 0, st, w);
+    else if (p.it == 64) hipLaunchKernelGGL((wgrad1x1_kernel<256, 64>), p.grid, dim3(p.threads), 0, st, w);
+    else hipLaunchKernelGGL((wgrad1x1_kernel<64, 256>), p.grid, dim3(p.threads), 0, st, w);
+    DH_CHECK_LAUNCH("conv_wgrad 1x1");
+    return 0;
+}
+
+// ---- the plan: every predicate below is asked by wg_splitk_estimate / wg_plan and by nobody else ----------------------------
+// 3x3 layers with >= 64 input channels and a 64-wide co tile run the 512-thread, 64co x 64ci variant (CIG = 2)
+static inline bool wide_ci3x3(int Cin, int CoutUse, int ks) {
+    static const bool off = getenv("DAHITRA_WGRAD_CIG1") != nullptr;       // A/B switch for tools/kbench.py
+    return !off && ks == 3 && Cin >= 64 && co_tile(CoutUse) == 64;
+}
+// 1x1 layers with >= 128 input channels and a 64-wide co tile: the 512-thread form, 64co x 128ci per workgroup (CIG = 2 on the
+// 64-wide ci tile) -- the dY slice of a co tile is staged once for 128 input channels instead of twice.  The Bottleneck layers of
+// the ResNet-50 trunk (1024 x 256 at 128 x 128 x 8 pixels: 16 x 4 tile pairs re-read a 335 MB operand pair)
+static inline bool wide_ci1x1(int Cin, int CoutUse, int ks) {
+    static const bool on = getenv("DAHITRA_WGRAD_1X1_CIG2") ? atoi(getenv("DAHITRA_WGRAD_1X1_CIG2")) != 0 : true;
+    return on && ks == 1 && Cin >= 128 && Cin % 128 == 0 && co_tile(CoutUse) == 64;
+}
+// eligibility of the wave-specialised form (DAHITRA_WGRAD_NO_WS=1: A/B switch back to conv_wgrad_kernel)
+static inline bool ws_eligible(const WgArgs& a, const WgLaunch& l) {
+    static const bool off = getenv("DAHITRA_WGRAD_NO_WS") != nullptr;
+    return !off && l.prec == WG_BF16 && l.tr && l.ks == 3 && l.stride == 1 && a.groups == 1 && !a.phase_mode && !a.dyt_y &&
+           a.Cin % 64 == 0 && a.Cout % 64 == 0 && a.CoutUse == a.Cout && a.npix == a.OH * a.OW && a.in_npix == a.H * a.W &&
+           (a.x_split ? (a.CinPitch * 2 == a.Cin && a.Cin % 128 == 0 && a.in_scale == nullptr) : a.CinPitch == a.Cin) &&
+           (a.in_scale == nullptr || a.in_groups <= 8);
+}
+static inline bool c32_batch_on() { static const bool off = getenv("DAHITRA_WGRAD_BATCH32") && atoi(getenv("DAHITRA_WGRAD_BATCH32")) == 0; return !off; }
+// the second family a batch takes: the 32-channel 3x3 layers (DAHiTra's top-down path: seven launches of ~32 us per step)
+static inline bool c32_eligible(const WgArgs& a, const WgLaunch& l) {
+    return l.prec == WG_BF16 && l.tr && l.ks == 3 && l.stride == 1 && a.dil == 1 && a.groups == 1 && !a.phase_mode && !a.dyt_y &&
+           !a.direct && co_tile(a.CoutUse) == 32 && a.npix == a.OH * a.OW && a.in_npix == a.H * a.W;
+}
+// wgrad1x1_kernel's block shape by operand traffic: dY is read once per ci tile, X once per co tile
 static inline void w1_pick(long Cout, long Cin, int& ct, int& it) {
     const int cand[4][2] = {{256, 128}, {128, 256}, {256, 64}, {64, 256}};
     double best = 1e30;
@@ -1237,92 +1222,37 @@ static inline bool w1_shape(int Cin, int Cout, int ks) {
     static const bool on = getenv("DAHITRA_WGRAD_1X1_BIG") ? atoi(getenv("DAHITRA_WGRAD_1X1_BIG")) != 0 : true;
     return on && ks == 1 && Cin % 8 == 0 && Cout % 8 == 0 && (long)Cin * Cout >= 128 * 128 && (Cin >= 256 || Cout >= 256);
 }
-static inline bool w1_eligible(const WgArgs& a, int ks, int stride, bool bf16_, bool tr) {
-    const bool geo = stride == 1 ? (a.H == a.OH && a.W == a.OW) : (stride == 2 && a.OH == (a.H + 1) / 2 && a.OW == (a.W + 1) / 2);
-    return bf16_ && tr && geo && w1_shape(a.Cin, a.Cout, ks) && a.groups == 1 && !a.in_scale && !a.x_split && !a.direct &&
+static inline bool w1_eligible(const WgArgs& a, const WgLaunch& l) {
+    const bool geo = l.stride == 1 ? (a.H == a.OH && a.W == a.OW) : (l.stride == 2 && a.OH == (a.H + 1) / 2 && a.OW == (a.W + 1) / 2);
+    return l.prec == WG_BF16 && l.tr && geo && w1_shape(a.Cin, a.Cout, l.ks) && a.groups == 1 && !a.in_scale && !a.x_split && !a.direct &&
            !a.dyt_y && !a.phase_mode && a.CoutUse == a.Cout && a.CinPitch % 8 == 0 && a.pad == 0 &&
            a.npix == a.OH * a.OW && a.in_npix == a.H * a.W && (long)a.N * a.OH * a.OW < (1L << 31);
 }
-// ... and only where its few fat blocks still fill the chip (blocks x pixel splits >= 256 workgroups; the split count is capped by
-// 8 pixel tiles per workgroup, so a 256 x 128 layer at 64 x 32 x 32 pixels would be 64 workgroups: that one stays with wg_body)
-static inline bool w1_fills(const WgArgs& a) {
-    int ct = 256, it = 128;
-    w1_pick(a.Cout, a.Cin, ct, it);
-    return (long)dh_cdiv(a.Cout, ct) * dh_cdiv(a.Cin, it) * a.splitk >= 256;
+// wg_body's tiles: the co tile, the ci channels per workgroup (64-wide ci tiles only where accumulators / LDS fit) and its ci
+// wave groups
+static inline void wg_tiles(int ks, int stride, int Cin, int CoutUse, int& ct, int& it, int& cig) {
+    const bool wide = Cin > 32 && ks == 1 && stride == 1;
+    const bool wide2 = wide && wide_ci1x1(Cin, CoutUse, ks);
+    const bool big = stride == 1 && wide_ci3x3(Cin, CoutUse, ks);
+    ct = co_tile(CoutUse);
+    it = ks == 4 ? 16 : (wide2 ? 128 : ((wide || big) ? 64 : 32));
+    cig = (wide2 || big) ? 2 : 1;
 }
-static int launch_w1(const WgArgs& a, hipStream_t st) {
-    int ct = 256, it = 128;
-    w1_pick(a.Cout, a.Cin, ct, it);
-    W1Args w;
-    w.x = reinterpret_cast<const bf16*>(a.x); w.dy = reinterpret_cast<const bf16*>(a.dy); w.part = a.part;
-    w.P = (long)a.N * a.OH * a.OW; w.stride = (a.H == a.OH && a.W == a.OW) ? 1 : 2; w.OW = a.OW; w.OHW = a.OH * a.OW; w.W = a.W; w.HW = a.H * a.W;
-    w.Cin = a.Cin; w.CinPitch = a.CinPitch; w.Cout = a.Cout; w.CoutUse = a.CoutUse;
-    w.splitk = a.splitk; w.ci_tiles = dh_cdiv(a.Cin, it); w.no_xcd_remap = a.no_xcd_remap;
-    dim3 grid(dh_cdiv(a.Cout, ct) * w.ci_tiles, a.splitk);
-    if (ct == 256 && it == 128) hipLaunchKernelGGL((wgrad1x1_kernel<256, 128>), grid, dim3(256), 0, st, w);
-    else if (ct == 128) hipLaunchKernelGGL((wgrad1x1_kernel<128, 256>), grid, dim3(256), 0, st, w);
-    else if (it == 64) hipLaunchKernelGGL((wgrad1x1_kernel<256, 64>), grid, dim3(256), 0, st, w);
-    else hipLaunchKernelGGL((wgrad1x1_kernel<64, 256>), grid, dim3(256), 0, st, w);
-    DH_CHECK_LAUNCH("conv_wgrad 1x1");
-    return 0;
-}
-
-// 1x1 layers with >= 128 input channels and a 64-wide co tile: the 512-thread form, 64co x 128ci per workgroup (CIG = 2 on the
-// 64-wide ci tile) -- the dY slice of a co tile is staged once for 128 input channels instead of twice.  The Bottleneck layers of
-// the ResNet-50 trunk (1024 x 256 at 128 x 128 x 8 pixels: 16 x 4 tile pairs re-read a 335 MB operand pair)
-static inline bool wide_ci1x1(int Cin, int CoutUse, int ks) {
-    static const bool on = getenv("DAHITRA_WGRAD_1X1_CIG2") ? atoi(getenv("DAHITRA_WGRAD_1X1_CIG2")) != 0 : true;
-    return on && ks == 1 && Cin >= 128 && Cin % 128 == 0 && co_tile(CoutUse) == 64;
-}
-template <typename T>
-int launch_all(WgArgs& a, int ks, int stride, bool tr, hipStream_t st) {
-    const bool wide = a.Cin > 32 && ks == 1 && stride == 1;   // 64-wide ci tiles only where accumulators / LDS fit
-    const bool wide2 = wide && wide_ci1x1(a.Cin, a.CoutUse, ks);
-    const int it = ks == 4 ? 16 : (wide2 ? 128 : ((wide || (stride == 1 && wide_ci3x3(a.Cin, a.CoutUse, ks))) ? 64 : 32));
-    a.ci_tiles = dh_cdiv(a.Cin, it);
-    if (w1_eligible(a, ks, stride, std::is_same<T, bf16>::value, tr) && w1_fills(a)) return launch_w1(a, st);
-    if (ws_eligible(a, ks, stride, sizeof(T) == 2, tr) && wide_ci3x3(a.Cin, a.CoutUse, ks)) {
-        if (g_wsb.on && a.dil == 1 && !a.direct) return ws_batch_add(a, st);
-        return a.dil == 2 ? launch_ws<2>(a, st) : launch_ws<1>(a, st);
-    }
-    if (ks == 3 && stride == 1 && a.dil == 2) return launch<T, 3, 1, 32, 2>(a, tr, st);
-    if (g_wsb.on && c32_batch_on() && c32_eligible(a, ks, stride, sizeof(T) == 2, tr)) return c32_batch_add(a, st);
-    if (ks == 3 && stride == 1) return launch<T, 3, 1, 32>(a, tr, st);
-    if (ks == 3 && stride == 2) return launch<T, 3, 2, 32>(a, tr, st);
-    if (ks == 1 && stride == 1 && wide2) return launch_ct<T, 1, 1, 64, 1, 64, 2>(a, tr, st);
-    if (ks == 1 && stride == 1) return wide ? launch<T, 1, 1, 64>(a, tr, st) : launch<T, 1, 1, 32>(a, tr, st);
-    if (ks == 1 && stride == 2) return launch<T, 1, 2, 32>(a, tr, st);
-    if (ks == 4 && stride == 1) return launch<T, 4, 1, 16>(a, tr, st);     // space-to-depth stem (12 real channels)
-    if (ks == 2 && stride == 1 && a.phase_mode) return launch<T, 2, 1, 32>(a, tr, st);
-    DH_FAIL("conv_wgrad: unsupported kernel %d stride %d", ks, stride);
-}
-
-}  // namespace
-
-// dh_set_f32_mma_mode(1 / 2) (conv_mfma.hip): fp32 launches whose channel counts are multiples of 4 (16-byte aligned half
-// pieces: the class head's one-piece-per-pixel dlogits have 4) take the split-bf16 three-product form (wg_body<f32x3>); the
-// others keep the exact fp32 MFMA
-extern "C" int dh_get_f32_mma_mode(void);
-static inline bool wgrad_x3(int dtype, const WgArgs& a) {
-    static const bool skip = getenv("DAHITRA_X3_NO_WGRAD") != nullptr;      // experiment switch
-    return !skip && dtype == DH_DTYPE_F32 && dh_get_f32_mma_mode() != 0 && a.Cin % 4 == 0 && a.Cout % 4 == 0 && a.CinPitch % 4 == 0;
-}
-
-// split-K factor: one resident round of workgroups, never more slabs than pixel tiles
-extern "C" int dh_conv2d_wgrad_splitk(int N, int OH, int OW, int Cin, int Cout, int ks, int groups) {
-    const long tiles = (long)(N / (groups > 0 ? groups : 1)) * dh_cdiv(OW, TW) * dh_cdiv(OH, TH);
-    // NOTE: stride is not known here; the 64-wide ci tile is only used at stride 1, where this
-    // estimate is exact; at stride 2 it under-estimates the slab count (harmless: more workgroups)
-    const bool big = wide_ci3x3(Cin, Cout, ks);       // 512-thread workgroups, one per CU
-    const int it = ks == 4 ? 16 : (wide_ci1x1(Cin, Cout, ks) ? 128 : (((Cin > 32 && ks == 1) || big) ? 64 : 32));
-    long slabs = (long)dh_cdiv(Cout, co_tile(Cout)) * dh_cdiv(Cin, it) * (groups > 0 ? groups : 1);
-    bool w1 = false;
-    if (groups <= 1 && w1_shape(Cin, Cout, ks)) {      // (dtype / stride unknown here: a launch that takes another kernel just gets fewer, fatter slabs)
-        int ct = 256, it1 = 128;
-        w1_pick(Cout, Cin, ct, it1);
-        slabs = (long)dh_cdiv(Cout, ct) * dh_cdiv(Cin, it1);
-        w1 = true;
-    }
+// The split-K factor: one resident round of workgroups, never more slabs than pixel tiles.
+// THE ESTIMATE: it knows the shape alone, so it counts the slabs of the launch this shape would get as a bf16, transpose-read,
+// stride-1, plain-input layer with a dense dy (CoutUse = Cout) -- wgrad1x1_kernel's blocks wherever w1_shape holds.  The
+// workspace contract (dh_conv2d_wgrad_workspace_size) is sized by this number, so wg_plan takes its split-K from here and from
+// nowhere else: a launch that ends in another family (stride 2, fp32, BatchNorm on load, a 1x1 layer too small to fill the
+// chip with fat blocks) keeps the factor and just gets fewer, fatter slabs.
+static int wg_splitk_estimate(int N, int OH, int OW, int Cin, int Cout, int ks, int groups) {
+    const int g = groups > 0 ? groups : 1;
+    const long tiles = (long)(N / g) * dh_cdiv(OW, TW) * dh_cdiv(OH, TH);
+    int ct, it, cig;
+    wg_tiles(ks, 1, Cin, Cout, ct, it, cig);
+    const bool big = ks == 3 && cig == 2;          // 512-thread workgroups, one per CU
+    const bool w1 = groups <= 1 && w1_shape(Cin, Cout, ks);
+    if (w1) w1_pick(Cout, Cin, ct, it);
+    const long slabs = (long)dh_cdiv(Cout, ct) * dh_cdiv(Cin, it) * g;
     // workgroups in flight: the 3x3 / 4x4 kernels hold two workgroups per CU (168+ registers per lane), so 512 fill the
     // chip in ONE round -- a second round only doubles the partial-slab traffic and the per-workgroup prologue / slab
     // write (measured: layer3 115.6 -> 107.6 us, classifier 75.7 -> 65.1 us); the light 1x1 kernels fit four per CU
@@ -1334,73 +1264,153 @@ extern "C" int dh_conv2d_wgrad_splitk(int N, int OH, int OW, int Cin, int Cout, 
     if (sk > 1024) sk = 1024;
     return (int)(sk < 1 ? 1 : sk);
 }
-
-// whether a plain bf16 1x1 / stride-1 weight gradient of this shape (one group, no BatchNorm on load) runs as wgrad1x1_kernel
-// blocks -- for tests and tools: the rule of launch_all, w1_eligible and w1_fills
-extern "C" int dh_conv2d_wgrad_1x1_blocks(int N, int H, int W, int Cin, int Cout) {
-    if (!w1_shape(Cin, Cout, 1)) return 0;
-    int ct = 256, it = 128;
-    w1_pick(Cout, Cin, ct, it);
-    const long blocks = (long)dh_cdiv(Cout, ct) * dh_cdiv(Cin, it);
-    return blocks * dh_conv2d_wgrad_splitk(N, H, W, Cin, Cout, 1, 1) >= 256 ? (int)blocks : 0;
+// the 2x2 phase form: one 32-wide co tile x ci tiles per phase
+static int phase_splitk(int N, int H, int W, int Cin) {
+    const long tiles = (long)N * dh_cdiv(W, TW) * dh_cdiv(H, TH);
+    const long slabs = (long)dh_cdiv(Cin, 32);
+    long sk = (128 + slabs - 1) / slabs;                       // 4 phases x slabs x sk ~ 512 workgroups
+    if (sk > tiles / 8) sk = tiles / 8;
+    return (int)(sk < 1 ? 1 : sk);
 }
 
+// Plans the launch of `a` (its shape and on-load forms) as `l`: fills `p` and a.splitk / a.direct / a.ci_tiles.  Touches no device
+// and no error string: conv2d_wgrad_impl words the two refusals
+enum { WG_OK, WG_NO_SPLIT, WG_NO_KERNEL };
+static int wg_plan(WgArgs& a, const WgLaunch& l, WgPlan& p) {
+    p = WgPlan{};
+    const long tiles = (long)a.N * a.tilesX * a.tilesY;
+    const int in_groups = a.in_scale ? a.in_groups : 0;
+    p.splitk = a.phase_mode ? phase_splitk(a.N, a.H, a.W, a.Cin) : wg_splitk_estimate(a.N, a.OH, a.OW, a.Cin, a.Cout, l.ks, a.groups);
+    // 1x1 with a single K slab: [tap = 1][Cout][Cin] is exactly dW's [Cout][Cin] (also per image: [N][Cout][Cin])
+    a.direct = p.direct = (l.ks == 1 && p.splitk == 1 && a.CoutUse == a.Cout) ? (l.accumulate ? 2 : 1) : 0;
+    auto planned = [&](int family, int gx, int gz, int threads, size_t lds) {
+        p.family = family; p.grid = dim3(gx, p.splitk, gz); p.threads = threads; p.lds = lds;
+        a.splitk = p.splitk; a.ci_tiles = p.ci_tiles;
+        return WG_OK;
+    };
+    const bool ws = ws_eligible(a, l) && wide_ci3x3(a.Cin, a.CoutUse, l.ks);
+    if (a.x_split && !ws) return WG_NO_SPLIT;
+    p.cig = 1;
+    if (w1_eligible(a, l)) {
+        w1_pick(a.Cout, a.Cin, p.ct, p.it); p.ci_tiles = dh_cdiv(a.Cin, p.it);
+        // ... and only where its few fat blocks still fill the chip (>= 256 workgroups; the split count is capped by 8 pixel tiles per
+        // workgroup, so a 256 x 128 layer at 64 x 32 x 32 pixels would be 64 workgroups: that one stays with wg_body)
+        const long blocks = (long)dh_cdiv(a.Cout, p.ct) * p.ci_tiles;
+        if (blocks * p.splitk >= 256) return planned(WG_W1, (int)blocks, 1, 256, 0);
+    }
+    if (ws) {
+        p.ct = p.it = 64; p.ci_tiles = a.Cin / 64;
+        const int blocks = (a.Cout / 64) * p.ci_tiles;
+        const bool batch = l.batch && a.dil == 1 && !a.direct;
+        if (batch) p.splitk = batch_splitk(tiles, batch_tpw(64, blocks), p.splitk);
+        return planned(batch ? WG_WS_BATCH : WG_WS, blocks, 1, 512, ws_lds(a.dil, in_groups));
+    }
+    wg_tiles(l.ks, l.stride, a.Cin, a.CoutUse, p.ct, p.it, p.cig); p.ci_tiles = dh_cdiv(a.Cin, p.it);
+    const bool s12 = l.stride == 1 || l.stride == 2;
+    if (!(a.phase_mode ? (l.ks == 2 && l.stride == 1) : ((l.ks == 3 || l.ks == 1) ? s12 : (l.ks == 4 && l.stride == 1)))) return WG_NO_KERNEL;
+    const bool batch = l.batch && c32_batch_on() && c32_eligible(a, l);
+    if (batch) p.splitk = batch_splitk(tiles, batch_tpw(32, 0), p.splitk);
+    return planned(batch ? WG_C32_BATCH : (a.phase_mode ? WG_PHASE : WG_GENERIC), dh_cdiv(a.CoutUse, p.ct) * p.ci_tiles, a.phase_mode ? 4 : a.groups, 256 * p.cig,
+                   wg_lds(l.ks, l.stride, a.dil, p.it / p.cig, p.ct, p.cig, l.prec == WG_F32 ? 4 : 2, l.prec == WG_X3 ? 2 : 1, in_groups,
+                          a.dyt_y ? a.dyt_groups : 0));
+}
+
+// the launch of a plan; conv_wgrad_kernel's template ladder is keyed by the plan's numbers
+template <typename T>
+int launch_generic(const WgArgs& a, const WgLaunch& l, const WgPlan& p, hipStream_t st) {
+    const int ks = l.ks, stride = l.stride;
+    if (ks == 3 && stride == 1 && a.dil == 2) return launch<T, 3, 1, 32, 2>(a, p, l.tr, st);
+    if (ks == 3 && stride == 1) return launch<T, 3, 1, 32>(a, p, l.tr, st);
+    if (ks == 3 && stride == 2) return launch<T, 3, 2, 32>(a, p, l.tr, st);
+    if (ks == 1 && stride == 1 && p.cig == 2) return launch_ct<T, 1, 1, 64, 1, 64, 2>(a, p, l.tr, st);
+    if (ks == 1 && stride == 1) return p.it == 64 ? launch<T, 1, 1, 64>(a, p, l.tr, st) : launch<T, 1, 1, 32>(a, p, l.tr, st);
+    if (ks == 1 && stride == 2) return launch<T, 1, 2, 32>(a, p, l.tr, st);
+    return ks == 4 ? launch<T, 4, 1, 16>(a, p, l.tr, st) : launch<T, 2, 1, 32>(a, p, l.tr, st);     // the space-to-depth stem; the phase form
+}
+static int wg_launch(const WgArgs& a, const WgLaunch& l, const WgPlan& p, hipStream_t st) {
+    switch (p.family) {
+    case WG_W1: return launch_w1(a, p, st);
+    case WG_WS: return a.dil == 2 ? launch_ws<2>(a, p, st) : launch_ws<1>(a, p, st);
+    case WG_WS_BATCH: return batch_add(g_wsb, a, p.lds, st);
+    case WG_C32_BATCH: return batch_add(g_c32b, a, p.lds, st);
+    default: return l.prec == WG_BF16 ? launch_generic<bf16>(a, l, p, st)
+                    : l.prec == WG_X3 ? launch_generic<f32x3>(a, l, p, st) : launch_generic<float>(a, l, p, st);
+    }
+}
+}  // namespace
+
+// dh_set_f32_mma_mode(1 / 2) (conv_mfma.hip): fp32 launches whose channel counts are multiples of 4 (16-byte aligned half
+// pieces: the class head's one-piece-per-pixel dlogits have 4) take the split-bf16 three-product form (wg_body<f32x3>); the
+// others keep the exact fp32 MFMA
+extern "C" int dh_get_f32_mma_mode(void);
+static inline bool wgrad_x3(int dtype, const WgArgs& a) {
+    static const bool skip = getenv("DAHITRA_X3_NO_WGRAD") != nullptr;      // experiment switch
+    return !skip && dtype == DH_DTYPE_F32 && dh_get_f32_mma_mode() != 0 && a.Cin % 4 == 0 && a.Cout % 4 == 0 && a.CinPitch % 4 == 0;
+}
+// The one WgArgs initialiser: a dense, plain, one-group, undilated layer N x H x W x Cin -> OH x OW x Cout; callers name what differs
+static WgArgs wg_args(int N, int H, int W, int Cin, int OH, int OW, int Cout, int pad) {
+    static const int no_remap = getenv("DAHITRA_NO_XCD_REMAP") ? 1 : 0;
+    WgArgs a{};
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout; a.pad = pad;
+    a.tilesX = dh_cdiv(OW, TW); a.tilesY = dh_cdiv(OH, TH); a.npix = OH * OW; a.in_npix = H * W;
+    a.CinPitch = Cin; a.CoutUse = Cout; a.groups = a.dil = a.in_groups = a.dyt_groups = 1;
+    a.no_xcd_remap = no_remap;
+    return a;
+}
+extern "C" int dh_conv2d_wgrad_splitk(int N, int OH, int OW, int Cin, int Cout, int ks, int groups) {
+    return wg_splitk_estimate(N, OH, OW, Cin, Cout, ks, groups);
+}
 extern "C" long dh_conv2d_wgrad_workspace_size(int N, int OH, int OW, int Cin, int Cout, int ks, int groups) {
-    return (long)groups * dh_conv2d_wgrad_splitk(N, OH, OW, Cin, Cout, ks, groups) * ks * ks * Cout * Cin * 4;
+    return (long)groups * wg_splitk_estimate(N, OH, OW, Cin, Cout, ks, groups) * ks * ks * Cout * Cin * 4;
 }
-
+// the wgrad1x1_kernel blocks of a plain bf16 1x1 / stride-1 weight gradient of this shape, 0: another kernel (the plan of that launch)
+extern "C" int dh_conv2d_wgrad_1x1_blocks(int N, int H, int W, int Cin, int Cout) {
+    WgArgs a = wg_args(N, H, W, Cin, H, W, Cout, 0);
+    WgPlan p;
+    return wg_plan(a, WgLaunch{WG_BF16, true, 1, 1, 0, false}, p) == WG_OK && p.family == WG_W1 ? (int)p.grid.x : 0;
+}
 // x: [N,H,W,Cin], dy: [N,OH,OW,Cout]; groups == 1: dw_oihw (+)= gradient in torch OIHW layout;
 // groups == N : dw_oihw is [N][Cout][Cin] (ks must be 1) -- one gradient per image.
 // defer != 0: only the partial slabs are written; returns the split-K factor (0: the result went straight into dW)
+// describe != NULL: nothing is launched, the plan goes to describe[12] (batch_open: as a deferred call inside a batch); phase: ks = 2
 static int conv2d_wgrad_impl(int dtype, const void* x, const void* dy, float* dw_oihw, int accumulate, int N,
                              int H, int W, int Cin, int OH, int OW, int Cout, int ks, int stride, int pad,
                              int groups, int npix_valid, int use_tr, int Cout_real, int cin_pitch, int dilation,
                              void* workspace, void* stream, int defer, int* splitk_out, const float* in_scale = nullptr,
                              const float* in_shift = nullptr, int in_groups = 1, const void* dyt_y = nullptr,
-                             const float* dytoef = nullptr, int dyt_groups = 1, long x_split = 0) {
+                             const float* dytoef = nullptr, int dyt_groups = 1, long x_split = 0, int* describe = nullptr,
+                             int batch_open = 0, int phase = 0) {
     DH_REQUIRE(groups == 1 || (groups == N && ks == 1), "conv2d_wgrad: groups must be 1 or N (with ks=1)");
-    WgArgs a;
-    a.x = x; a.dy = dy; a.part = reinterpret_cast<float*>(workspace);
-    a.x_split = x_split;
     DH_REQUIRE(dilation == 1 || (dilation == 2 && ks == 3 && stride == 1), "conv2d_wgrad: dilation %d unsupported here", dilation);
-    a.dil = dilation;
-    a.phase_mode = 0;
-    static const int no_remap = getenv("DAHITRA_NO_XCD_REMAP") ? 1 : 0;
-    a.no_xcd_remap = no_remap;
+    WgArgs a = wg_args(N, H, W, Cin, OH, OW, Cout, pad);
+    a.x = x; a.dy = dy; a.x_split = x_split; a.dil = dilation; a.groups = groups; a.phase_mode = phase;
     a.dyt_y = dyt_y; a.dytoef = dytoef; a.dyt_groups = dyt_groups;
     a.in_scale = in_scale; a.in_shift = in_shift; a.in_groups = in_groups > 0 ? in_groups : 1;
     if (in_scale) DH_REQUIRE(in_shift && groups == 1 && N % a.in_groups == 0 && (Cin * (dtype == DH_DTYPE_BF16 ? 2 : 4)) % 16 == 0,
                              "conv2d_wgrad: BatchNorm-on-load needs in_shift, one weight group, N %% in_groups == 0, 16-byte channel pieces");
-    a.CinPitch = cin_pitch > 0 ? cin_pitch : Cin;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout; a.pad = pad;
-    a.tilesX = dh_cdiv(OW, TW); a.tilesY = dh_cdiv(OH, TH);
-    a.CoutUse = Cout_real > 0 ? Cout_real : Cout;
-    a.groups = groups; a.splitk = dh_conv2d_wgrad_splitk(N, OH, OW, Cin, Cout, ks, groups);
-    // 1x1 with a single K slab: [tap = 1][Cout][Cin] is exactly dW's [Cout][Cin] (also per image: [N][Cout][Cin])
-    a.direct = (ks == 1 && a.splitk == 1 && a.CoutUse == Cout) ? (accumulate ? 2 : 1) : 0;
-    if (a.direct) a.part = dw_oihw;
-    a.npix = npix_valid > 0 ? npix_valid : OH * OW;
-    a.in_npix = npix_valid > 0 ? npix_valid : H * W;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (x_split) {
-        a.ci_tiles = dh_cdiv(Cin, 64);
-        DH_REQUIRE(dtype == DH_DTYPE_BF16 && ws_eligible(a, ks, stride, true, use_tr != 0) && wide_ci3x3(Cin, a.CoutUse, ks),
-                   "conv2d_wgrad: a split input is served by the wave-specialised 3x3 kernel only (Cin=%d Cout=%d ks=%d)", Cin, Cout, ks);
+    if (cin_pitch > 0) a.CinPitch = cin_pitch;
+    if (Cout_real > 0) a.CoutUse = Cout_real;       // dy may carry zero-padded channels
+    if (npix_valid > 0) a.npix = a.in_npix = npix_valid;
+    const int prec = dtype == DH_DTYPE_BF16 ? WG_BF16 : (wgrad_x3(dtype, a) ? WG_X3 : WG_F32);
+    const bool batch = describe ? batch_open != 0 : (g_wsb.on && defer);      // (!defer: reduced right after its launch, never recorded)
+    const WgLaunch l{prec, prec == WG_BF16 ? use_tr != 0 : prec == WG_X3, ks, stride, accumulate, batch};
+    WgPlan p;
+    const int e = wg_plan(a, l, p);
+    if (e == WG_NO_SPLIT) DH_FAIL("conv2d_wgrad: a split input is served by the wave-specialised 3x3 kernel only (Cin=%d Cout=%d ks=%d)", Cin, Cout, ks);
+    if (e == WG_NO_KERNEL) DH_FAIL("conv_wgrad: unsupported kernel %d stride %d", ks, stride);
+    if (describe) {
+        const int v[12] = {p.family, p.ct, p.it, p.cig, p.ci_tiles, p.splitk, p.direct, (int)p.grid.x, (int)p.grid.y, (int)p.grid.z, p.threads, (int)p.lds};
+        memcpy(describe, v, sizeof(v));
+        return 0;
     }
-    const bool batching = g_wsb.on;
-    if (!defer) g_wsb.on = false;           // this call reduces right after its launch: never recorded into a batch
-    int rc = dtype == DH_DTYPE_BF16 ? launch_all<bf16>(a, ks, stride, use_tr != 0, st)
-             : wgrad_x3(dtype, a)   ? launch_all<f32x3>(a, ks, stride, true, st)
-                                    : launch_all<float>(a, ks, stride, false, st);
-    g_wsb.on = batching;
-    if (rc) return rc;
+    a.part = a.direct ? dw_oihw : reinterpret_cast<float*>(workspace);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = wg_launch(a, l, p, st)) return rc;
     if (splitk_out) *splitk_out = a.direct ? 0 : a.splitk;
     if (a.direct || defer) return 0;
-    const int taps = ks * ks;
-    const int oreal = Cout_real > 0 ? Cout_real : Cout;     // dy may carry zero-padded channels
-    const long n = (long)oreal * Cin * taps;
+    const long n = (long)a.CoutUse * Cin * ks * ks;
     hipLaunchKernelGGL(wgrad_reduce_oihw_kernel, dim3(dh_cdiv(n, wgrad_reduce_epb(Cin)), groups), dim3(256), 0, st, a.part, a.splitk,
-                       taps, Cout, oreal, Cin, dw_oihw, accumulate);
+                       ks * ks, Cout, a.CoutUse, Cin, dw_oihw, accumulate);
     DH_CHECK_LAUNCH("wgrad_reduce");
     return 0;
 }
@@ -1414,8 +1424,8 @@ extern "C" int dh_wgrad_batch_pending() { return g_wsb.n + g_c32b.n; }
 // closes the batch WITHOUT launching what it recorded (an aborted pass: the recorded operands may be gone)
 extern "C" int dh_wgrad_batch_abort() { g_wsb.on = false; g_wsb.n = 0; g_wsb.lds = 0; g_c32b.n = 0; g_c32b.lds = 0; return 0; }
 extern "C" int dh_wgrad_batch_launch(void* stream) {
-    const int rc = ws_batch_flush(reinterpret_cast<hipStream_t>(stream));
-    return rc ? rc : c32_batch_flush(reinterpret_cast<hipStream_t>(stream));
+    const int rc = batch_flush(g_wsb, reinterpret_cast<hipStream_t>(stream));
+    return rc ? rc : batch_flush(g_c32b, reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int dh_wgrad_batch_end(void* stream) {
     const int rc = dh_wgrad_batch_launch(stream);
@@ -1444,12 +1454,10 @@ extern "C" int dh_conv2d_wgrad_partial(int dtype, const void* x, const void* dy,
 // dh_conv2d_wgrad_partial for a 3x3 / stride 1 / pad 1 layer whose input is cat([A, B], channel) of two [N][H][W][Cin / 2]
 // tensors, A at x and B at x + x_split_bytes, never materialised (see dh_conv3x3_split_fwd; models/networks.py:1344).
 bool dh_wgrad_split_supported(int N, int H, int W, int Cin, int Cout) {
-    WgArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dil = 1; a.in_groups = 1; a.dyt_groups = 1;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.OH = H; a.OW = W; a.Cout = Cout; a.CoutUse = Cout; a.pad = 1; a.groups = 1;
-    a.CinPitch = Cin / 2; a.x_split = 16; a.npix = H * W; a.in_npix = H * W;
-    return ws_eligible(a, 3, 1, true, true) && wide_ci3x3(Cin, Cout, 3);
+    WgArgs a = wg_args(N, H, W, Cin, H, W, Cout, 1);
+    a.CinPitch = Cin / 2; a.x_split = 16;       // (any offset: the plan asks whether there is one)
+    WgPlan p;
+    return wg_plan(a, WgLaunch{WG_BF16, true, 3, 1, 0, false}, p) == WG_OK && p.family == WG_WS;
 }
 extern "C" int dh_conv2d_wgrad_split(const void* x, long x_split_bytes, const void* dy, float* dw_oihw, int accumulate, int N, int H,
                                      int W, int Cin, int Cout, void* workspace, int* splitk_out, void* stream) {
@@ -1468,6 +1476,17 @@ extern "C" int dh_conv2d_wgrad_bn_in(int dtype, const void* x, const void* dy, f
     return conv2d_wgrad_impl(dtype, x, dy, dw_oihw, accumulate, N, H, W, Cin, OH, OW, Cout, ks, stride, pad, 1, 0, use_tr,
                              Cout_real, 0, dilation, workspace, stream, splitk_out ? 1 : 0, splitk_out, in_scale, in_shift,
                              in_groups);
+}
+// the plan of such a call, for tests and tools (see dahitra_hip.h); ks == 2: of dh_conv2d_wgrad_phase.  Host only
+extern "C" int dh_conv2d_wgrad_describe(int dtype, int accumulate, int N, int H, int W, int Cin, int OH, int OW, int Cout, int ks,
+                                        int stride, int pad, int groups, int npix_valid, int use_tr, int Cout_real, int cin_pitch,
+                                        int dilation, int in_groups, int has_in_scale, int split_input, int batch_open, int* out) {
+    static const float on[1] = {0.f};       // stands for the scale / shift tables: only their presence is planned
+    DH_REQUIRE(out, "conv2d_wgrad_describe: out missing");
+    return conv2d_wgrad_impl(dtype, nullptr, nullptr, nullptr, accumulate, N, H, W, Cin, OH, OW, Cout, ks, stride, pad, groups, npix_valid,
+                             use_tr, Cout_real, split_input ? Cin / 2 : cin_pitch, dilation, nullptr, nullptr, 1, nullptr,
+                             has_in_scale ? on : nullptr, has_in_scale ? on : nullptr, in_groups, nullptr, nullptr, 1,
+                             split_input ? 16 : 0, out, batch_open, ks == 2);
 }
 // The stem's weight gradient with BatchNorm backward applied on load (see WgArgs::dyt_y): xs16 [N][OH][OW][16] bf16 (the
 // space-to-depth by-product of dh_stem7_fwd), d / y [N][OH][OW][64] bf16, coef [groups][3][64] from dh_stem_pool_bn_bwd;
@@ -1491,40 +1510,19 @@ extern "C" int dh_wgrad_reduce_multi(const void* jobs_dev, int njobs, int total_
 }
 
 // ---- 2x2 phase form of conv3x3(nearest-upsample-x2(x)) with 32 output channels: weight gradient per output parity ----
-static int phase_splitk(int N, int H, int W, int Cin) {
-    const long tiles = (long)N * dh_cdiv(W, TW) * dh_cdiv(H, TH);
-    const long slabs = (long)dh_cdiv(Cin, 32);                 // one 32-wide co tile x ci tiles, per phase
-    long sk = (128 + slabs - 1) / slabs;                       // 4 phases x slabs x sk ~ 512 workgroups
-    if (sk > tiles / 8) sk = tiles / 8;
-    return (int)(sk < 1 ? 1 : sk);
-}
 extern "C" long dh_conv2d_wgrad_phase_workspace_size(int N, int H, int W, int Cin) {
-    return (long)4 * phase_splitk(N, H, W, Cin) * 4 * 32 * Cin * 4;
+    WgArgs a = wg_args(N, H, W, Cin, H, W, 32, 1);
+    a.phase_mode = 1;
+    WgPlan p;
+    wg_plan(a, WgLaunch{WG_BF16, true, 2, 1, 0, false}, p);
+    return (long)4 * p.splitk * 4 * 32 * Cin * 4;
 }
 extern "C" int dh_conv2d_wgrad_phase(int dtype, const void* x, const void* dy, int N, int H, int W, int Cin, int use_tr,
                                      void* workspace, int* splitk_out, void* stream) {
     DH_REQUIRE(splitk_out && workspace, "conv2d_wgrad_phase: workspace / splitk_out missing");
     DH_REQUIRE((Cin * (dtype == DH_DTYPE_BF16 ? 2 : 4)) % 16 == 0, "conv2d_wgrad_phase: Cin=%d not 16-byte aligned", Cin);
-    WgArgs a;
-    a.x = x; a.dy = dy; a.part = reinterpret_cast<float*>(workspace);
-    a.dil = 1; a.phase_mode = 1;
-    a.no_xcd_remap = getenv("DAHITRA_NO_XCD_REMAP") ? 1 : 0;
-    a.dyt_y = nullptr; a.dytoef = nullptr; a.dyt_groups = 1;
-    a.in_scale = nullptr; a.in_shift = nullptr; a.in_groups = 1;
-    a.CinPitch = Cin;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.OH = H; a.OW = W; a.Cout = 32; a.pad = 1;
-    a.tilesX = dh_cdiv(W, TW); a.tilesY = dh_cdiv(H, TH);
-    a.CoutUse = 32;
-    a.x_split = 0;
-    a.groups = 1; a.splitk = phase_splitk(N, H, W, Cin);
-    a.direct = 0;
-    a.npix = H * W; a.in_npix = H * W;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int rc = dtype == DH_DTYPE_BF16 ? launch_all<bf16>(a, 2, 1, use_tr != 0, st)
-                   : wgrad_x3(dtype, a)   ? launch_all<f32x3>(a, 2, 1, true, st) : launch_all<float>(a, 2, 1, false, st);
-    if (rc) return rc;
-    *splitk_out = a.splitk;
-    return 0;
+    return conv2d_wgrad_impl(dtype, x, dy, nullptr, 0, N, H, W, Cin, H, W, 32, 2, 1, 1, 1, 0, use_tr, 0, 0, 1, workspace, stream, 1,
+                             splitk_out, nullptr, nullptr, 1, nullptr, nullptr, 1, 0, nullptr, 0, 1);
 }
 
 namespace {

@@ -122,8 +122,18 @@ int dh_conv2d_wgrad(int dtype, const void* x, const void* dy, float* dw_oihw, in
                     int npix_valid, int use_tr, int Cout_real, int cin_pitch, int dilation, void* workspace, void* stream);
 /* > 0: a plain bf16 1x1 / stride-1 weight gradient of this shape runs in the block form (wgrad1x1_kernel: a 256 x 128 / 128 x 256 /
  * 256 x 64 / 64 x 256 block of dW per workgroup over flat pixels, all blocks of a pixel split on one XCD); the value = blocks per
- * split.  0: the 64 x 64-slab kernel (too few pixels to fill the chip with fat blocks, or a small layer). */
+ * split.  0: the 64 x 64-slab kernel (too few pixels to fill the chip with fat blocks, a small layer, or a launch that goes
+ * direct: split-K 1 -- a handful of pixel tiles -- writes dW itself, whatever the channel counts). */
 int dh_conv2d_wgrad_1x1_blocks(int N, int H, int W, int Cin, int Cout);
+/* Host only (no launch, no device): the launch plan of a dh_conv2d_wgrad / _partial call with these arguments, of dh_conv2d_wgrad_bn_in
+ * (has_in_scale, in_groups), of dh_conv2d_wgrad_split (split_input: cin_pitch is Cin / 2) and, with ks == 2, of
+ * dh_conv2d_wgrad_phase(dtype, N, H, W, Cin, use_tr); batch_open: as a deferred call between dh_wgrad_batch_begin and _end.
+ * out[12] = family (0 wgrad1x1_kernel, 1 the wave-specialised 3x3 kernel, 2 / 3 recorded into the wave-specialised / the 32-wide
+ * job-table launch, 4 conv_wgrad_kernel, 5 its 2x2 phase form), co tile, ci channels per workgroup, ci wave groups, ci tiles,
+ * split-K factor, direct, grid x, y, z, threads, dynamic LDS bytes.  Returns non-zero where the launch itself would be refused. */
+int dh_conv2d_wgrad_describe(int dtype, int accumulate, int N, int H, int W, int Cin, int OH, int OW, int Cout, int ks, int stride,
+                             int pad, int groups, int npix_valid, int use_tr, int Cout_real, int cin_pitch, int dilation,
+                             int in_groups, int has_in_scale, int split_input, int batch_open, int* out);
 long dh_conv2d_wgrad_workspace_size(int N, int OH, int OW, int Cin, int Cout, int ks, int groups);
 /* The weight gradient with its split-K reduce deferred: only the partial slabs are written into `workspace` (which
  * must stay alive until the batched reduce) and *splitk_out receives their count (0: the single-slab 1x1 case wrote
@@ -160,7 +170,7 @@ int dh_conv2d_wgrad_split(const void* x, long x_split_bytes, const void* dy, flo
 /* classifier.0 on nn.Upsample(4, 'bilinear')(abs(x1 - x2)) WITHOUT that map (models/networks.py:383-389, models/help_funcs.py:9;
  * bf16): a, b [N][H / 4][W / 4][32] are the two streams' decoder outputs, H x W the fine size (multiples of 4).
  *   dh_conv3x3_up4_fwd   y [N][H][W][32] = act(conv3x3(upsample4(|a - b|)) + bias), act 0 / ReLU; w_packed [9][32][32]
- *                        (dh_pack_weight forward form); stats_partial as dh_conv2d_fwd, dh_conv2d_fwd_num_tiles(DH_BF16, N, H, W, 32, 3, 1)
+ *                        (dh_pack_weight forward form); stats_partial as dh_conv2d_fwd, dh_conv2d_fwd_num_tiles(DH_DTYPE_BF16, N, H, W, 32, 3, 1)
  *                        rows.  The 8 x 16-pixel tile's haloed input is interpolated from its 4 x 6 coarse footprint with the
  *                        terms and order of dh_absdiff_upsample4_fwd: equal to dh_conv2d_fwd on that kernel's output, bit for bit.
  * (the data gradient through the upsample is dh_conv3x3_dgrad_up4; the weight gradient still reads the materialised map:

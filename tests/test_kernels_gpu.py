@@ -1,6 +1,7 @@
 """Per-kernel parity: every C-ABI entry point against a plain torch fp32 computation of the same op
 on the CPU (same seeded inputs).  fp32 mode must agree to fp32 round-off (the parity mode of the
 product); bf16 mode to bf16 round-off of inputs/outputs (2^-8 relative)."""
+import ctypes
 import numpy as np
 import pytest
 import torch
@@ -36,6 +37,19 @@ def nhwc(x):      # NCHW cpu -> NHWC
 
 def nchw(x):
     return x.permute(0, 3, 1, 2).contiguous()
+
+
+W1, WS, WS_BATCH, C32_BATCH, GENERIC, PHASE = range(6)      # the kernel families of dh_conv2d_wgrad_describe
+
+
+def wgrad_plan(ops, dtype, N, H, W, Cin, OH, OW, Cout, ks, stride=1, pad=0, dil=1, tr=True, bn_groups=0, batch=False):
+    """dh_conv2d_wgrad_describe's row [family, ct, it, cig, ci_tiles, splitk, direct, grid x, y, z, threads, lds] for the launch
+    ops.conv2d_wgrad (ks = 2: ops.conv_up2_wgrad) makes of these arguments"""
+    out = (ctypes.c_int * 12)()
+    rc = ops._lib.lib().dh_conv2d_wgrad_describe(int(dtype == torch.bfloat16), 0, N, H, W, Cin, OH, OW, Cout, ks, stride, pad, 1, 0,
+                                                 int(tr), 0, 0, dil, bn_groups, int(bn_groups > 0), 0, int(batch), out)
+    ops._lib.check(rc, "dh_conv2d_wgrad_describe")
+    return list(out)
 
 
 @pytest.fixture(scope="module")
@@ -176,6 +190,9 @@ def test_conv2d_dgrad_and_wgrad(ops, dtype, mma, cfg):
                     dilation=dil)
     close(nchw(dx), x.grad, dtype, "dgrad", factor=2.0)
     for tr in ([True, False] if dtype == torch.bfloat16 else [False]):
+        if not tr:          # conv_wgrad_kernel itself: nothing else takes fp32 or a launch without transpose reads
+            assert wgrad_plan(ops, dtype, N, cfg["h"], cfg["w"], cfg["cin"], y.shape[2], y.shape[3], cfg["cout"], cfg["ks"],
+                              cfg["stride"], cfg["pad"], dil, tr=False)[0] == GENERIC
         dw = torch.full(tuple(w.shape), 0.5, device="cuda")
         ops.conv2d_wgrad(dev(nhwc(x.detach()), dtype), dev(nhwc(dy), dtype), dw, cfg["ks"], cfg["stride"], cfg["pad"],
                          accumulate=True, use_tr=tr, dilation=dil)
@@ -895,6 +912,9 @@ def test_conv2d_dgrad_wgrad_bench_scale(ops, dtype, mma, cfg):
     dx = ops.conv2d(dev(dyp, dtype), wd, cfg["cin"], 3, 1, 1)
     close(nchw(dx), x.grad, dtype, "dgrad (bench scale)", factor=2.0)
     xd, dyd = dev(nhwc(x.detach()), dtype), dev(nhwc(dy), dtype)
+    if dtype == torch.bfloat16:        # the wave-specialised kernel; conv_pred: the 32-wide co tile of conv_wgrad_kernel
+        p = wgrad_plan(ops, dtype, N, cfg["h"], cfg["w"], cfg["cin"], cfg["h"], cfg["w"], cfg["cout"], 3, 1, 1)
+        assert p[:2] == ([WS, 64] if cfg["cout"] % 64 == 0 else [GENERIC, 32])
     gscale = float(w.grad.abs().max())
     # K = N*H*W pixels (65 536 .. 131 072): bf16 products, fp32 accumulation in split-K slabs
     fac = 4.0 if dtype == torch.float32 else 1.0
@@ -935,6 +955,8 @@ def test_weight_gradient_of_wide_1x1_layers_in_256_by_128_blocks(ops, cfg):
     N, H, W, Cin, Cout = cfg["n"], cfg["h"], cfg["w"], cfg["cin"], cfg["cout"]
     st = cfg.get("stride", 1)
     assert ops._lib.lib().dh_conv2d_wgrad_1x1_blocks(N, H, W, Cin, Cout) == cfg["blocks"]       # (H, W: the OUTPUT grid)
+    p = wgrad_plan(ops, dtype, N, st * H - (st - 1), st * W - (st - 1), Cin, H, W, Cout, 1, st)
+    assert (p[0], p[7]) == (W1, cfg["blocks"]) if cfg["blocks"] else p[0] == GENERIC
     x = rnd((N, Cin, st * H - (st - 1), st * W - (st - 1)), dtype, 2301)
     w = rnd((Cout, Cin, 1, 1), dtype, 2302, scale=Cin ** -0.5).requires_grad_(True)
     y = F.conv2d(x, w, None, st)
@@ -1148,6 +1170,9 @@ def test_weight_gradients_of_a_pass_in_one_launch(ops):
             x = ops.BnInput(x, sc, sh, 2)
         xs.append(x)
         dys.append(dev(rnd((L["n"], L["h"], L["w"], L["o"]), dtype, 1260 + i, 1.0), dtype))
+    fams = [wgrad_plan(ops, dtype, L["n"], L["h"], L["w"], L["c"], L["h"], L["w"], L["o"], 3, 1, 1, bn_groups=2 * L["bn"], batch=True)[0]
+            for L in layers]
+    assert fams == [WS_BATCH] * 4 + [C32_BATCH] * 2 + [GENERIC]
     out = {}
     for batch in (False, True):
         plan = ops.WgradPlan("cuda", batch=batch)
@@ -1339,6 +1364,7 @@ def test_upsample2_conv3x3_as_four_phase_convs(ops, dtype, mma, cfg):
     dx = ops.conv_up2_dgrad(dyd, wd, Cin)
     close(nchw(dx), x.grad, dtype, "phase conv data gradient", factor=3.0)
     dw = torch.full((32, Cin, 3, 3), 0.5, device="cuda")
+    assert wgrad_plan(ops, dtype, N, H, W, Cin, H, W, 32, 2, 1, 1)[0] == PHASE
     ops.conv_up2_wgrad(xd, dyd, dw, accumulate=True)
     fac = 4.0 if dtype == torch.float32 or N < 64 else 1.0
     close(dw - 0.5, w.grad, dtype, "phase conv weight gradient", factor=fac)
