@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void head_dgrad3x3_reg_kernel(const T* __restr
 // horizontal / vertical flip, ToTensor + Normalize(0.5, 0.5) -- for a whole batch in one pass: a PIL loader delivers a few
 // hundred pairs/s per worker, the train step consumes ~7 000.  src images [S][H][W][3] uint8 (A and B), labels [S][H][W]
 // uint8; sample n takes source pair idx[n] with params[n] = {x0, y0, hflip, vflip}; outputs A / B fp32 [N][3][h][w] in
-// [-1, 1] and L uint8 [N][1][h][w].  (The reference's random Gaussian blur has no counterpart here.)
+// [-1, 1] and L uint8 [N][1][h][w].  (The reference's random Gaussian blur has no counterpart in this kernel; see augment_blur.hip.)
 __global__ void augment_pairs_u8_kernel(const unsigned char* __restrict__ a, const unsigned char* __restrict__ b,
                                         const unsigned char* __restrict__ l, const int* __restrict__ idx,
                                         const int* __restrict__ params, int N, int H, int W, int h, int w,

@@ -12,7 +12,7 @@ and never implemented scale-crop; split='train' reads `.size[1]` of its first in
 images have.
 
 The per-sample PIL work (decode, blur) caps a loader at a few hundred pairs/s per worker while the MI355X step consumes
-~7 000 pairs/s: dahitra_amd/datasets/gpu_pipeline.py is the pre-decoded, on-device alternative."""
+~7 000 pairs/s: dahitra_amd/datasets/gpu_pipeline.py is the pre-decoded, on-device alternative (the blur included)."""
 import random
 
 import numpy as np

@@ -1,14 +1,18 @@
-"""Pre-decoded image pairs resident in HBM + crop / flip / normalise on the device (dh_augment_pairs_u8).
+"""Pre-decoded image pairs resident in HBM + crop / flip / blur / normalise on the device (dh_augment_pairs_u8,
+dh_augment_pairs_blur_u8).
 
 The reference's loader decodes two PNGs and runs PIL transforms per sample in DataLoader workers
 (datasets/CD_dataset.py:112-134, datasets/data_utils.py:55-111); at the ~7 000 pairs/s of the MI355X train step that is the
 bottleneck by an order of magnitude.  A LEVIR-sized training set (7 120 pairs of 256x256x3 uint8 = 2.8 GB, or the 445
 1024x1024 tiles) fits the 288 GB of HBM many times over, so: decode once (`from_dataset_root`, same folder layout as
 CDDataset), keep uint8 on the device, and produce every batch with ONE kernel -- same crop-window rule, same flip
-probabilities, same normalisation as CDDataAugmentation; the random Gaussian blur is the one augmentation not reproduced.
+probabilities, same normalisation as CDDataAugmentation.  With `blur=True` the batch also gets the reference's random
+Gaussian blur (ImageFilter.GaussianBlur(radius=random.random()) on both images of a training sample, datasets/data_utils.py:
+99-102), byte for byte what Pillow computes: flips + blur is the reference's training augmentation.  The blur is off by
+default (the loader then produces what it always did).
 
     pipe = GpuPairPipeline.from_dataset_root(root, split='train', device='cuda:0')
-    for batch in pipe.batches(batch_size=32, img_size=256, train=True, generator=g):   # {'A', 'B', 'L', 'name'}
+    for batch in pipe.batches(batch_size=32, img_size=256, train=True, generator=g, blur=True):   # {'A', 'B', 'L', 'name'}
         trainer.train_step(batch)
 """
 import os
@@ -19,6 +23,48 @@ from PIL import Image
 
 from .. import ops
 from .CD_dataset import get_img_path, get_img_post_path, get_label_path
+
+
+def box_blur_weights(radius):
+    """(ww, fw) of Pillow's ImageFilter.GaussianBlur(radius) for a radius whose box has integer radius 0 (radius < sqrt(2);
+    the reference draws radius = random.random() < 1).  Pillow approximates the Gaussian by three box-blur passes per axis
+    (BoxBlur.c); a box of radius 0 + a, 0 <= a < 1, is the 3-tap filter
+        out[x] = (in[x] * ww + (in[x - 1] + in[x + 1]) * fw + (1 << 23)) >> 24
+    on uint8 with the edge pixel replicated, and (ww, fw) are 8.24 fixed-point weights.  The derivation follows Pillow's
+    _gaussian_blur_radius(radius, passes=3) and ImagingLineBoxBlur in ITS precision, float32: a float64 derivation gives
+    another ww for some radii (0.25: 16427690 instead of 16427691).  Checked byte for byte against Pillow on random radii in
+    [0, sqrt(2)) and on {0, 1e-9, 1e-3, 0.25, 0.5, 0.999999} (tests/test_gpu_blur_cpu.py).  radius == 0 is a special case in
+    Pillow (GaussianBlur.filter returns image.copy() without calling the C filter); the formula gives (1 << 24, 0) there,
+    the identity, so it needs no special case here.  ValueError for a negative or non-finite radius and for one whose box
+    has a non-zero integer radius (radius >= sqrt(2))."""
+    ww, fw = _box_blur_weights(np.asarray([radius], dtype=np.float32))
+    return int(ww[0]), int(fw[0])
+
+
+def _box_blur_weights(r):
+    """box_blur_weights for a float32 array of radii -> (ww, fw) int64 arrays; every operation rounds to float32"""
+    f = np.float32
+    bad = ~np.isfinite(r) | (r < 0)
+    if bad.any():
+        raise ValueError("blur radius %r is negative or not finite" % (float(r[bad][0]),))
+    sigma2 = r * r / f(3)
+    big_l = np.sqrt(f(12) * sigma2 + f(1))
+    l = np.floor((big_l - f(1)) / f(2))
+    if (l != 0).any():
+        raise ValueError("blur radius %r: its box is not a 3-tap filter (radius must be < sqrt(2))" % (float(r[l != 0][0]),))
+    a = (f(2) * l + f(1)) * (l * (l + f(1)) - f(3) * sigma2) / (f(6) * (sigma2 - (l + f(1)) * (l + f(1))))
+    ww = (f(1 << 24) / (f(2) * (l + a) + f(1))).astype(np.int64)        # truncation, as the C cast to UINT32
+    return ww, ((1 << 24) - ww) // 2
+
+
+def blur_table(radii):
+    """[n, 2] int32 (ww, fw) rows for dh_augment_pairs_blur_u8, with the bounds its 32-bit accumulator relies on checked
+    where the table is written: 0 < ww <= 1 << 24, fw >= 0, ww + 2 fw <= 1 << 24 (255 (ww + 2 fw) + (1 << 23) < 2^32)"""
+    ww, fw = _box_blur_weights(np.asarray(radii, dtype=np.float32).reshape(-1))
+    bad = ~((0 < ww) & (ww <= 1 << 24) & (fw >= 0) & (ww + 2 * fw <= 1 << 24))
+    if bad.any():
+        raise ValueError("blur weights (%d, %d) outside 0 < ww <= 2^24, ww + 2 fw <= 2^24" % (ww[bad][0], fw[bad][0]))
+    return torch.from_numpy(np.stack([ww, fw], axis=1).astype(np.int32))
 
 
 class GpuPairPipeline:
@@ -42,9 +88,10 @@ class GpuPairPipeline:
     def __len__(self):
         return self.a.shape[0]
 
-    def make_batch(self, indices, img_size, flips=None, patch=None):
-        """indices: source pairs of the batch; flips: [n, 2] 0/1 (hflip, vflip) or None.  The crop window follows
-        CDDataAugmentation: origin (256, 256) -- or the patch origin for a non-zero patch index -- when
+    def make_batch(self, indices, img_size, flips=None, patch=None, blur=None):
+        """indices: source pairs of the batch; flips: [n, 2] 0/1 (hflip, vflip) or None; blur: n Gaussian-blur radii
+        (box_blur_weights) applied to A and B of each sample after the crop, or None for no blur (the unblurred kernel).  The
+        crop window follows CDDataAugmentation: origin (256, 256) -- or the patch origin for a non-zero patch index -- when
         img_size < width // 2, the whole image otherwise."""
         n = len(indices)
         S, H, W, _ = self.a.shape
@@ -60,18 +107,28 @@ class GpuPairPipeline:
         params[:, 0], params[:, 1] = x0, y0
         if flips is not None:
             params[:, 2:] = torch.as_tensor(flips, dtype=torch.int32)
+        if blur is not None:
+            if len(blur) != n:
+                raise ValueError("blur: %d radii for %d samples" % (len(blur), n))
+            table = blur_table(blur)
         dev = self.a.device
         idx = torch.as_tensor(indices, dtype=torch.int32).to(dev)
         params = params.to(dev)
         out_a = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
         out_b = torch.empty_like(out_a)
         out_l = torch.empty(n, 1, h, w, dtype=torch.uint8, device=dev)
-        ops._call("dh_augment_pairs_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params), n, H, W, h, w,
-                  ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
+        if blur is None:
+            ops._call("dh_augment_pairs_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params), n, H, W,
+                      h, w, ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
+        else:
+            table = table.to(dev)
+            ops._call("dh_augment_pairs_blur_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params),
+                      ops.P(table), n, H, W, h, w, ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
         return {'A': out_a, 'B': out_b, 'L': out_l, 'name': [self.names[i] for i in indices]}
 
-    def batches(self, batch_size, img_size, train=True, generator=None, patch=None, drop_last=False):
-        """one epoch: shuffled with random flips (p = 0.5 each, as the reference's training augmentation) when `train`"""
+    def batches(self, batch_size, img_size, train=True, generator=None, patch=None, drop_last=False, blur=False):
+        """one epoch: shuffled with random flips (p = 0.5 each, as the reference's training augmentation) when `train`; with
+        `blur` a training batch also draws one blur radius in [0, 1) per sample, after its flips (evaluation never blurs)"""
         S = len(self)
         order = torch.randperm(S, generator=generator).tolist() if train else list(range(S))
         for s in range(0, S, batch_size):
@@ -79,17 +136,20 @@ class GpuPairPipeline:
             if drop_last and len(ind) < batch_size:
                 break
             flips = (torch.rand(len(ind), 2, generator=generator) > 0.5).int() if train else None
-            yield self.make_batch(ind, img_size, flips, patch)
+            radii = torch.rand(len(ind), generator=generator).tolist() if train and blur else None
+            yield self.make_batch(ind, img_size, flips, patch, radii)
 
 
 class GpuPairLoader:
     """A DataLoader-shaped view of a GpuPairPipeline (`for batch in loader`, `len(loader)`): what utils.get_loaders returns
-    with args.gpu_loader.  Every epoch draws a fresh permutation and fresh flips from `generator` (train mode).  With
+    with args.gpu_loader.  Every epoch draws a fresh permutation and fresh flips from `generator` (train mode), and with
+    `blur` one Gaussian-blur radius in [0, 1) per sample after the flips of its batch (train mode only).  With
     world > 1 the epoch's permutation is cut into equal per-rank shards (every rank must pass an equally seeded generator;
     the tail that does not fill a full global batch is dropped so that all ranks take the same number of steps)."""
 
-    def __init__(self, pipe, batch_size, img_size, train, generator=None, drop_last=False, rank=0, world=1):
+    def __init__(self, pipe, batch_size, img_size, train, generator=None, drop_last=False, rank=0, world=1, blur=False):
         self.pipe, self.batch_size, self.img_size, self.train = pipe, int(batch_size), img_size, train
+        self.blur = bool(blur) and bool(train)
         self.generator, self.drop_last, self.rank, self.world = generator, drop_last or world > 1, rank, world
 
     def __len__(self):
@@ -106,4 +166,5 @@ class GpuPairLoader:
             if self.drop_last and len(ind) < self.batch_size:
                 break
             flips = (torch.rand(len(ind), 2, generator=self.generator) > 0.5).int() if self.train else None
-            yield self.pipe.make_batch(ind, self.img_size, flips)
+            radii = torch.rand(len(ind), generator=self.generator).tolist() if self.blur else None
+            yield self.pipe.make_batch(ind, self.img_size, flips, blur=radii)

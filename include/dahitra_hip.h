@@ -331,6 +331,14 @@ int dh_reduce_partials(const float* partial, long nt, long n, float scale, float
 int dh_augment_pairs_u8(const unsigned char* a, const unsigned char* b, const unsigned char* l, const int* idx,
                         const int* params, int N, int H, int W, int h, int w, float* out_a, float* out_b,
                         unsigned char* out_l, void* stream);
+/* The same batch with the reference's random Gaussian blur on A and B (PIL ImageFilter.GaussianBlur(radius), radius < sqrt(2),
+ * datasets/data_utils.py:99-102), byte-exact: three 3-tap box passes along the rows, then three along the columns, on uint8 with
+ * the window's edge pixel replicated in every pass, out = (in * ww + (left + right) * fw + (1 << 23)) >> 24.  blur [N][2] int32 =
+ * sample n's (ww, fw), 0 < ww <= 1 << 24, fw >= 0, ww + 2 fw <= 1 << 24 (the caller checks them where it writes the table:
+ * the 32-bit accumulator relies on it); (1 << 24, 0) is the unblurred result bit for bit.  Labels are not blurred. */
+int dh_augment_pairs_blur_u8(const unsigned char* a, const unsigned char* b, const unsigned char* l, const int* idx,
+                             const int* params, const int* blur, int N, int H, int W, int h, int w, float* out_a,
+                             float* out_b, unsigned char* out_l, void* stream);
 int dh_nchw_to_nhwc(int dtype, const float* src, void* dst, int N, int C, long HW, int CP, void* stream);
 /* data gradient of the class head (3x3 / s1 / p1, 32 -> n_class <= 8 channels; help_funcs.py:13-14, networks.py:1247):
  * dy [N][H][W][CP] (CP = 8 bf16 / 4 or 8 fp32 channels per pixel, the first NC real), w_oihw [NC][32][3][3] fp32,
