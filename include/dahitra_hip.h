@@ -339,6 +339,22 @@ int dh_augment_pairs_u8(const unsigned char* a, const unsigned char* b, const un
 int dh_augment_pairs_blur_u8(const unsigned char* a, const unsigned char* b, const unsigned char* l, const int* idx,
                              const int* params, const int* blur, int N, int H, int W, int h, int w, float* out_a,
                              float* out_b, unsigned char* out_l, void* stream);
+/* Input pipeline of the xBD step (TrainData / ValData.__getitem__, xBD_code/train.py:99-183, 194-244, for pre-decoded samples):
+ * pre, post [n_src][H][W][3] uint8, pre_mask (0 / 255; NULL in train mode, which overwrites it) and post_label (0 .. 4)
+ * [n_src][H][W] uint8.  Output sample n takes source idx[n] with params[n] = {x0, y0, hflip, vflip, resize, top, left, height,
+ * width}: the S x S crop at (x0, y0), the flips, then -- if `resize` -- TF.resized_crop(img, top, left, height, width, (S, S)) on
+ * all four arrays (train.py:132-136), byte-exact: PIL's img.crop(box).resize((S, S), Image.BILINEAR), two fixed-point passes
+ * (rows, then columns) that each round to uint8.  The box lies inside the crop, 1 <= height, width <= S.  coef [N][2][S][4] int32
+ * = (first source index, k0, k1, k2) of every output index, axis 0 along x (`width` source pixels) and axis 1 along y (`height`),
+ * as datasets/xbd_pipeline.resize_coeffs writes it.  The caller guarantees 0 <= k and k0 + k1 + k2 <= (1 << 22) + 8192: a pass's
+ * byte is then in range without a clip.  Rows of samples without the flag are not read, and coef == NULL means that no sample
+ * resizes (the flag is then ignored).  Then the masks: mode 0 (train) msk[k] = (label == k)
+ * for k = 1 .. 4 and msk[0] = any of them; mode 1 (val) msk[0] = (pre_mask > 127) instead, and out_lbl = label - 1 where label is
+ * 1 .. 4, else 0.  out_img fp32 [N][6][S][S] = preprocess_inputs(concat(pre, post)) = x / 127 - 1; out_msk uint8 [N][5][S][S],
+ * 0 / 1; out_lbl uint8 [N][S][S], written in mode 1 only (NULL allowed in mode 0). */
+int dh_xbd_augment_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* pre_mask,
+                      const unsigned char* post_label, const int* idx, const int* params, const int* coef, int N, int H, int W,
+                      int S, int mode, float* out_img, unsigned char* out_msk, unsigned char* out_lbl, void* stream);
 int dh_nchw_to_nhwc(int dtype, const float* src, void* dst, int N, int C, long HW, int CP, void* stream);
 /* data gradient of the class head (3x3 / s1 / p1, 32 -> n_class <= 8 channels; help_funcs.py:13-14, networks.py:1247):
  * dy [N][H][W][CP] (CP = 8 bf16 / 4 or 8 fp32 channels per pixel, the first NC real), w_oihw [NC][32][3][3] fp32,

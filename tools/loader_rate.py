@@ -6,6 +6,12 @@ pays per batch: the parameter tables' host-to-device copies, the output allocati
 (dh_augment_pairs_u8 / dh_augment_pairs_blur_u8 on tables already on the device).
 
     python tools/loader_rate.py [--batch 32] [--size 256] [--sources 64] [--rounds 5]
+
+--xbd measures the xBD loader instead (datasets/xbd_pipeline.py, dh_xbd_augment_u8): batches of `--size` crops from sources of
+the same size, in three variants -- no sample resized, every sample resized with a box at the mean of the reference's offsets
+(top = left = 100: the worst case, every byte goes through both passes with real coefficients), and val mode.
+
+    python tools/loader_rate.py --xbd --batch 4 --size 1024 --sources 8
 """
 import argparse
 import os
@@ -35,8 +41,62 @@ def timed(fn):
     return e0.elapsed_time(e1) / REPS * 1e3
 
 
+def main_xbd(args):
+    from dahitra_amd.datasets.xbd_pipeline import GpuXbdPipeline, check_params, coef_table
+    n, sz, S = args.batch, args.size, args.sources
+    g = torch.Generator().manual_seed(1)
+    pre = torch.randint(0, 256, (S, sz, sz, 3), generator=g, dtype=torch.uint8).cuda()
+    post = torch.randint(0, 256, (S, sz, sz, 3), generator=g, dtype=torch.uint8).cuda()
+    pmask = ((torch.rand(S, sz, sz, generator=g) > 0.9) * 255).to(torch.uint8).cuda()
+    label = torch.randint(0, 5, (S, sz, sz), generator=g, dtype=torch.uint8).cuda()
+    pipe = GpuXbdPipeline(pre, post, pmask, label)
+    ind = torch.randint(0, S, (n,), generator=g).tolist()
+    flips = (torch.rand(n, 2, generator=g) > 0.5).int().tolist()
+    off = min(100, sz // 4)
+    rows = {"plain": [[0, 0, hf, vf, 0, 0, 0, sz, sz] for hf, vf in flips],
+            "resized": [[0, 0, hf, vf, 1, off, off, sz - off, sz - off] for hf, vf in flips]}
+    rows["val"] = [[0, 0, 0, 0, 0, 0, 0, sz, sz]] * n
+
+    dev = pre.device
+    idx = torch.tensor(ind, dtype=torch.int32, device=dev)
+    img = torch.empty(n, 6, sz, sz, dtype=torch.float32, device=dev)
+    msk = torch.empty(n, 5, sz, sz, dtype=torch.uint8, device=dev)
+    lbl = torch.empty(n, sz, sz, dtype=torch.uint8, device=dev)
+    tables = {}
+    for k, r in rows.items():
+        p = check_params(r, sz, sz, sz)
+        c = coef_table(p, sz)
+        tables[k] = (p.to(dev), c.to(dev) if c is not None else None)
+
+    def kernel(k):
+        p, c = tables[k]
+        val = k == "val"
+        ops._call("dh_xbd_augment_u8", ops.P(pre), ops.P(post), ops.P(pmask if val else None), ops.P(label), ops.P(idx), ops.P(p),
+                  ops.P(c), n, sz, sz, sz, int(val), ops.P(img), ops.P(msk), ops.P(lbl if val else None), ops.S())
+
+    variants = {}
+    for k in rows:
+        variants["make_batch " + k] = lambda k=k: pipe.make_batch(ind, sz, rows[k], train=k != "val")
+        variants["kernel " + k] = lambda k=k: kernel(k)
+    times = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for k, fn in variants.items():
+            times[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    for k in variants:
+        print("%-19s %8.1f us per batch of %d  (min %.1f)  %9.0f samples/s" % (k, med[k], n, min(times[k]), n / med[k] * 1e6))
+    # bytes the kernel has to move: the source pixels inside the box (6 + 1 bytes, + 1 in val mode) and the outputs
+    out_b = n * sz * sz * (6 * 4 + 5)
+    for k in rows:
+        side = sz - off if k == "resized" else sz
+        in_b = n * side * side * (8 if k == "val" else 7)
+        tot = in_b + out_b + (n * sz * sz if k == "val" else 0)
+        print("kernel %-8s %.1f MB in + %.1f MB out: %.2f TB/s" % (k, in_b / 1e6, (tot - in_b) / 1e6, tot / med["kernel " + k] / 1e6))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--xbd", action="store_true", help="the xBD loader (datasets/xbd_pipeline.py) instead of the pair loader")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--sources", type=int, default=64)
@@ -44,6 +104,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("loader_rate: needs the GPU (no rate is reported without one)")
+    if args.xbd:
+        return main_xbd(args)
     n, sz, S = args.batch, args.size, args.sources
     g = torch.Generator().manual_seed(1)
     a = torch.randint(0, 256, (S, sz, sz, 3), generator=g, dtype=torch.uint8).cuda()
