@@ -1,32 +1,39 @@
-"""Pre-decoded xBD samples resident in HBM + TrainData / ValData.__getitem__ on the device (dh_xbd_augment_u8).
+"""Pre-decoded xBD samples resident in HBM + TrainData / ValData.__getitem__ on the device (dh_xbd_augment_u8,
+dh_xbd_augment_jitter_u8).
 
 The reference's xBD loader opens four 1024x1024 PNGs per sample (pre and post image, pre mask, post label) and, in training,
 crops, flips and bilinearly resizes all four in Pillow before it builds the mask channels (xBD_code/train.py:99-183); DataLoader
 workers do not feed the MI355X xBD step that way.  Here the four uint8 stacks are decoded once and stay on the device, and ONE
 kernel per batch produces what `GraphedXbdStep(net, opt, imgs, msks)` consumes: crop, flips, TF.resized_crop -- Pillow's
 two-pass fixed-point BILINEAR resize, byte for byte, on the masks as well -- the five mask channels and preprocess_inputs.
+With `jitter_gen` the 9 % of the samples that draw it also get the reference's ColorJitter (train.py:138-139), byte for byte what
+PIL's ImageEnhance chain computes; a batch with such a sample takes a second launch for contrast's whole-image mean.
 
     pipe = GpuXbdPipeline.from_image_dir('/data/xbd/train/images', device='cuda:0')
-    for batch in pipe.batches(4, 1024, train=True, rng=random.Random(0)):        # {'img', 'msk', 'lbl_msk', 'fn'}
-        loss = step(batch['img'], batch['msk'])
+    for batch in pipe.batches(4, 1024, train=True, rng=random.Random(0), jitter_gen=torch.Generator().manual_seed(0)):
+        loss = step(batch['img'], batch['msk'])                                  # {'img', 'msk', 'lbl_msk', 'fn'}
 
 Differences from the reference, all deliberate:
   * `msk` is uint8 (0 / 1), not long: the step casts it to float where it always did (graph.py, GraphedXbdStep._loss_and_grad;
     models/xbd.xbd_loss), and 5 bytes per pixel instead of 40 is most of the batch's mask traffic.  `lbl_msk` is uint8 too.
   * `lbl_msk` of a TRAINING batch is zeros, as in the reference: there msk[0] is set wherever any other channel is, so
     msk.argmax(axis=2) is 0 at every pixel (train.py:171-174).  One zero tensor is kept and returned; do not write to it.
-  * ColorJitter (train.py:138-139, 9 % of the samples) is not applied: it is torchvision's, drawn from torch's generator.
-    `draw_train_params` consumes the reference's Python draws up to and including the one that decides it and reports the flag.
+  * ColorJitter is applied only to an epoch that is given `jitter_gen`, the torch.Generator its draws come from (the reference
+    draws them from torch's global generator, in its worker processes); without one the flag `draw_train_params` reports is
+    dropped, as before.  The draws are torchvision's (>= 0.8: one randperm(4), then the three factors) and the arithmetic is
+    Pillow's (`jitter_reference_u8` states it).
 """
+import ctypes
 import functools
 import glob
+import math
 import os
 
 import numpy as np
 import torch
 from PIL import Image
 
-from .. import ops
+from .. import _lib, ops
 
 PRECISION_BITS = 22        # Pillow's 8-bit resize: coefficients in 2.22 fixed point (Resample.c)
 PARAM_FIELDS = ("x0", "y0", "hflip", "vflip", "resize", "top", "left", "height", "width")
@@ -99,6 +106,97 @@ def draw_train_params(rng, H, W, crop):
     return [x0, y0, hf, vf, rs, top, left, bh, bw], jitter
 
 
+def draw_jitter_params(gen=None):
+    """One ColorJitter(brightness=[0.8, 1.2], contrast=[0.8, 1.2], saturation=[0.8, 1.2]) call's draws (train.py:139;
+    torchvision >= 0.8, ColorJitter.get_params), from the torch.Generator `gen` or, as the reference does, from torch's global
+    one: fn_idx = randperm(4), then the brightness, contrast and saturation factors, each float(empty(1).uniform_(0.8, 1.2)).
+    Hue is None: it draws nothing.  Returns (order, (b, c, s)): the order as drawn, a permutation of 0 .. 3 (0 brightness,
+    1 contrast, 2 saturation, 3 hue = nothing), and the factors, float32 values."""
+    order = torch.randperm(4, generator=gen).tolist()
+    factors = tuple(float(torch.empty(1).uniform_(0.8, 1.2, generator=gen)) for _ in range(3))
+    return order, factors
+
+
+def _luma(img):
+    """PIL's convert("L") of [..., 3] uint8 -> int64"""
+    c = img.astype(np.int64)
+    return (c[..., 0] * 19595 + c[..., 1] * 38470 + c[..., 2] * 7471 + 0x8000) >> 16
+
+
+def _blend_u8(d, i, factor):
+    """PIL's Image.blend(degenerate, image, factor) on uint8 arrays (Blend.c): per byte t = (float)d + alpha * (float)(i - d)
+    with alpha = (float)factor -- the product is rounded to float32, then the sum (numpy does not fuse them); for 0 <= alpha <= 1
+    the byte is (int)t, otherwise t is clipped to 0 .. 255 first."""
+    alpha = np.float32(factor)
+    d = np.broadcast_to(d, i.shape).astype(np.int32)
+    prod = alpha * (i.astype(np.int32) - d).astype(np.float32)
+    t = d.astype(np.float32) + prod
+    assert prod.dtype == np.float32 and t.dtype == np.float32
+    if not 0 <= alpha <= 1:
+        t = np.clip(t, np.float32(0), np.float32(255))
+    return t.astype(np.int32).astype(np.uint8)
+
+
+def jitter_reference_u8(img_u8, order, factors):
+    """What ColorJitter computes on an [h, w, 3] uint8 RGB image with PIL: the operations of `order` (0 brightness, 1 contrast,
+    2 saturation, 3 hue = skipped; any sequence of them) in turn, each ImageEnhance.X(img).enhance(f) = Image.blend(degenerate,
+    img, f) with f = factors[op].  The degenerate image is 0 (Brightness), L of each pixel on all three channels (Color, L =
+    (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16) or, for Contrast, int(mean + 0.5) of L over the whole image AS IT
+    STANDS when contrast is applied: with the exact sum s over n pixels, (2 s + n) // (2 n).  Byte for byte PIL on all 24
+    orders (tests/test_xbd_jitter_cpu.py); the kernel's statement of the arithmetic (csrc/augment_xbd.hip)."""
+    img = np.ascontiguousarray(img_u8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("jitter_reference_u8: an [h, w, 3] uint8 image, got %s %s" % (img.shape, img.dtype))
+    for op in order:
+        if op == 0:
+            img = _blend_u8(np.uint8(0), img, factors[0])
+        elif op == 1:
+            lum = _luma(img)
+            s, n = int(lum.sum()), lum.size
+            img = _blend_u8(np.uint8((2 * s + n) // (2 * n)), img, factors[1])
+        elif op == 2:
+            img = _blend_u8(_luma(img)[..., None].astype(np.uint8), img, factors[2])
+        elif op != 3:
+            raise ValueError("jitter_reference_u8: operation %r is none of 0 .. 3" % (op,))
+    return img
+
+
+JITTER_WORDS = 8           # int32 words of a row of dh_xbd_augment_jitter_u8's table
+
+
+def jitter_table(jitter):
+    """[n, 2, 8] int32 numpy table for dh_xbd_augment_jitter_u8 from one entry per sample, None or (pre, post) with each a
+    draw_jitter_params result: row = (1, the three operations in applied order -- the drawn order without hue --, the float32
+    bits of the three factors, 0); rows of samples without jitter stay 0.  None when every entry is None.  ValueError for an
+    entry that is no pair, an order that is no permutation of 0 .. 3 or a factor that is not finite."""
+    if all(j is None for j in jitter):
+        return None
+    table = np.zeros((len(jitter), 2, JITTER_WORDS), dtype=np.int32)
+    for n, entry in enumerate(jitter):
+        if entry is None:
+            continue
+        if len(entry) != 2:
+            raise ValueError("jitter[%d]: None or a (pre, post) pair of draw_jitter_params results" % n)
+        for im, (order, factors) in enumerate(entry):
+            order = [int(o) for o in order]
+            if sorted(order) != [0, 1, 2, 3]:
+                raise ValueError("jitter[%d]: order %r is not a permutation of 0 .. 3" % (n, order))
+            with np.errstate(over='ignore'):                 # a factor beyond float32 becomes inf and is refused below
+                f = np.asarray([float(x) for x in factors], dtype=np.float32)
+            if f.shape != (3,) or not all(math.isfinite(float(x)) for x in factors) or not np.isfinite(f).all():
+                raise ValueError("jitter[%d]: factors %r are not three finite numbers" % (n, tuple(factors)))
+            table[n, im, 0] = 1
+            table[n, im, 1:4] = [o for o in order if o != 3]
+            table[n, im, 4:7] = f.view(np.int32)
+    return table
+
+
+def jitter_workspace_bytes(n, crop):
+    """bytes of dh_xbd_augment_jitter_u8's workspace for n samples of crop x crop: the device copy of the table, then one
+    partial sum of L per tile and image"""
+    return n * 2 * (JITTER_WORDS + _lib.lib().dh_xbd_augment_jitter_tiles(crop)) * 4
+
+
 def check_params(params, H, W, crop):
     """[n, 9] int32 tensor of parameter rows; ValueError for a crop window outside the image, a flag that is not 0 / 1 or a
     resize box that is empty or leaves the crop (the kernel trusts the rows)"""
@@ -141,6 +239,7 @@ class GpuXbdPipeline:
         self.pre_mask, self.post_label = pre_mask_u8.contiguous(), post_label_u8.contiguous()
         self.files = list(files) if files is not None else [str(i) for i in range(pre_u8.shape[0])]
         self._zero_lbl = None
+        self._jitter_ws = None
 
     @classmethod
     def from_image_dir(cls, images_dir, device='cuda:0', files=None):
@@ -172,15 +271,27 @@ class GpuXbdPipeline:
     def __len__(self):
         return self.pre.shape[0]
 
-    def make_batch(self, indices, crop, params=None, train=True):
+    def make_batch(self, indices, crop, params=None, train=True, jitter=None):
         """indices: source samples of the batch; params: one row per sample in PARAM_FIELDS order (draw_train_params), or None
         for the crop at the origin without augmentation.  train=False builds ValData's masks (msk[0] from the pre mask,
         lbl_msk = label - 1 on the buildings); the reference validates whole images, i.e. crop == H == W and params=None.
         Returns {'img': fp32 [n, 6, crop, crop], 'msk': uint8 [n, 5, crop, crop], 'lbl_msk': uint8 [n, crop, crop], 'fn'}.
         `lbl_msk` of a training batch is all zeros (module docstring) and is ONE tensor shared by every training batch of
         that shape: read it, never write to it in place.
-        ValueError for a crop larger than the image, a window outside it or a resize box that leaves the crop."""
+        jitter: one entry per sample, None or the pair (pre, post) of draw_jitter_params results applied to the sample's two
+        images (ColorJitter, train.py:139; training batches only).  None, or every entry None, is dh_xbd_augment_u8 exactly
+        as without the argument; otherwise one call of dh_xbd_augment_jitter_u8.
+        ValueError for a crop larger than the image, a window outside it, a resize box that leaves the crop, jitter in a
+        validation batch, jitter rows that do not match the samples, an order that is no permutation, a factor that is not
+        finite."""
         n = len(indices)
+        table = None
+        if jitter is not None:
+            if not train:
+                raise ValueError("jitter: ColorJitter belongs to the training augmentation (train=False)")
+            if len(jitter) != n:
+                raise ValueError("jitter: %d entries for %d samples" % (len(jitter), n))
+            table = jitter_table(jitter)
         _, H, W, _ = self.pre.shape
         if params is None:
             params = [[0, 0, 0, 0, 0, 0, 0, crop, crop]] * n
@@ -202,17 +313,30 @@ class GpuXbdPipeline:
             lbl = self._zero_lbl
         else:
             lbl = torch.empty(n, crop, crop, dtype=torch.uint8, device=dev)
-        ops._call("dh_xbd_augment_u8", ops.P(self.pre), ops.P(self.post), ops.P(None if train else self.pre_mask),
-                  ops.P(self.post_label), ops.P(idx), ops.P(p), ops.P(coef), n, H, W, crop, 0 if train else 1, ops.P(img),
-                  ops.P(msk), ops.P(None if train else lbl), ops.S())
+        if table is None:
+            ops._call("dh_xbd_augment_u8", ops.P(self.pre), ops.P(self.post), ops.P(None if train else self.pre_mask),
+                      ops.P(self.post_label), ops.P(idx), ops.P(p), ops.P(coef), n, H, W, crop, 0 if train else 1, ops.P(img),
+                      ops.P(msk), ops.P(None if train else lbl), ops.S())
+        else:
+            need = jitter_workspace_bytes(n, crop)
+            if self._jitter_ws is None or self._jitter_ws.numel() < need:
+                self._jitter_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ws = self._jitter_ws
+            # the table is host memory: the entry checks it and copies it into the workspace before it returns
+            ops._call("dh_xbd_augment_jitter_u8", ops.P(self.pre), ops.P(self.post), ops.P(None), ops.P(self.post_label),
+                      ops.P(idx), ops.P(p), ops.P(coef), ctypes.c_void_p(table.ctypes.data), n, H, W, crop, 0, ops.P(img),
+                      ops.P(msk), ops.P(None), ops.P(ws), ws.numel(), ops.S())
         return {'img': img, 'msk': msk, 'lbl_msk': lbl, 'fn': [self.files[int(i)] for i in indices]}
 
-    def batches(self, batch_size, crop, train=True, rng=None):
+    def batches(self, batch_size, crop, train=True, rng=None, jitter_gen=None):
         """one epoch.  train: `rng` (a random.Random) shuffles the samples, then every sample draws its parameters with
         draw_train_params, in batch order (the reference's DataLoader shuffles with torch's generator and draws in its worker
         processes: the order of the samples is this loader's own, a sample's draws are the reference's).  Otherwise the
         samples in order with ValData's masks, as ValData takes them: whole images, so `crop` must be the (square) image
-        size -- ValueError otherwise; a validation crop is make_batch(..., params, train=False)."""
+        size -- ValueError otherwise; a validation crop is make_batch(..., params, train=False).
+        jitter_gen: a torch.Generator; every training sample whose draw_train_params flag is set then draws its ColorJitter
+        parameters from it (draw_jitter_params, pre then post, in sample order) and gets them applied.  None: no ColorJitter
+        and no draw from any torch generator."""
         _, H, W, _ = self.pre.shape
         if not train and not crop == H == W:
             raise ValueError("a validation epoch takes whole images: crop %d is not the %dx%d image" % (crop, H, W))
@@ -223,5 +347,13 @@ class GpuXbdPipeline:
             rng.shuffle(order)
         for s in range(0, len(order), batch_size):
             ind = order[s:s + batch_size]
-            params = [draw_train_params(rng, H, W, crop)[0] for _ in ind] if train else None
-            yield self.make_batch(ind, crop, params, train)
+            if not train:
+                yield self.make_batch(ind, crop, None, train)
+                continue
+            params, jitter = [], []
+            for _ in ind:
+                row, flag = draw_train_params(rng, H, W, crop)
+                params.append(row)
+                jitter.append((draw_jitter_params(jitter_gen), draw_jitter_params(jitter_gen))
+                              if flag and jitter_gen is not None else None)
+            yield self.make_batch(ind, crop, params, train, jitter if jitter_gen is not None else None)

@@ -355,6 +355,23 @@ int dh_augment_pairs_blur_u8(const unsigned char* a, const unsigned char* b, con
 int dh_xbd_augment_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* pre_mask,
                       const unsigned char* post_label, const int* idx, const int* params, const int* coef, int N, int H, int W,
                       int S, int mode, float* out_img, unsigned char* out_msk, unsigned char* out_lbl, void* stream);
+/* The same batch with the reference's ColorJitter(brightness, contrast, saturation) on the pre and post images of the samples
+ * that draw it (train.py:138-139), byte-exact against PIL's ImageEnhance chain, after the resize and before preprocess_inputs;
+ * masks and labels are not touched.  jitter_host [N][2][8] int32 in HOST memory (the entry checks it, then copies it into the
+ * workspace on `stream`; it is read before the call returns): row (n, image) = {enabled 0 / 1, the three operations in applied
+ * order (0 brightness, 1 contrast, 2 saturation, each once), the float32 bits of the brightness, contrast and saturation
+ * factors, 0}; image 0 is pre, 1 is post.  An operation is Image.blend(degenerate, image, factor) per byte, (float)d + factor *
+ * (float)(i - d) in two float32 roundings (not fused), clipped to 0 .. 255 and truncated; d = 0 (brightness), L of the pixel
+ * (saturation) or int(mean + 0.5) of L over the whole S x S image as it stands when contrast is applied.  That mean takes a launch
+ * of its own before the apply launch (exact integer partial sums per tile, in the workspace; none when no row is enabled).
+ * workspace: device memory, 4-byte aligned, N * 2 * (8 + dh_xbd_augment_jitter_tiles(S)) * 4 bytes (tiles: the workgroups of an
+ * S x S image; 0 for an S the entry refuses).  S <= 4096 (32-bit sums), 2 N <= 65535.  A sample whose rows are both disabled gets
+ * dh_xbd_augment_u8's bytes. */
+int dh_xbd_augment_jitter_tiles(int S);
+int dh_xbd_augment_jitter_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* pre_mask,
+                             const unsigned char* post_label, const int* idx, const int* params, const int* coef,
+                             const int* jitter_host, int N, int H, int W, int S, int mode, float* out_img, unsigned char* out_msk,
+                             unsigned char* out_lbl, void* workspace, long workspace_bytes, void* stream);
 int dh_nchw_to_nhwc(int dtype, const float* src, void* dst, int N, int C, long HW, int CP, void* stream);
 /* data gradient of the class head (3x3 / s1 / p1, 32 -> n_class <= 8 channels; help_funcs.py:13-14, networks.py:1247):
  * dy [N][H][W][CP] (CP = 8 bf16 / 4 or 8 fp32 channels per pixel, the first NC real), w_oihw [NC][32][3][3] fp32,

@@ -12,8 +12,13 @@ the same size, in three variants -- no sample resized, every sample resized with
 (top = left = 100: the worst case, every byte goes through both passes with real coefficients), and val mode.
 
     python tools/loader_rate.py --xbd --batch 4 --size 1024 --sources 8
+
+--jitter FRACTION adds a fourth variant to --xbd: the plain rows with ColorJitter (dh_xbd_augment_jitter_u8) on that fraction of
+the samples, spread evenly over the 50 batches of a measurement (the reference jitters 9 %: --jitter 0.09; 1 jitters every
+sample, 0 none).  A batch without a jittered sample goes through dh_xbd_augment_u8, as it does in the loader.
 """
 import argparse
+import ctypes
 import os
 import statistics
 import sys
@@ -78,6 +83,38 @@ def main_xbd(args):
     for k in rows:
         variants["make_batch " + k] = lambda k=k: pipe.make_batch(ind, sz, rows[k], train=k != "val")
         variants["kernel " + k] = lambda k=k: kernel(k)
+    if args.jitter is not None:
+        from dahitra_amd.datasets.xbd_pipeline import draw_jitter_params, jitter_table, jitter_workspace_bytes
+        if not 0 <= args.jitter <= 1:
+            raise SystemExit("loader_rate: --jitter takes a fraction in [0, 1]")
+        gj = torch.Generator().manual_seed(2)
+        # sample j of the REPS batches is jittered where the running count j * fraction steps: evenly spread, exact in total
+        flag = [int((j + 1) * args.jitter + 1e-9) > int(j * args.jitter + 1e-9) for j in range(n * REPS)]
+        lists = [[(draw_jitter_params(gj), draw_jitter_params(gj)) if flag[b * n + k] else None for k in range(n)]
+                 for b in range(REPS)]
+        tabs = [jitter_table(l) for l in lists]
+        need = jitter_workspace_bytes(n, sz)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        calls = {"make_batch": 0, "kernel": 0}
+
+        def make_batch_jitter():
+            b = calls["make_batch"] % REPS
+            calls["make_batch"] += 1
+            pipe.make_batch(ind, sz, rows["plain"], jitter=lists[b])
+
+        def kernel_jitter():
+            b = calls["kernel"] % REPS
+            calls["kernel"] += 1
+            if tabs[b] is None:
+                return kernel("plain")
+            p, c = tables["plain"]
+            ops._call("dh_xbd_augment_jitter_u8", ops.P(pre), ops.P(post), ops.P(None), ops.P(label), ops.P(idx), ops.P(p), ops.P(c),
+                      ctypes.c_void_p(tabs[b].ctypes.data), n, sz, sz, sz, 0, ops.P(img), ops.P(msk), ops.P(None), ops.P(ws), need,
+                      ops.S())
+
+        variants["make_batch jitter"], variants["kernel jitter"] = make_batch_jitter, kernel_jitter
+        print("jitter: %d of the %d samples of %d batches, %d batches with one" % (sum(flag), n * REPS, REPS,
+                                                                                  sum(t is not None for t in tabs)))
     times = {k: [] for k in variants}
     for _ in range(args.rounds):
         for k, fn in variants.items():
@@ -101,6 +138,8 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--sources", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--jitter", type=float, default=None, metavar="FRACTION",
+                    help="with --xbd: also measure ColorJitter on this fraction of the samples (the reference: 0.09)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("loader_rate: needs the GPU (no rate is reported without one)")
