@@ -177,19 +177,29 @@ __global__ void argmax_nchw_kernel(const float* __restrict__ logits, long long* 
     mask[i] = arg;
 }
 
+// One element of torch.optim.AdamW's update, shared by the eager and the HIP-graph form so that both return the same bits.  Left
+// to itself the compiler contracts a * b + c into fused multiply-adds differently in the two kernels (fma(grad_scale, g, -m) and
+// an unfused second moment in one, the opposite in the other), and the moments differ in the last bit.  Contraction is therefore
+// off here, and the two fused operations are written out: the sequence is the one the graph form has always compiled to.
+__device__ __forceinline__ void adamw_update(float& w, float& m, float& v, float g, float lr, float beta1, float beta2, float eps,
+                                             float wd, float bc1, float bc2_sqrt, float grad_scale) {
+#pragma clang fp contract(off)
+    const float gr = g * grad_scale;
+    w *= fmaf(-lr, wd, 1.f);
+    m = m + (1.f - beta1) * (gr - m);
+    v = fmaf(gr, (1.f - beta2) * gr, beta2 * v);
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    w -= (lr / bc1) * (m / denom);
+}
+
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, long n, float lr, float beta1, float beta2, float eps,
                              float wd, float bc1, float bc2_sqrt, float grad_scale) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gr = g[i] * grad_scale;
-        float w = p[i];
-        w *= 1.f - lr * wd;
-        const float mm = m[i] + (1.f - beta1) * (gr - m[i]);
-        const float vv = beta2 * v[i] + (1.f - beta2) * gr * gr;
+        float w = p[i], mm = m[i], vv = v[i];
+        adamw_update(w, mm, vv, g[i], lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale);
         m[i] = mm;
         v[i] = vv;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        w -= (lr / bc1) * (mm / denom);
         p[i] = w;
     }
 }
@@ -372,14 +382,10 @@ __global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict_
     const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], wd = hyper[4], gs = hyper[5];
     const float bc1 = hyper[6], bc2_sqrt = hyper[7];
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gr = g[i] * gs;
-        float w = p[i];
-        w *= 1.f - lr * wd;
-        const float mm = m[i] + (1.f - beta1) * (gr - m[i]);
-        const float vv = beta2 * v[i] + (1.f - beta2) * gr * gr;
+        float w = p[i], mm = m[i], vv = v[i];
+        adamw_update(w, mm, vv, g[i], lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, gs);
         m[i] = mm;
         v[i] = vv;
-        w -= (lr / bc1) * (mm / (sqrtf(vv) / bc2_sqrt + eps));
         p[i] = w;
     }
 }
