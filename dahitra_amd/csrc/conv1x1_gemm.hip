@@ -263,49 +263,57 @@ __global__ __launch_bounds__(2 * BM, 256 / BM) void conv1x1_gemm_kernel(ConvArgs
 
 
 template <int BN, int BM = GBM, bool XDEEP = false>
-int launch_gemm(const ConvArgs& a, hipStream_t st) {
-    constexpr int GBM = BM;
-    constexpr int ROWS = BN + GBM;
-    const size_t staging = XDEEP ? (size_t)(2 * BN + 3 * GBM) * 128 : (size_t)2 * ROWS * 128;
-    const size_t otile = (size_t)(BM / 32) * 2 * BN * 4 + (size_t)GBM * (BN * 2 + 16);
-    const size_t lds = staging > otile ? staging : otile;
+int launch_gemm(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     auto kern = conv1x1_gemm_kernel<BN, BM, XDEEP>;
     static bool attr_done = false;
-    if (lds > 64 * 1024 && !attr_done) {
+    if (p.lds > 64 * 1024 && !attr_done) {
         attr_done = true;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds) != hipSuccess) {
             (void)hipGetLastError();
-            DH_FAIL("conv1x1_gemm: cannot raise dynamic LDS to %zu", lds);
+            DH_FAIL("conv1x1_gemm: cannot raise dynamic LDS to %zu", (size_t)p.lds);
         }
     }
-    const long M = (long)a.N * a.OH * a.OW;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((M / GBM) * (a.Cout / BN))), dim3(2 * BM), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid_x), dim3(p.threads), p.lds, st, a);
     DH_CHECK_LAUNCH("conv1x1_gemm");
     return 0;
 }
 
 }  // namespace
 
-// the shapes this kernel serves (everything else stays on the direct kernel); bf16 only
-bool dh_conv1x1_gemm_eligible(const ConvArgs& a, int ks, int stride, int dtype) {
+// the shapes this kernel serves (everything else stays on the direct kernel; bf16 only), and for those the tile and the launch
+bool dh_conv1x1_gemm_plan(const ConvArgs& a, int ks, int stride, int dtype, ConvPlan& p) {
     static const bool off = getenv("DAHITRA_NO_GEMM1X1") != nullptr;
     static const bool no_s2 = getenv("DAHITRA_GEMM1X1_NO_S2") != nullptr;       // A/B switch: stride-2 layers stay on the direct kernel
+    static const bool small = getenv("DAHITRA_GEMM1X1_SMALL") != nullptr;       // A/B switch: 128-pixel tiles only
+    static const bool shallow = getenv("DAHITRA_GEMM1X1_SHALLOW") != nullptr;   // A/B switch: activation two stages deep as the weights
     const bool geo = stride == 1 ? (a.H == a.OH && a.W == a.OW)
                                  : (stride == 2 && !no_s2 && a.OH == (a.H + 1) / 2 && a.OW == (a.W + 1) / 2 && a.in_npix == a.H * a.W);
-    return !off && dtype == DH_DTYPE_BF16 && ks == 1 && geo && a.pad == 0 && a.Cin >= 64 && a.Cin % GBK == 0 &&
-           a.Cout % 64 == 0 && a.CoutPad == a.Cout && a.OH % 8 == 0 && a.OW % 16 == 0 &&
-           !a.gate_y && !a.y2 && !a.in_scale && a.w_nstride == 0 && a.npix == a.OH * a.OW && a.act != DH_ACT_GELU &&
-           !(a.stats && (a.res || a.act != DH_ACT_NONE)) && ((long)a.N * a.OH * a.OW) % GBM == 0;
-}
-int dh_conv1x1_gemm_launch(const ConvArgs& a, hipStream_t st) {
-    static const bool small = getenv("DAHITRA_GEMM1X1_SMALL") != nullptr;       // A/B switch: 128-pixel tiles only
     const long M = (long)a.N * a.OH * a.OW;
+    // (whole 8x16 tiles: a 128-pixel half of a workgroup's tile is one stats_partial row of dh_conv2d_fwd_num_tiles)
+    if (off || dtype != DH_DTYPE_BF16 || ks != 1 || !geo || a.pad != 0 || a.Cin < 64 || a.Cin % GBK || a.Cout % 64 || a.CoutPad != a.Cout ||
+        a.OH % 8 || a.OW % 16 || a.gate_y || a.y2 || a.in_scale || a.w_nstride != 0 || a.npix != a.OH * a.OW || a.act == DH_ACT_GELU ||
+        (a.stats && (a.res || a.act != DH_ACT_NONE)) || M % GBM)
+        return false;
+    p.family = CONV_GEMM1X1;
+    p.BN = a.Cout % 128 == 0 ? 128 : 64;
+    p.BM = GBM;
     // 256-pixel tiles where they still give the chip at least two rounds of workgroups
-    static const bool shallow = getenv("DAHITRA_GEMM1X1_SHALLOW") != nullptr;   // A/B switch: activation two stages deep as the weights
     if (!small && M % 256 == 0 && a.Cout % 128 == 0 && (M / 256) * (a.Cout / (a.Cout % 256 == 0 ? 256 : 128)) >= 512) {
-        if (shallow) return a.Cout % 256 == 0 ? launch_gemm<256, 256>(a, st) : launch_gemm<128, 256>(a, st);
+        p.BM = 256;
+        p.BN = a.Cout % 256 == 0 ? 256 : 128;
         // (the three-deep activation ring: 222 -> 214 us on 1024 -> 256, neutral on the others, slower at 128 couts: 83 -> 86)
-        return a.Cout % 256 == 0 ? launch_gemm<256, 256, true>(a, st) : launch_gemm<128, 256>(a, st);
+        p.XDEEP = p.BN == 256 && !shallow;
     }
-    return a.Cout % 128 == 0 ? launch_gemm<128>(a, st) : launch_gemm<64>(a, st);
+    const size_t staging = p.XDEEP ? (size_t)(2 * p.BN + 3 * p.BM) * 128 : (size_t)2 * (p.BN + p.BM) * 128;
+    const size_t otile = (size_t)(p.BM / 32) * 2 * p.BN * 4 + (size_t)p.BM * (p.BN * 2 + 16);
+    p.lds = (int)(staging > otile ? staging : otile);
+    p.grid_x = (int)((M / p.BM) * (a.Cout / p.BN));
+    p.grid_y = 1;
+    p.threads = 2 * p.BM;
+    p.stats_rows = (int)(M / GBM);
+    return true;
+}
+int dh_conv1x1_gemm_launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    if (p.BM == 256) return p.XDEEP ? launch_gemm<256, 256, true>(a, p, st) : (p.BN == 256 ? launch_gemm<256, 256>(a, p, st) : launch_gemm<128, 256>(a, p, st));
+    return p.BN == 128 ? launch_gemm<128>(a, p, st) : launch_gemm<64>(a, p, st);
 }

@@ -26,7 +26,6 @@
 namespace {
 
 constexpr int TW = 16;                  // output tile: 16 pixels wide, 4*RW rows (RW rows per wavefront)
-constexpr int DH_CONV_NO_FIT = -2;      // a split-bf16 launch whose staging planes exceed the LDS: nothing was launched
 // LDS rows hold one 64-byte channel chunk.  ds_read_b128 is served in 16-lane groups
 // {0-3,12-15,20-27},{4-11,16-19,28-31},... (MI355X_MICROARCH.md), each needing 16 distinct 16-byte slots
 // mod 256 B.  Brute force over layouts: for consecutive rows (stride-1 pixels, weight rows) pitch 64 with
@@ -109,6 +108,22 @@ struct ConvArgs {
     // written or read.  H, W stay the FINE sizes.
     const void* up4_a;
     const void* up4_b;
+};
+
+// The whole host-side decision of one forward / data-gradient launch (conv_plan, conv_mfma.hip): made once per call from the
+// ConvArgs, then read by the launch functions, the shape queries and dh_conv2d_fwd_describe.  Each family's file fills it in its
+// one <family>_plan function and switches on it in its launch function.  All int, in the order dh_conv2d_fwd_describe documents.
+enum ConvFamily { CONV_TAP_BF16 = 0, CONV_TAP_F32, CONV_TAP_X3, CONV_TAP_X6, CONV_TAP_H3, CONV_GEMM1X1, CONV_WREG64, CONV_WREG128,
+                  CONV_WREG256, CONV_WREG32, CONV_WREG32_UP4 };
+struct ConvPlan {
+    int family;
+    int KS, STRIDE, NT, RW, DIL, PF, FAST, INBN, INUP4;        // conv_mfma_kernel's template arguments (tap families)
+    int BN, BM, XDEEP;                                           // conv1x1_gemm_kernel's
+    int NCH, D, PFD, WPS, WINBN, RES, RELU;                      // conv3x3_wreg*_kernel's (those the kernel has, 0 otherwise) ...
+    int J, ncb;                                                  // ... and the persistent grid: J workgroups per each of ncb channel blocks
+    int grid_x, grid_y, threads, lds;
+    int tilesX, tilesY, rw;                                      // = ConvArgs's
+    int stats_rows;                                              // rows of stats_partial the kernel indexes (dh_conv2d_fwd_num_tiles)
 };
 
 namespace {
@@ -763,113 +778,74 @@ static inline int pick_rw(int N, int OH, int OW, int Cin, int ks, int stride) {
     return 2;
 }
 
+// The cascade from the plan's run-time values to the template arguments.  Every rule is in tap_plan (conv_mfma.hip); the
+// if-constexpr guards only name which combinations are built, and a plan outside them is an error.
 template <typename T, int KS, int STRIDE, int NT, int RW, int DIL, bool PF, bool FAST, bool INBN = false, bool INUP4 = false>
-int launch_fast(const ConvArgs& a, hipStream_t st) {
-    constexpr int TH = 4 * RW;
-    constexpr int HH = (TH - 1) * STRIDE + (KS - 1) * DIL + 1, HWD = (TW - 1) * STRIDE + (KS - 1) * DIL + 1;
-    const size_t staging = Prec<T>::NPL * ((size_t)HH * HWD * HaloLayout<STRIDE>::PITCH + (size_t)KS * KS * NT * WPITCH) +
-                           (INBN ? (size_t)2 * a.Cin * sizeof(float) : 0) + (INUP4 ? (size_t)4 * 6 * 32 * sizeof(float) : 0);
-    const size_t otile = (size_t)4 * 2 * NT * 4 + (size_t)TH * TW * (NT * sizeof(T) + 16);     // epilogue: stats scratch + transposed tile
-    const size_t lds = staging > otile ? staging : otile;
+int launch_fast(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     auto kern = conv_mfma_kernel<T, KS, STRIDE, NT, RW, DIL, PF, FAST, INBN, INUP4>;
     static bool attr_done = false;      // once per instantiation (and never inside a graph capture)
-    if (lds > 64 * 1024 && !attr_done) {
+    if (p.lds > 64 * 1024 && !attr_done) {
         attr_done = true;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            DH_FAIL("conv_mfma: cannot raise dynamic LDS to %zu", lds);
+            DH_FAIL("conv_mfma: cannot raise dynamic LDS to %zu", (size_t)p.lds);
         }
     }
-    dim3 grid(a.N * a.tilesX * a.tilesY, a.CoutPad / NT);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(p.grid_x, p.grid_y), dim3(p.threads), p.lds, st, a);
     DH_CHECK_LAUNCH("conv_mfma");
     return 0;
 }
 
 template <typename T, int KS, int STRIDE, int NT, int RW, int DIL, bool PF>
-int launch_pf(const ConvArgs& a, hipStream_t st) {
-    // compact-epilogue instantiation: 16-byte output pieces, no gating / pre-activation copy / GELU
-    const bool fast = ((a.Cout % (16 / (int)sizeof(T))) == 0 || a.y_nchw) && !a.gate_y && !a.y2 && a.act != DH_ACT_GELU;
+int launch_pf(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     if constexpr (KS == 3 && STRIDE == 1 && DIL == 1) {        // BN-apply + ReLU on load: the 3x3 consumers of a BN layer
-        if (a.in_scale) {
-            if (fast) return launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, true, true>(a, st);
-            return launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, false, true>(a, st);
-        }
-    } else if (a.in_scale) {
-        DH_FAIL("conv_mfma: BatchNorm-on-load is built for 3x3 stride-1 dilation-1 convolutions (got %dx%d s%d d%d)", KS, KS, STRIDE, DIL);
+        if (p.INBN) return p.FAST ? launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, true, true>(a, p, st)
+                                  : launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, false, true>(a, p, st);
     }
     if constexpr (KS == 3 && STRIDE == 1 && DIL == 1 && NT == 32 && RW == 2 && !PF && sizeof(T) == 2) {
-        if (a.up4_a) {
-            if (!fast || a.in_scale) DH_FAIL("conv_mfma: the bilinear-x4-on-load form has the compact epilogue and no BatchNorm on load");
-            return launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, true, false, true>(a, st);
-        }
+        if (p.INUP4 && p.FAST && !p.INBN) return launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, true, false, true>(a, p, st);
     }
-    if (a.up4_a) DH_FAIL("conv_mfma: bilinear x4 on load is built for the bf16 3x3 / stride 1, 32 -> 32 channel convolution on 8-row tiles");
-    if (fast) return launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, true>(a, st);
-    return launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, false>(a, st);
+    if (p.INBN || p.INUP4) DH_FAIL("conv_mfma: no on-load form is built for this %dx%d s%d d%d launch", KS, KS, STRIDE, DIL);
+    return p.FAST ? launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, true>(a, p, st) : launch_fast<T, KS, STRIDE, NT, RW, DIL, PF, false>(a, p, st);
 }
 
 template <typename T, int KS, int STRIDE, int NT, int RW, int DIL>
-int launch_rw(const ConvArgs& a, hipStream_t st) {
-    constexpr int CK = Prec<T>::CK;
+int launch_rw(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     if constexpr (RW == 2 && KS == 3 && DIL == 1) {
-        // (split-bf16 forms run one workgroup per CU -- no second workgroup to cover a chunk's loads -- so a two-chunk layer
-        // prefetches its second chunk under the first one's MFMAs: +2.9 % on the bf16x3 step, same-box)
-        if (a.Cin <= 2 * CK && !(Prec<T>::NPL > 1 && a.Cin == 2 * CK)) return launch_pf<T, KS, STRIDE, NT, RW, DIL, false>(a, st);
+        if (!p.PF) return launch_pf<T, KS, STRIDE, NT, RW, DIL, false>(a, p, st);
     }
-    return launch_pf<T, KS, STRIDE, NT, RW, DIL, true>(a, st);
+    return launch_pf<T, KS, STRIDE, NT, RW, DIL, true>(a, p, st);
 }
 
 template <typename T, int KS, int STRIDE, int NT>
-int launch(const ConvArgs& a, hipStream_t st) {
+int launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     if constexpr (KS == 3 && STRIDE == 1) {
-        if (a.dil == 2) return a.rw == 4 ? launch_rw<T, KS, STRIDE, NT, 4, 2>(a, st) : launch_rw<T, KS, STRIDE, NT, 2, 2>(a, st);
-        if (a.rw == 4) return launch_rw<T, KS, STRIDE, NT, 4, 1>(a, st);
+        if (p.DIL == 2) return p.RW == 4 ? launch_rw<T, KS, STRIDE, NT, 4, 2>(a, p, st) : launch_rw<T, KS, STRIDE, NT, 2, 2>(a, p, st);
+        if (p.RW == 4) return launch_rw<T, KS, STRIDE, NT, 4, 1>(a, p, st);
     }
     if constexpr (KS == 2) {
-        if (a.rw == 4) return launch_rw<T, KS, STRIDE, NT, 4, 1>(a, st);
+        if (p.RW == 4) return launch_rw<T, KS, STRIDE, NT, 4, 1>(a, p, st);
     }
-    return launch_rw<T, KS, STRIDE, NT, 2, 1>(a, st);
+    return launch_rw<T, KS, STRIDE, NT, 2, 1>(a, p, st);
 }
 
 template <typename T, int KS, int STRIDE>
-int launch_nt(const ConvArgs& a, hipStream_t st) {
-    if constexpr (KS == 2) {      // the phase convolutions: forward = one cout block (32 or 64 channels) per phase
-        if (a.phase_mode == 1) return a.Cout == 128 ? launch<T, KS, STRIDE, 32>(a, st) : launch<T, KS, STRIDE, 64>(a, st);
-        return a.Cout % 64 ? launch<T, KS, STRIDE, 32>(a, st) : launch<T, KS, STRIDE, 64>(a, st);     // data gradient: Cout = the 3x3's Cin
-    }
-    if constexpr (Prec<T>::NPL > 1) {
-        // split-bf16 forms: NPL planes of halo + weights must fit the CU's 160 KB of LDS -- the widest output tile that does
-        // (e.g. three planes of a 16-row 3x3 tile: 32 channels; stride 2 with three planes: none -- DH_CONV_NO_FIT tells the
-        // caller to take the exact fp32 kernel for that launch)
-        const int rw = (KS == 3 && STRIDE == 1) || KS == 2 ? a.rw : 2, dil = (KS == 3 && STRIDE == 1) ? a.dil : 1;
-        const int hh = (4 * rw - 1) * STRIDE + (KS - 1) * dil + 1, hwd = (TW - 1) * STRIDE + (KS - 1) * dil + 1;
-        const size_t budget = 160 * 1024 - (a.in_scale ? (size_t)2 * a.Cin * sizeof(float) : 0);
-        auto fits = [&](int nt) {
-            return Prec<T>::NPL * ((size_t)hh * hwd * HaloLayout<STRIDE>::PITCH + (size_t)KS * KS * nt * WPITCH) <= budget;
-        };
-        if (a.CoutPad % 64 == 0 && fits(64)) return launch<T, KS, STRIDE, 64>(a, st);
-        if (a.CoutPad % 32 == 0 && fits(32)) return launch<T, KS, STRIDE, 32>(a, st);
-        // (16-wide tiles only for layers that ARE that narrow: the one 3x3 stride-2 layer, 64 -> 128 channels, fits three planes
-        // at 16 channels per workgroup and then takes 165 us where the exact fp32 kernel takes 97)
-        if (a.CoutPad % 32 != 0 && fits(16)) return launch<T, KS, STRIDE, 16>(a, st);
-        return DH_CONV_NO_FIT;
-    }
-    if (a.CoutPad % 64 == 0) return launch<T, KS, STRIDE, 64>(a, st);
-    if (a.CoutPad % 32 == 0) return launch<T, KS, STRIDE, 32>(a, st);
-    return launch<T, KS, STRIDE, 16>(a, st);
+int launch_nt(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    if (p.NT == 64) return launch<T, KS, STRIDE, 64>(a, p, st);
+    if (p.NT == 32) return launch<T, KS, STRIDE, 32>(a, p, st);
+    return launch<T, KS, STRIDE, 16>(a, p, st);
 }
 
 template <typename T>
-int launch_ks(const ConvArgs& a, int ks, int stride, hipStream_t st) {
-    if (ks == 3 && stride == 1) return launch_nt<T, 3, 1>(a, st);
-    if (ks == 3 && stride == 2) return launch_nt<T, 3, 2>(a, st);
-    if (ks == 1 && stride == 1) return launch_nt<T, 1, 1>(a, st);
-    if (ks == 1 && stride == 2) return launch_nt<T, 1, 2>(a, st);
-    if (ks == 4 && stride == 1) return launch_nt<T, 4, 1>(a, st);     // space-to-depth stem
-    if (ks == 2 && stride == 1 && a.phase_mode) return launch_nt<T, 2, 1>(a, st);      // phase convs of upsample-x2 + 3x3
+int launch_ks(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    const int ks = p.KS, stride = p.STRIDE;
+    if (ks == 3 && stride == 1) return launch_nt<T, 3, 1>(a, p, st);
+    if (ks == 3 && stride == 2) return launch_nt<T, 3, 2>(a, p, st);
+    if (ks == 1 && stride == 1) return launch_nt<T, 1, 1>(a, p, st);
+    if (ks == 1 && stride == 2) return launch_nt<T, 1, 2>(a, p, st);
+    if (ks == 4 && stride == 1) return launch_nt<T, 4, 1>(a, p, st);     // space-to-depth stem
+    if (ks == 2 && stride == 1) return launch_nt<T, 2, 1>(a, p, st);     // phase convs of upsample-x2 + 3x3
     DH_FAIL("conv_mfma: unsupported kernel %dx%d stride %d", ks, ks, stride);
 }
 

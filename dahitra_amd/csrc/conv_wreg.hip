@@ -460,46 +460,47 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_wreg_kernel(WrArgs a) {
     WR_TS(31);
 }
 
-template <int NSUB, int NCH, int D, int PFD, bool INBN, int WPS, bool RES, bool RELU>
-int wr_launch(const ConvArgs& c, hipStream_t st, int cus) {
-    constexpr int NCO = 64 * NSUB;
+// the kernel argument of a planned stream, and the 160 KB every kernel of this file may ask for (once per instantiation)
+static WrArgs wr_args(const ConvArgs& c, const ConvPlan& p) {
     WrArgs a;
     a.c = c;
-    a.ncb = c.Cout / NCO;
+    a.ncb = p.ncb;
+    a.J = p.J;
+    a.nunits = p.stats_rows;
     a.subt = c.rw == 4 ? 2 : 1;
     a.tilesX = c.OW / TW;
     a.unitsY = c.OH / (WR_TH * a.subt);
-    a.nunits = c.N * a.unitsY * a.tilesX;
-    int J = (cus * WPS / a.ncb) & ~7;                      // WPS workgroups per CU, a multiple of 8 per output-channel block
-    if (J > a.nunits) J = (a.nunits + 7) & ~7;
-    if (J < 8) J = 8;
-    a.J = J;
     a.wfrag = c.w_frag != nullptr;
     if (a.wfrag) a.c.w = c.w_frag;
-    const size_t lds = (size_t)D * WR_IMG + (size_t)WR_TH * TW * (NCO * 2 + 16) + (INBN ? (size_t)c.in_groups * 2 * c.Cin * 4 : 0);
-    auto kern = conv3x3_wreg_kernel<NSUB, NCH, D, PFD, INBN, WPS, RES, RELU>;
-    static bool attr_done = false;
+    return a;
+}
+template <typename K>
+int wr_issue(K kern, bool& attr_done, const char* name, const char* no_lds, const ConvArgs& c, const ConvPlan& p, hipStream_t st) {
     if (!attr_done) {
         attr_done = true;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
             (void)hipGetLastError();
-            DH_FAIL("conv_wreg: cannot raise dynamic LDS to 160 KB");
+            DH_FAIL("%s", no_lds);
         }
     }
-    hipLaunchKernelGGL(kern, dim3(a.ncb * J), dim3(256), lds, st, a);
-    DH_CHECK_LAUNCH("conv_wreg");
+    hipLaunchKernelGGL(kern, dim3(p.grid_x), dim3(p.threads), p.lds, st, wr_args(c, p));
+    DH_CHECK_LAUNCH(name);
     return 0;
 }
 
+template <int NSUB, int NCH, int D, int PFD, bool INBN, int WPS, bool RES, bool RELU>
+int wr_launch(const ConvArgs& c, const ConvPlan& p, hipStream_t st) {
+    static bool attr_done = false;
+    return wr_issue(conv3x3_wreg_kernel<NSUB, NCH, D, PFD, INBN, WPS, RES, RELU>, attr_done, "conv_wreg", "conv_wreg: cannot raise dynamic LDS to 160 KB", c, p, st);
+}
+
 template <int NSUB, int NCH, int D, int PFD, int WPS>
-int wr_launch_bn(const ConvArgs& c, hipStream_t st, int cus) {
-    // (BatchNorm on load comes with neither residual nor ReLU in any caller: dh_conv_wreg_eligible refuses the combination)
-    const bool relu = c.act == DH_ACT_RELU;
-    if (c.in_scale) return wr_launch<NSUB, NCH, D, PFD, true, WPS, false, false>(c, st, cus);
-    if (c.res) return relu ? wr_launch<NSUB, NCH, D, PFD, false, WPS, true, true>(c, st, cus)
-                           : wr_launch<NSUB, NCH, D, PFD, false, WPS, true, false>(c, st, cus);
-    return relu ? wr_launch<NSUB, NCH, D, PFD, false, WPS, false, true>(c, st, cus)
-                : wr_launch<NSUB, NCH, D, PFD, false, WPS, false, false>(c, st, cus);
+int wr_launch_bn(const ConvArgs& c, const ConvPlan& p, hipStream_t st) {
+    if (p.WINBN) return wr_launch<NSUB, NCH, D, PFD, true, WPS, false, false>(c, p, st);     // (never with residual or ReLU: the plan refuses)
+    if (p.RES) return p.RELU ? wr_launch<NSUB, NCH, D, PFD, false, WPS, true, true>(c, p, st)
+                             : wr_launch<NSUB, NCH, D, PFD, false, WPS, true, false>(c, p, st);
+    return p.RELU ? wr_launch<NSUB, NCH, D, PFD, false, WPS, false, true>(c, p, st)
+                  : wr_launch<NSUB, NCH, D, PFD, false, WPS, false, false>(c, p, st);
 }
 
 // ---- 32 -> 32 channels (classifier.0, the 32-channel convolutions of the UNet up path) ----------------------------------------
@@ -757,34 +758,10 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_wreg32_kernel(WrArgs a) {
 }
 
 template <bool RES, bool RELU>
-int wr32_launch(const ConvArgs& c, hipStream_t st, int cus) {
-    constexpr int WPS = 2;                                 // (57 KB of LDS per workgroup)
-    WrArgs a;
-    a.c = c;
-    a.ncb = 1;
-    a.subt = 1;
-    a.tilesX = c.OW / TW;
-    a.unitsY = c.OH / WR_TH;
-    a.nunits = c.N * a.unitsY * a.tilesX;
-    int J = (cus * WPS) & ~7;
-    if (J > a.nunits) J = (a.nunits + 7) & ~7;
-    if (J < 8) J = 8;
-    a.J = J;
-    a.wfrag = c.w_frag != nullptr;
-    if (a.wfrag) a.c.w = c.w_frag;
-    const size_t lds = (size_t)3 * WR_IMG + (size_t)2 * WR_TH * TW * (32 * 2 + 16) + 2 * 64 * 4;
-    auto kern = conv3x3_wreg32_kernel<RES, RELU, WPS>;
+int wr32_launch(const ConvArgs& c, const ConvPlan& p, hipStream_t st) {
     static bool attr_done = false;
-    if (!attr_done) {
-        attr_done = true;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            DH_FAIL("conv_wreg32: cannot raise dynamic LDS");
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(J), dim3(256), lds, st, a);
-    DH_CHECK_LAUNCH("conv_wreg32");
-    return 0;
+    // (57 KB of LDS: two workgroups per CU)
+    return wr_issue(conv3x3_wreg32_kernel<RES, RELU, 2>, attr_done, "conv_wreg32", "conv_wreg32: cannot raise dynamic LDS", c, p, st);
 }
 
 
@@ -1077,34 +1054,9 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_up4_wreg32_kernel(WrArgs a) 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int wr32_up4_launch(const ConvArgs& c, hipStream_t st, int cus) {
-    constexpr int WPS = 2;
-    WrArgs a;
-    a.c = c;
-    a.ncb = 1;
-    a.subt = 1;
-    a.tilesX = c.OW / TW;
-    a.unitsY = c.OH / WR_TH;
-    a.nunits = c.N * a.unitsY * a.tilesX;
-    int J = (cus * WPS) & ~7;
-    if (J > a.nunits) J = (a.nunits + 7) & ~7;
-    if (J < 8) J = 8;
-    a.J = J;
-    a.wfrag = c.w_frag != nullptr;
-    if (a.wfrag) a.c.w = c.w_frag;
-    const size_t lds = (size_t)3 * WR_IMG + (size_t)2 * WR_TH * TW * (32 * 2 + 16) + 2 * 64 * 4 + 2 * (24 * 32 * 4);
-    auto kern = conv3x3_up4_wreg32_kernel<WPS>;
+int wr32_up4_launch(const ConvArgs& c, const ConvPlan& p, hipStream_t st) {
     static bool attr_done = false;
-    if (!attr_done) {
-        attr_done = true;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            DH_FAIL("conv_wreg32 (up4): cannot raise dynamic LDS");
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(J), dim3(256), lds, st, a);
-    DH_CHECK_LAUNCH("conv_wreg32_up4");
-    return 0;
+    return wr_issue(conv3x3_up4_wreg32_kernel<2>, attr_done, "conv_wreg32_up4", "conv_wreg32 (up4): cannot raise dynamic LDS", c, p, st);
 }
 
 int g_wreg_mode = -1;      // dh_conv_wreg_mode: -1 = where it is the faster kernel, 0 = never, 1 = wherever it can run
@@ -1112,38 +1064,74 @@ int g_wreg_mode = -1;      // dh_conv_wreg_mode: -1 = where it is the faster ker
 
 }  // namespace
 
-// the launches this kernel serves: what conv_mfma_kernel<bf16, 3, 1, 64, *, 1, *, FAST = true, *> serves at 64 / 128 / 256
-// input channels, whole 8x16 tiles, and enough tiles per persistent workgroup to amortise loading the weights
-bool dh_conv_wreg_eligible(const ConvArgs& a, int ks, int stride, int dtype) {
+// The launches the kernels of this file serve, and for those the kernel, its template arguments and the persistent grid on
+// `cus` compute units.
+//  - 64 / 128 / 256 input channels: what conv_mfma_kernel<bf16, 3, 1, 64, *, 1, *, FAST = true, *> serves, whole 8x16 tiles, and
+//    enough tiles per persistent workgroup to amortise loading the weights;
+//  - 32 -> 32 channels: no BatchNorm on load, whole 8x16 tiles, 8-row statistics units, enough tiles for its 768 streams;
+//  - classifier.0 on upsample4(|a - b|) from the coarse maps (ConvArgs::up4_a / up4_b): that 32 -> 32 stream with the
+//    interpolation in LDS, without residual or activation.  NOT the default route (DAHITRA_UP4_WREG=1, or dh_conv_wreg_mode(1)):
+//    measured at 32 x 256 x 256 (tools/up4_bench.py, profiles/r06a_up4_fused.txt) it takes 116 us against 29.5 + 83.5 for
+//    dh_absdiff_upsample4_fwd + the plain stream -- the interpolation more than doubles the stream's vector instructions
+//    (rocprofv3 SQ_INSTS_VALU 4.15e7 against 1.82e7, SQ_INSTS_LDS 3.6e6 against 1.7e6) and two waves per SIMD are then bound by
+//    VALU issue (~630 instructions per wave and tile next to 36 MFMAs), where the plain stream is bound by the 268 MB it moves.
+bool dh_conv_wreg_plan(const ConvArgs& a, int ks, int stride, int dtype, int cus, ConvPlan& p) {
     static const bool off = getenv("DAHITRA_NO_WREG") != nullptr;
+    static const bool up4_on = getenv("DAHITRA_UP4_WREG") != nullptr && atoi(getenv("DAHITRA_UP4_WREG")) == 1;
     if (off || g_wreg_mode == 0 || dtype != DH_DTYPE_BF16 || ks != 3 || stride != 1 || a.dil != 1 || a.pad != 1) return false;
-    if (a.Cin == 32) {
-        // the 32 -> 32 kernel: no BatchNorm on load, whole 8x16 tiles, 8-row statistics units, enough tiles for its 768 streams
-        if (a.x_split || a.y_split) return false;
-        if (a.Cout != 32 || a.CoutPad != 32 || a.in_scale || a.rw != 2 || a.phase_mode || a.gate_y || a.y2 || a.y_nchw || a.w_nstride ||
-            a.up4_partial || a.act == DH_ACT_GELU)
+    const long tiles = (long)a.N * (a.OH / 8) * (a.OW / 16);
+    //                NCH D PFD WPS
+    int shape[4] = {0, 0, 0, 2};
+    if (a.up4_a || a.Cin == 32) {
+        if (a.Cin != 32 || a.Cout != 32 || a.CoutPad != 32 || a.in_scale || a.OH != a.H || a.OW != a.W || a.OH % 8 || a.OW % 16) return false;
+        if (a.up4_a) {
+            if (!(up4_on || g_wreg_mode == 1) || !a.up4_b || a.res || a.act != DH_ACT_NONE) return false;
+        } else if (a.x_split || a.y_split || a.rw != 2 || a.phase_mode || a.gate_y || a.y2 || a.y_nchw || a.w_nstride || a.up4_partial ||
+                   a.act == DH_ACT_GELU || a.npix != a.OH * a.OW || a.in_npix != a.H * a.W) {
             return false;
-        if (a.npix != a.OH * a.OW || a.in_npix != a.H * a.W || a.OH != a.H || a.OW != a.W || a.OH % 8 || a.OW % 16) return false;
-        return (long)a.N * (a.OH / 8) * (a.OW / 16) >= (g_wreg_mode == 1 ? 16 : 4 * 512);
+        }
+        if (tiles < (g_wreg_mode == 1 ? 16 : 4 * 512)) return false;
+        p.family = a.up4_a ? CONV_WREG32_UP4 : CONV_WREG32;
+        p.lds = 3 * WR_IMG + 2 * WR_TH * TW * (32 * 2 + 16) + 2 * 64 * 4 + (a.up4_a ? 2 * (24 * 32 * 4) : 0);
+    } else {
+        if (a.Cin != 64 && a.Cin != 128 && a.Cin != 256) return false;
+        if (a.Cout % 64 || a.CoutPad != a.Cout || a.phase_mode || a.gate_y || a.y2 || a.y_nchw || a.w_nstride) return false;
+        if (a.act == DH_ACT_GELU || a.npix != a.OH * a.OW || a.in_npix != a.H * a.W || a.OH != a.H || a.OW != a.W) return false;
+        if (a.OH % (a.rw == 4 ? 16 : 8) || a.OW % 16) return false;
+        if (a.in_scale && (a.in_groups > 4 || a.res || a.act == DH_ACT_RELU)) return false;
+        if ((a.x_split && (a.Cin % 128 || a.in_scale)) || (a.y_split && (a.Cout % 128 || a.res))) return false;   // halves = whole chunks / blocks
+        if (g_wreg_mode != 1) {
+            // measured (tools/wreg_bench.py, 64 images, gpurun_out/wreg_bench_{9,10}*.txt): the shapes on which this kernel is the
+            // faster one -- the 64-channel layers (x1.16 with BatchNorm on load, x1.26 - 1.30 without) and, given the
+            // fragment-order weights, 128 / 256 input channels without BatchNorm on load (x1.04 - 1.13 / x1.07 - 1.11; with it
+            // x0.86 - 0.90: one wave per SIMD cannot hide the in-LDS transform).  DESIGN.md section 6c.
+            if (!(a.Cin == 64 || (a.w_frag && !a.in_scale))) return false;
+        }
+        // a persistent workgroup must see enough tiles to amortise loading its weights (74 KB at 64 input channels, two workgroups
+        // per CU; 147 / 295 KB at 128 / 256, one per CU): measured down to 4 tiles per workgroup (256 -> 128 at 64 images: x1.08)
+        const long work = tiles * (a.Cout / 64);
+        if (work < (g_wreg_mode == 1 ? 2 * 256 : (a.Cin == 64 ? 4 * 512 : 4 * 256))) return false;
+        // 64 input channels: 72 weight registers, two workgroups per CU; 256: 288, one wave per SIMD.  128: also measured and dropped: 32
+        // output channels per wave (288 registers + 64 accumulators: 60 spills, x0.7), two workgroups per CU at 144 registers (31 spills,
+        // x0.77), deeper rings (D = 5 / 8: no change, cache-cold inputs included).
+        p.family = a.Cin == 64 ? CONV_WREG64 : (a.Cin == 128 ? CONV_WREG128 : CONV_WREG256);
+        shape[0] = a.Cin / 32; shape[1] = 4; shape[2] = a.Cin == 64 ? 3 : 4; shape[3] = a.Cin == 64 ? 2 : 1;
+        p.WINBN = a.in_scale != nullptr;
+        p.lds = shape[1] * WR_IMG + WR_TH * TW * (64 * 2 + 16) + (p.WINBN ? a.in_groups * 2 * a.Cin * 4 : 0);
     }
-    if (a.Cin != 64 && a.Cin != 128 && a.Cin != 256) return false;
-    if (a.Cout % 64 || a.CoutPad != a.Cout || a.phase_mode || a.gate_y || a.y2 || a.y_nchw || a.w_nstride) return false;
-    if (a.act == DH_ACT_GELU || a.npix != a.OH * a.OW || a.in_npix != a.H * a.W || a.OH != a.H || a.OW != a.W) return false;
-    if (a.OH % (a.rw == 4 ? 16 : 8) || a.OW % 16) return false;
-    if (a.in_scale && (a.in_groups > 4 || a.res || a.act == DH_ACT_RELU)) return false;
-    if ((a.x_split && (a.Cin % 128 || a.in_scale)) || (a.y_split && (a.Cout % 128 || a.res))) return false;   // halves = whole chunks / blocks
-    if (g_wreg_mode != 1) {
-        // measured (tools/wreg_bench.py, 64 images, gpurun_out/wreg_bench_{9,10}*.txt): the shapes on which this kernel is the
-        // faster one -- the 64-channel layers (x1.16 with BatchNorm on load, x1.26 - 1.30 without) and, given the
-        // fragment-order weights, 128 / 256 input channels without BatchNorm on load (x1.04 - 1.13 / x1.07 - 1.11; with it
-        // x0.86 - 0.90: one wave per SIMD cannot hide the in-LDS transform).  DESIGN.md section 6c.
-        if (!(a.Cin == 64 || (a.w_frag && !a.in_scale))) return false;
-    }
-    // a persistent workgroup must see enough tiles to amortise loading its weights (74 KB at 64 input channels, two workgroups
-    // per CU; 147 / 295 KB at 128 / 256, one per CU): measured down to 4 tiles per workgroup (256 -> 128 at 64 images: x1.08)
-    const long work = (long)a.N * (a.OH / 8) * (a.OW / 16) * (a.Cout / 64);
-    if (g_wreg_mode == 1) return work >= 2 * 256;
-    return a.Cin == 64 ? work >= 4 * 512 : work >= 4 * 256;
+    p.NCH = shape[0]; p.D = shape[1]; p.PFD = shape[2]; p.WPS = shape[3];
+    p.RES = !p.WINBN && a.res;
+    p.RELU = !p.WINBN && a.act == DH_ACT_RELU;
+    // statistics units (= rows of the stats buffer): 8-row tiles, paired vertically where dh_conv2d_fwd_num_tiles counts 16-row tiles
+    p.stats_rows = (int)(a.rw == 4 ? tiles / 2 : tiles);
+    p.ncb = p.family == CONV_WREG32 || p.family == CONV_WREG32_UP4 ? 1 : a.Cout / 64;
+    p.J = (cus * p.WPS / p.ncb) & ~7;                      // WPS workgroups per CU, a multiple of 8 per output-channel block
+    if (p.J > p.stats_rows) p.J = (p.stats_rows + 7) & ~7;
+    if (p.J < 8) p.J = 8;
+    p.grid_x = p.ncb * p.J;
+    p.grid_y = 1;
+    p.threads = 256;
+    return true;
 }
 
 // C ABI (include/dahitra_hip.h): route the eligible 3x3 convolutions through the tap-oriented kernel instead (mode 0), or
@@ -1159,42 +1147,15 @@ extern "C" int dh_debug_wreg_ts(long long* host, int n) { return (int)hipMemcpyF
 extern "C" int dh_debug_wreg_clear() { static long long z[4096 * 32]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(wr_ts), z, sizeof(z)); }
 #endif
 
-// classifier.0 on upsample4(|a - b|) from the coarse maps (ConvArgs::up4_a / up4_b): the persistent 32 -> 32 stream with the
-// interpolation in LDS.  Eligible: what that stream serves (whole 8x16 tiles, enough of them), no residual, no activation.
-// NOT the default route (DAHITRA_UP4_WREG=1, or dh_conv_wreg_mode(1)): measured at 32 x 256 x 256 (tools/up4_bench.py,
-// profiles/r06a_up4_fused.txt) it takes 116 us against 29.5 + 83.5 for dh_absdiff_upsample4_fwd + the plain stream -- the
-// interpolation more than doubles the stream's vector instructions (rocprofv3 SQ_INSTS_VALU 4.15e7 against 1.82e7, SQ_INSTS_LDS
-// 3.6e6 against 1.7e6) and two waves per SIMD are then bound by VALU issue (~630 instructions per wave and tile next to 36
-// MFMAs), where the plain stream is bound by the 268 MB it moves.
-bool dh_conv_wreg_up4_eligible(const ConvArgs& a) {
-    static const bool off = getenv("DAHITRA_NO_WREG") != nullptr;
-    static const bool on = getenv("DAHITRA_UP4_WREG") != nullptr && atoi(getenv("DAHITRA_UP4_WREG")) == 1;
-    if (off || g_wreg_mode == 0 || !(on || g_wreg_mode == 1) || !a.up4_a || !a.up4_b) return false;
-    if (a.Cin != 32 || a.Cout != 32 || a.CoutPad != 32 || a.res || a.act != DH_ACT_NONE || a.in_scale) return false;
-    if (a.OH != a.H || a.OW != a.W || a.OH % 8 || a.OW % 16) return false;
-    return (long)a.N * (a.OH / 8) * (a.OW / 16) >= (g_wreg_mode == 1 ? 16 : 4 * 512);
-}
-int dh_conv_wreg_up4_launch(const ConvArgs& a, hipStream_t st) {
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    return wr32_up4_launch(a, st, cus);
-}
-
-int dh_conv_wreg_launch(const ConvArgs& a, hipStream_t st) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+int dh_conv_wreg_launch(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    switch (p.family) {
+        case CONV_WREG32_UP4: return wr32_up4_launch(a, p, st);
+        case CONV_WREG32:
+            if (p.RES) return p.RELU ? wr32_launch<true, true>(a, p, st) : wr32_launch<true, false>(a, p, st);
+            return p.RELU ? wr32_launch<false, true>(a, p, st) : wr32_launch<false, false>(a, p, st);
+        //                                         NSUB NCH D PFD WPS
+        case CONV_WREG64: return wr_launch_bn<1, 2, 4, 3, 2>(a, p, st);
+        case CONV_WREG128: return wr_launch_bn<1, 4, 4, 4, 1>(a, p, st);
+        default: return wr_launch_bn<1, 8, 4, 4, 1>(a, p, st);
     }
-    if (a.Cin == 32) {
-        const bool relu = a.act == DH_ACT_RELU;
-        if (a.res) return relu ? wr32_launch<true, true>(a, st, cus) : wr32_launch<true, false>(a, st, cus);
-        return relu ? wr32_launch<false, true>(a, st, cus) : wr32_launch<false, false>(a, st, cus);
-    }
-    //                                 NSUB NCH D PFD WPS
-    if (a.Cin == 64) return wr_launch_bn<1, 2, 4, 3, 2>(a, st, cus);      // 72 weight registers: two workgroups per CU
-    if (a.Cin == 256) return wr_launch_bn<1, 8, 4, 4, 1>(a, st, cus);     // 288: one wave per SIMD
-    // 128 input channels.  Also measured and dropped: 32 output channels per wave (288 registers + 64 accumulators: 60 spills, x0.7), two
-    // workgroups per CU at 144 registers (31 spills, x0.77), deeper rings (D = 5 / 8: no change, cache-cold inputs included).
-    return wr_launch_bn<1, 4, 4, 4, 1>(a, st, cus);
 }

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ x, 
 
 // x [N][H][W][32] bf16, or fp32 (dtype DH_DTYPE_F32: ONLY under dh_set_f32_mma_mode(3), whose arithmetic this is) (pre-BatchNorm when in_scale / in_shift [in_groups][32] are given: relu(x * scale + shift) is the head's
 // input, rounded to bf16 as every BatchNorm-on-load consumer sees it); w_oihw [n_class][32][3][3] fp32 master weights;
-// bias [n_class] or NULL; logits_nchw [N][n_class][H][W] fp32.  Returns DH_CONV_NO_FIT-style -2 (nothing launched, no error text)
+// bias [n_class] or NULL; logits_nchw [N][n_class][H][W] fp32.  Returns -2 (nothing launched, no error text)
 // when the shape is not this kernel's: n_class > 2, or four P rows of W + 2 pixels do not fit a workgroup's LDS share.
 extern "C" int dh_head_fwd_supported(int NC, int W) { return NC >= 1 && NC <= 2 && (long)HF_SLOTS * (W + 2) * HF_KP * 4 <= 80 * 1024; }
 extern "C" int dh_head_fwd(int dtype, const void* x, const float* w_oihw, const float* bias, int NC, const float* in_scale,

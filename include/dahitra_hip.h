@@ -73,6 +73,25 @@ int dh_conv2d_fwd(int dtype, const void* x, const void* w_packed, void* y, const
  * dh_bn_bwd_from_partials consumes (replaces the reduction pass of dh_bn_bwd; torch autograd's native_batch_norm
  * backward + threshold_backward, called from models/resnet.py:58-73 via loss.backward()). */
 int dh_conv2d_fwd_num_tiles(int dtype, int N, int OH, int OW, int Cin, int ks, int stride);   /* dtype: of the launch that fills the buffer */
+/* Host only (no launch, no device, no tensor is read): the launch plan of a forward / data-gradient convolution call under the
+ * thread's current dh_set_f32_mma_mode and dh_conv_wreg_mode, on a device of `cus` compute units.  entry: 0 dh_conv2d_fwd (every
+ * scalar argument as there), 1 dh_conv3x3_head_fwd (dtype, N, H, W, Cin, Cout, in_groups), 2 dh_conv3x3_split_fwd (N, H, W, Cin, Cout),
+ * 3 dh_conv3x3_up4_fwd (N, H, W, act), 4 dh_conv3x3_dgrad_up4 (dtype, N, H, W, Cin = K); the other arguments are ignored.  flags: which
+ * of the tensors the decision depends on are given -- 1 residual, 2 stats_partial, 4 y_preact, 8 the gate_* tensors, 16 in_scale /
+ * in_shift, 32 w_frag, 64 x_split_bytes, 128 y_split_bytes.
+ * out[30], unused fields 0:
+ *   [0]      family: 0 tap kernel bf16, 1 exact fp32, 2 / 3 / 4 its split forms bf16x3 / bf16x6 / fp16x3, 5 the 1x1 GEMM, 6 / 7 / 8 the
+ *            weights-resident stream at 64 / 128 / 256 input channels, 9 its 32 -> 32 form, 10 that with the bilinear x4 on load
+ *   [1..9]   tap kernel: KS, STRIDE, NT, RW, DIL, PF, FAST, INBN, INUP4
+ *   [10..12] GEMM: BN, BM, XDEEP
+ *   [13..21] stream: NCH, D, PFD, WPS, INBN, RES, RELU (those its kernel has), workgroups per channel block J, channel blocks
+ *   [22..25] grid x, grid y, threads, dynamic LDS bytes
+ *   [26..28] tilesX, tilesY, rows per wavefront rw (tile height 4 rw)
+ *   [29]     rows of stats_partial the kernel indexes (= dh_conv2d_fwd_num_tiles of the launch)
+ * Returns non-zero, with dh_last_error set, where the call itself would be refused. */
+int dh_conv2d_fwd_describe(int entry, int dtype, int N, int H, int W, int Cin, int OH, int OW, int Cout, int CoutPad, int ks, int stride,
+                           int pad, int act, int npix_valid, long w_image_stride, int dilation, int gate_groups, int in_groups,
+                           int phase_mode, int flags, int cus, int* out);
 /* bf16 3x3 / stride-1 / pad-1 convolutions with 64 / 128 / 256 input channels and Cout % 64 == 0 on whole 8x16 tiles run,
  * inside dh_conv2d_fwd, on the register-resident-weights kernel (csrc/conv_wreg.hip: persistent workgroups, the weights of
  * a wavefront's output channels stay in its registers, only the input halo is staged) -- same products in the same order as

@@ -451,6 +451,75 @@ def test_fragment_order_packed_weights(ops, cfg):
     close(nchw(y_f), F.conv2d(x, w, None, 1, 1), dtype, "conv, fragment-order weights")
 
 
+# the kernel families of dh_conv2d_fwd_describe (out[0]); out[3] NT, out[10..12] the GEMM's BN, BM, XDEEP
+TAP_BF16, TAP_F32, TAP_X3, TAP_X6, TAP_H3, GEMM, WREG64, WREG128, WREG256, WREG32, WREG32_UP4 = range(11)
+
+
+def conv_plan(ops, dtype, N, H, W, Cin, Cout, ks, stride=1, w_frag=False):
+    """dh_conv2d_fwd_describe's 30 ints for the launch ops.conv2d(x, wp, Cout, ks, stride, ks // 2) makes of a plain [N][H][W][Cin]
+    tensor on this device, under the thread's current modes"""
+    out = (ctypes.c_int * 30)()
+    OH, OW, cus = (H - 1) // stride + 1, (W - 1) // stride + 1, torch.cuda.get_device_properties(0).multi_processor_count
+    rc = ops._lib.lib().dh_conv2d_fwd_describe(0, int(dtype == torch.bfloat16), N, H, W, Cin, OH, OW, Cout, -(-Cout // 16) * 16, ks, stride,
+                                               ks // 2, 0, 0, 0, 1, 1, 1, 0, 32 if w_frag else 0, cus, out)
+    ops._lib.check(rc, "dh_conv2d_fwd_describe")
+    return list(out)
+
+
+@pytest.mark.parametrize("family,dtype,mma,wreg,cfg", [
+    pytest.param(TAP_BF16, torch.bfloat16, 0, -1, (1, 8, 16, 32, 16, 3), id="tap"),
+    pytest.param(TAP_BF16, torch.bfloat16, 0, -1, (1, 24, 24, 32, 32, 3), id="tap-ragged"),
+    pytest.param(GEMM, torch.bfloat16, 0, -1, (1, 8, 16, 64, 64, 1), id="gemm-128"),
+    pytest.param(GEMM, torch.bfloat16, 0, -1, (2, 256, 256, 64, 256, 1), id="gemm-256-deep"),    # the smallest with >= 512 workgroups
+    pytest.param(WREG64, torch.bfloat16, 0, 1, (4, 64, 128, 64, 128, 3), id="wreg"),
+    pytest.param(WREG32, torch.bfloat16, 0, 1, (1, 32, 64, 32, 32, 3), id="wreg32"),
+    pytest.param(TAP_X3, torch.float32, 1, -1, (1, 16, 16, 32, 32, 3), id="bf16x3"),
+    pytest.param(TAP_H3, torch.float32, 3, -1, (1, 16, 16, 32, 32, 3), id="f16x3"),
+])
+def test_the_launch_is_the_one_described(ops, family, dtype, mma, wreg, cfg):
+    """the smallest shape that reaches each kernel family of the forward / data-gradient plan (dh_conv2d_fwd_describe names the
+    family; the weights-resident stream under dh_conv_wreg_mode(1), the 64-channel one with fragment-order weights): dh_conv2d_fwd
+    against torch, at the tolerance of every convolution test here"""
+    N, H, W, Cin, Cout, ks = cfg
+    L = ops._lib.lib()
+    x = rnd((N, Cin, H, W), dtype, 41)
+    w = rnd((Cout, Cin, ks, ks), dtype, 42, scale=(Cin * ks * ks) ** -0.5)
+    frag = family == WREG64
+    if frag:
+        packs = ops.PackPlan(torch.device("cuda"))
+        ff, _ = packs.add(w.cuda(), dtype, dgrad_inner=Cout, frag=True)
+        packs.run()
+    wp, _ = ops.pack_weight(w.cuda(), dtype, want_dgrad=False)
+    prev = L.dh_conv_wreg_mode(wreg)
+    try:
+        plan = conv_plan(ops, dtype, N, H, W, Cin, Cout, ks, w_frag=frag)
+        y = ops.conv2d(dev(nhwc(x), dtype), wp, Cout, ks, 1, ks // 2, w_frag=ff if frag else None)
+    finally:
+        L.dh_conv_wreg_mode(prev)
+    assert plan[0] == family, plan
+    if family == GEMM:
+        assert plan[10:13] == ([256, 256, 1] if N == 2 else [64, 128, 0]), plan
+    close(nchw(y), F.conv2d(x, w, None, 1, ks // 2), dtype, "conv2d out")
+
+
+def test_split_precision_planes_that_do_not_fit_run_the_exact_fp32_kernel(ops):
+    """fp32 under dh_set_f32_mma_mode(2) (three bf16 planes), 3x3 stride 2, 32 -> 32 channels: three planes of the 17 x 33 halo at
+    80 bytes a pixel and of 9 x 32 weight rows are 3 x (44 880 + 18 432) bytes > 160 KB, and a 32-wide layer takes no narrower tile:
+    the plan names the exact fp32 family and the result is the mode-0 result bit for bit"""
+    dtype, N, H, C = torch.float32, 1, 16, 32
+    x = rnd((N, C, H, H), dtype, 43)
+    w = rnd((C, C, 3, 3), dtype, 44, scale=(C * 9) ** -0.5)
+    wp, _ = ops.pack_weight(w.cuda(), dtype, want_dgrad=False)
+    with ops.f32_mma_mode(2):
+        plan = conv_plan(ops, dtype, N, H, H, C, C, 3, stride=2)
+        y2 = ops.conv2d(dev(nhwc(x), dtype), wp, C, 3, 2, 1)
+    with ops.f32_mma_mode(0):
+        y0 = ops.conv2d(dev(nhwc(x), dtype), wp, C, 3, 2, 1)
+    assert plan[0] == TAP_F32, plan
+    assert torch.equal(y2, y0)
+    close(nchw(y0), F.conv2d(x, w, None, 2, 1), dtype, "conv2d out")
+
+
 @pytest.mark.parametrize("dtype,mma", DTYPES_MMA)
 def test_linear_rows_gelu_and_per_image_weights(ops, dtype, mma):
     rows, cin, cout = 40, 32, 64        # rows not a multiple of 16 -> masked tail
