@@ -290,6 +290,87 @@ class GraphedEvalStep:
         return self.logits
 
 
+class GraphedXbdEvalStep:
+    """One validation batch of the xBD loop (xBD_code/train.py:259-279) as ONE HIP graph: the eval-mode weight re-pack, the
+    forward of the 6-channel model and dh_xbd_val_count on its logits -- sigmoid, threshold, arg-max and the tp / fn / fp and
+    dice counts, no host read.
+
+        step = GraphedXbdEvalStep(net, imgs, msk, lbl_msk, class_counts)      # net.eval() is called here
+        logits = step(imgs, msk, lbl_msk)          # class_counts accumulated; step.image_counts [B, 3] holds the batch's rows
+
+    msk is the loader's [B, 5, H, W] mask or its channel 0 ([B, H, W]); only channel 0 is kept.  The shapes are static and
+    CHECKED: a batch of another shape (the ragged last one of an epoch) raises ValueError and goes through the eager path
+    (models/xbd.validate does that); nothing is broadcast.  The parameters are read when the graph replays."""
+
+    def __init__(self, net, imgs, msk, lbl_msk, class_counts, thr=0.3, select='reference', warmup=2):
+        self.net, self.class_counts, self.thr, self.select = net, class_counts, float(thr), select
+        net.eval()
+        self._check(imgs, msk, lbl_msk, tuple(imgs.shape))
+        self.imgs = imgs.clone()
+        self.msk0 = self._plane0(msk).to(torch.uint8).contiguous().clone()
+        self.lbl = lbl_msk.to(torch.uint8).contiguous().clone()
+        self.image_counts = torch.zeros(imgs.shape[0], 3, dtype=torch.int64, device=imgs.device)
+        net._ensure_arena(imgs.device)
+        counts0 = class_counts.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self._body()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        class_counts.copy_(counts0)                          # the warm-up batches are not part of the epoch
+        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
+        ops.rekey_workspace(imgs.device, s, cs)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cs):
+            self.logits = self._body()
+        self._pinned = ops.pin_captured_buffers(net)
+        self._generation = net._arena.generation
+        torch.cuda.synchronize()
+        class_counts.copy_(counts0)
+
+    @staticmethod
+    def _plane0(msk):
+        return msk[:, 0] if msk.dim() == 4 else msk
+
+    @staticmethod
+    def _check(imgs, msk, lbl_msk, want):
+        """`want`: the [B, 6, H, W] the step holds.  Every tensor must have exactly its shape: copy_ would broadcast a [1, ...]
+        batch over the static buffer and score one image B times."""
+        B, _, H, W = want
+        if imgs.dim() != 4 or imgs.shape[1] != 6 or tuple(imgs.shape) != tuple(want):
+            raise ValueError("GraphedXbdEvalStep: imgs %s, the step holds [%d, 6, %d, %d]" % (tuple(imgs.shape), B, H, W))
+        if tuple(msk.shape) not in ((B, 5, H, W), (B, H, W)):
+            raise ValueError("GraphedXbdEvalStep: msk %s is neither [%d, 5, %d, %d] nor its channel 0" % (tuple(msk.shape), B, H, W))
+        if tuple(lbl_msk.shape) != (B, H, W):
+            raise ValueError("GraphedXbdEvalStep: lbl_msk %s, the step holds [%d, %d, %d]" % (tuple(lbl_msk.shape), B, H, W))
+
+    def _body(self):
+        with torch.no_grad():
+            logits = self.net(self.imgs)
+        logits = logits.float()
+        ops.xbd_val_count(logits, self.msk0, self.lbl, self.image_counts, self.class_counts, self.thr, self.select)
+        return logits
+
+    def __call__(self, imgs=None, msk=None, lbl_msk=None):
+        if self.net._arena.generation != self._generation:
+            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this evaluation step was captured; "
+                               "build a new GraphedXbdEvalStep")
+        if self.net.training:
+            raise RuntimeError("dahitra_amd: GraphedXbdEvalStep replays the eval-mode forward; call net.eval() (a train-mode "
+                               "forward in between re-packs the weights for training)")
+        if imgs is not None:
+            if msk is None or lbl_msk is None:
+                raise ValueError("GraphedXbdEvalStep: a batch is imgs, msk and lbl_msk")
+            self._check(imgs, msk, lbl_msk, tuple(self.imgs.shape))
+            self.imgs.copy_(imgs, non_blocking=True)
+            self.msk0.copy_(self._plane0(msk), non_blocking=True)
+            self.lbl.copy_(lbl_msk, non_blocking=True)
+        self.graph.replay()
+        return self.logits
+
+
 class GraphedXbdStep(GraphedTrainStep):
     """The xBD step (xBD_code/train.py:331-374) as one HIP graph: forward of the 6-channel model, the five weighted
     ComboLoss terms, backward, clip_grad_norm_(0.999) and the hand-rolled AdamW.

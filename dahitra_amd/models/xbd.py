@@ -7,7 +7,15 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
     xbd_loss(out, msks)                               xBD_code/train.py:348-353   (the five weighted channel losses)
     clip_grad_norm_(parameters, max_norm)             torch.nn.utils.clip_grad_norm_ as called at train.py:373
     AdamW(params, lr, weight_decay)                   xBD_code/adamw.py:6-86      (hand-rolled; eps before bias correction)
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip + the shared model kernels); CPU tensors are refused."""
+    validate(model, data_loader)                      xBD_code/train.py:247-290   (dice of the localisation + harmonic F1)
+    evaluate_val(data_val, best_score, model, ...)    xBD_code/train.py:293-307   (the snapshot of the best score)
+        the reference reads `optimizer` and the snapshot's folder from globals; here they are arguments
+    dice(im1, im2, empty_score=1.0)                   xBD_code/utils.py:124-154   as val_score's per-image term, on counts
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip + the shared model kernels); CPU tensors
+are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
+import os
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -135,3 +143,113 @@ class AdamW(_ArenaAdamW):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, capturable=False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)
+
+
+# ---- validation (xBD_code/train.py:247-307) ----------------------------------------------------------------
+def val_score(image_counts, class_counts, empty_score=1.0):
+    """The reference's score from the counts of ops.xbd_val_count, in its own float64 numpy expressions.
+    image_counts: integers [n_images, 3] = |gt0|, |loc|, |gt0 & loc| per image; class_counts: integers [4, 3] = tp, fn, fp per
+    class.  dice of an image = 2 |gt0 & loc| / (|gt0| + |loc|), `empty_score` when both are empty (utils.py:147-154);
+    d0 = mean of the dices; f1_sc[c] = 2 tp / (2 tp + fp + fn), nan for 0 / 0 as numpy gives it; f1 = 4 / sum(1 / (f1_sc +
+    1e-6)); score = 0.3 d0 + 0.7 f1 (train.py:281-288).  A class without a counted pixel makes the score nan, and
+    `nan > best_score` is False: the reference's behaviour, kept.  Returns (score, {'dice', 'f1', 'f1_per_class'}).
+    The counts are additive: ranks that validate shards sum them before this call."""
+    ic = np.asarray(image_counts.cpu() if torch.is_tensor(image_counts) else image_counts).astype(np.int64).reshape(-1, 3)
+    cc = np.asarray(class_counts.cpu() if torch.is_tensor(class_counts) else class_counts).astype(np.int64).reshape(4, 3)
+    dices0 = []
+    for gt0, loc, both in ic:
+        im_sum = gt0 + loc
+        dices0.append(empty_score if im_sum == 0 else 2. * both / im_sum)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        d0 = np.mean(dices0) if dices0 else np.float64('nan')
+        tp, fn, fp = (cc[:, k].astype(np.float64) for k in range(3))          # np.zeros((4,)) accumulators: float64
+        f1_sc = np.zeros((4,))
+        for c in range(4):
+            f1_sc[c] = 2 * tp[c] / (2 * tp[c] + fp[c] + fn[c])
+        f1 = 4 / np.sum(1.0 / (f1_sc + 1e-6))
+        sc = 0.3 * d0 + 0.7 * f1
+    return sc, {'dice': d0, 'f1': f1, 'f1_per_class': f1_sc}
+
+
+def _eval_step(model, batch, class_counts, thr, select):
+    """the model's recorded validation step for this batch shape (kept on the model: a graph pins its buffers for the life of
+    the process, so an epoch must not record a new one)"""
+    from ..graph import GraphedXbdEvalStep
+    steps = model.__dict__.setdefault('_xbd_eval_steps', {})
+    key = (tuple(batch['img'].shape), float(thr), select, str(batch['img'].device))
+    step = steps.get(key)
+    if step is not None and (step._generation != model._arena.generation or step.class_counts is not class_counts):
+        step = None
+    if step is None:
+        step = steps[key] = GraphedXbdEvalStep(model, batch['img'], batch['msk'], batch['lbl_msk'], class_counts, thr, select)
+    return step
+
+
+def validate(model, batches, thr=0.3, select='reference', graph=True, want_counts=False):
+    """validate(model, data_loader) of xBD_code/train.py:247-290 on the device.  batches: dicts {'img' [B, 6, H, W] fp32,
+    'msk' [B, 5, H, W], 'lbl_msk' [B, H, W]} as GpuXbdPipeline.batches(b, size, train=False) yields them (uint8; the
+    reference's long tensors are converted).  Per batch: the eval-mode forward and ONE count kernel (ops.xbd_val_count); the
+    batch's image rows go into the epoch's [n_images, 3] device buffer by an asynchronous device copy.  Nothing is read by the
+    host until the epoch is over: ONE read then, and val_score on the integers.  graph=True replays a GraphedXbdEvalStep for
+    every batch of the first batch's shape (recorded once per model and shape) and runs other shapes -- a ragged last batch --
+    eagerly; the counts are the same bits either way.  select: 'reference' (default; train.py:271-274 as executed: rows chosen
+    by the first row of lbl_msk) or 'building' (pixels of msk[:, 0]), see ops.xbd_val_count.
+    Prints the reference's `Val Score: ...` line and returns the score (with want_counts: score, parts, image_counts,
+    class_counts as numpy integers)."""
+    if select not in ops.XBD_VAL_SELECT:
+        raise ValueError("validate: select %r is not one of %s" % (select, sorted(ops.XBD_VAL_SELECT)))
+    model.eval()
+    class_counts = model.__dict__.get('_xbd_val_class_counts')
+    rows, n, first, dev = None, 0, None, None
+    with torch.no_grad():
+        for batch in batches:
+            imgs, msk, lbl = batch['img'], batch['msk'], batch['lbl_msk']
+            if not imgs.is_cuda:
+                raise _lib.HipLibraryError("dahitra_amd xBD validation runs on MI355X only (no CPU fallback)")
+            B = imgs.shape[0]
+            if rows is None:
+                dev, first = imgs.device, tuple(imgs.shape)
+                if class_counts is None or class_counts.device != dev:
+                    class_counts = model.__dict__['_xbd_val_class_counts'] = torch.zeros(4, 3, dtype=torch.int64, device=dev)
+                class_counts.zero_()
+                rows = torch.zeros(max(64, B), 3, dtype=torch.int64, device=dev)
+            if n + B > rows.shape[0]:            # an iterator does not say how long it is: the buffer doubles, on the device
+                rows = torch.cat([rows, torch.zeros(max(rows.shape[0], B), 3, dtype=torch.int64, device=dev)])
+            if graph and tuple(imgs.shape) == first:
+                step = _eval_step(model, batch, class_counts, thr, select)
+                step(imgs, msk, lbl)
+                rows[n:n + B].copy_(step.image_counts, non_blocking=True)
+            else:
+                ops.xbd_val_count(model(imgs).float(), msk, lbl, rows[n:n + B], class_counts, thr, select)
+            n += B
+    if rows is None:
+        raise ValueError("validate: no batches")
+    both = torch.cat([rows[:n].reshape(-1), class_counts.reshape(-1)]).cpu().numpy()        # the epoch's one read
+    image_counts, cc = both[:n * 3].reshape(n, 3), both[n * 3:].reshape(4, 3)
+    sc, parts = val_score(image_counts, cc)
+    f1_sc = parts['f1_per_class']
+    print("Val Score: {}, Dice: {}, F1: {}, F1_0: {}, F1_1: {}, F1_2: {}, F1_3: {}".format(sc, parts['dice'], parts['f1'], f1_sc[0],
+                                                                                          f1_sc[1], f1_sc[2], f1_sc[3]))
+    return (sc, parts, image_counts, cc) if want_counts else sc
+
+
+def evaluate_val(batches, best_score, model, optimizer, path, current_epoch, thr=0.3, select='reference', graph=True):
+    """evaluate_val of xBD_code/train.py:293-307: validate, and when the score beats `best_score` save the snapshot {'epoch':
+    current_epoch + 1, 'state_dict', 'best_score', 'optimizer'} to `path` (the reference's models_folder/snapshot_name).  A nan
+    score (no counted pixel) beats nothing, as in the reference.  Prints its `score: ... score_best: ...` line and returns the
+    best score."""
+    model = model.eval()
+    d = validate(model, batches, thr=thr, select=select, graph=graph)
+    if d > best_score:
+        folder = os.path.dirname(path)
+        if folder:
+            os.makedirs(folder, exist_ok=True)
+        torch.save({
+            'epoch': current_epoch + 1,
+            'state_dict': model.state_dict(),
+            'best_score': d,
+            'optimizer': optimizer.state_dict(),
+        }, path)
+        best_score = d
+    print("score: {}\tscore_best: {}".format(d, best_score))
+    return best_score

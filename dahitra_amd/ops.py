@@ -1844,6 +1844,63 @@ def adamw_xbd_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weig
           step, P(grad_scale_dev), S())
 
 
+# ---- xBD validation count (csrc/xbd_eval.hip) -----------------------------------------------------------
+XBD_VAL_SELECT = {"reference": 0, "building": 1}
+
+
+def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select="reference"):
+    """The counts of the reference's validate() (xBD_code/train.py:258-279) for one batch, on the device, no host read.
+    logits [B, 5, H, W] fp32; msk: the batch's mask [B, 5, H, W] (channel 0 is read in place) or its localisation plane
+    [B, H, W] / msk[:, 0], uint8 as the device loader gives it; lbl [B, H, W] uint8 (classes 0 .. 3).  A long tensor (the
+    reference's dtype) is converted once.  image_counts int64 [B, 3] = |gt0|, |loc|, |gt0 & loc| is written, class_counts int64
+    [4, 3] = tp, fn, fp of each class is accumulated.  select: 'reference' (train.py:271-274: row r counts iff
+    lbl[j, 0, r] > 0; H == W) or 'building' (pixel p counts iff msk[j, 0, p] > 0).  ValueError for shapes or dtypes that do not
+    fit, before the call."""
+    if select not in XBD_VAL_SELECT:
+        raise ValueError("xbd_val_count: select %r is not one of %s" % (select, sorted(XBD_VAL_SELECT)))
+    if logits.dim() != 4 or logits.shape[1] != 5:
+        raise ValueError("xbd_val_count: logits %s are not [B, 5, H, W]" % (tuple(logits.shape),))
+    if logits.dtype != torch.float32:
+        raise ValueError("xbd_val_count: logits are %s, the sigmoid is taken in float32" % logits.dtype)
+    B, _, H, W = logits.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError("xbd_val_count: empty logits %s" % (tuple(logits.shape),))
+    if msk.dim() == 4:
+        if tuple(msk.shape) != (B, 5, H, W):
+            raise ValueError("xbd_val_count: msk %s does not match logits %s" % (tuple(msk.shape), tuple(logits.shape)))
+        msk = msk[:, 0]
+    if tuple(msk.shape) != (B, H, W):
+        raise ValueError("xbd_val_count: msk %s is neither [B, 5, H, W] nor [B, H, W] of logits %s"
+                         % (tuple(msk.shape), tuple(logits.shape)))
+    if tuple(lbl.shape) != (B, H, W):
+        raise ValueError("xbd_val_count: lbl_msk %s is not [B, H, W] of logits %s" % (tuple(lbl.shape), tuple(logits.shape)))
+    if select == "reference" and H != W:
+        raise ValueError("xbd_val_count: the reference's selection lbl_msk[j][lbl_msk[j, 0] > 0] indexes rows by the first row "
+                         "and needs H == W, got %dx%d (numpy raises IndexError there)" % (H, W))
+    for name, t in (("msk", msk), ("lbl_msk", lbl)):
+        if t.dtype not in (torch.uint8, torch.int64, torch.bool):
+            raise ValueError("xbd_val_count: %s is %s, expected uint8 (or the reference's long)" % (name, t.dtype))
+    if msk.dtype != torch.uint8:
+        msk = (msk != 0).to(torch.uint8)
+    if lbl.dtype != torch.uint8:
+        lbl = lbl.clamp(0, 255).to(torch.uint8)
+    # channel 0 of a contiguous [B, 5, H, W] mask: planes contiguous, images 5 * H * W bytes apart -- read without a copy
+    if not (msk.stride(2) == 1 and msk.stride(1) == W and (B == 1 or msk.stride(0) >= H * W)):
+        msk = msk.contiguous()
+    stride = msk.stride(0) if B > 1 else H * W
+    if tuple(image_counts.shape) != (B, 3) or image_counts.dtype != torch.int64:
+        raise ValueError("xbd_val_count: image_counts %s %s is not int64 [%d, 3]" % (tuple(image_counts.shape), image_counts.dtype, B))
+    if tuple(class_counts.shape) != (4, 3) or class_counts.dtype != torch.int64:
+        raise ValueError("xbd_val_count: class_counts %s %s is not int64 [4, 3]" % (tuple(class_counts.shape), class_counts.dtype))
+    if not 0.0 < float(thr) < 1.0:
+        raise ValueError("xbd_val_count: thr=%r must lie inside (0, 1)" % (thr,))
+    for t in (logits, msk, lbl, image_counts, class_counts):
+        if not t.is_cuda:
+            raise _lib.HipLibraryError("xbd_val_count runs on MI355X only (no CPU fallback)")
+    _call("dh_xbd_val_count", P(logits.contiguous()), _vp(msk.data_ptr()), stride, P(lbl.contiguous()), B, H, W, float(thr),
+          XBD_VAL_SELECT[select], P(image_counts), P(class_counts), S())
+
+
 # ---- variants writing into caller-provided (contiguous) buffers ------------------------------------
 def stem_space_to_depth_into(x_nchw, out):
     N, C, H, W = x_nchw.shape

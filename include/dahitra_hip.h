@@ -701,6 +701,17 @@ int dh_adamw_xbd_step(float* param, const float* grad, float* exp_avg, float* ex
 int dh_adamw_xbd_step_graph(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float* hyper_dev,
                             int* step_dev, const float* grad_scale_dev, void* stream);
 
+/* ---- xBD validation count (xBD_code/train.py:258-279; csrc/xbd_eval.hip) -------------------------------
+ * One pass over logits [B][5][H][W] fp32: s = sigmoid in fp32, loc = s[0] > thr (strict, in float32), pred = argmax(s[1:]) * loc
+ * with the first maximum of the fp32 sigmoids winning.  msk0: image j's ground-truth localisation plane [H][W] (nonzero = set) at
+ * msk0 + j * msk0_image_stride bytes (5 * H * W reads channel 0 of a [B][5][H][W] mask in place); lbl [B][H][W]: classes 0 .. 3.
+ * image_counts [B][3] = |gt0|, |loc|, |gt0 & loc| is WRITTEN; class_counts [4][3] = tp, fn, fp of each class is ACCUMULATED over the selected
+ * pixels: select 0 = the reference's boolean index by the first row (row r with all its columns iff lbl[j][0][r] > 0; needs
+ * H == W), select 1 = pixel p iff msk0[j][p] > 0.  All counting is integer: exact, independent of the order of the sums.
+ * Refused (nothing is written): a null pointer, B < 1, thr outside (0, 1), select 0 with H != W, H * W >= 2^31. */
+int dh_xbd_val_count(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl, int B,
+                     int H, int W, float thr, int select, long long* image_counts, long long* class_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
