@@ -1003,56 +1003,77 @@ template <int MLP> size_t bwd_lds_bytes() {
 }  // namespace
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
+#define KERN(...) reinterpret_cast<const void*>(__VA_ARGS__)
+// Kernels land in the code object in the order the host code first names them.  This list names them in the order the file always
+// had, so the host half can be rearranged without moving an instruction (profiles/decoder_plan_kernels.diff).
+[[maybe_unused]] static const void* const dec_code_order[] = {
+    KERN(dec_fwd_multi_kernel<32, false>), KERN(dec_fwd_multi_kernel<64, false>), KERN(dec_fwd_multi_kernel<32, true>), KERN(dec_fwd_multi_kernel<64, true>),
+    KERN(dec_bwd_multi_kernel<32, false>), KERN(dec_bwd_multi_kernel<64, false>), KERN(dec_bwd_multi_kernel<32, true>), KERN(dec_bwd_multi_kernel<64, true>),
+    KERN(dec_bwd_finalize_multi_kernel<32>), KERN(dec_bwd_finalize_multi_kernel<64>), KERN(dec_fwd_kernel<64, false>), KERN(dec_fwd_kernel<32, false>),
+    KERN(dec_bwd_kernel<64, false>), KERN(dec_bwd_finalize_kernel<64>), KERN(dec_bwd_kernel<32, false>), KERN(dec_bwd_finalize_kernel<32>),
+    KERN(dec_fwd_kernel<64, true>), KERN(dec_fwd_kernel<32, true>), KERN(dec_bwd_kernel<64, true>), KERN(dec_bwd_kernel<32, true>)};
 
+// ---- the DAHITRA_DEC_* switches, read once per process ----------------------------------------------------------------
+struct DecSwitches {
+    long fwd_minblk, bwd_minblk;      // DAHITRA_DEC_FWD_MINBLK (1024) / _BWD_MINBLK (256): workgroups a default plan keeps
+    int bwd_maxrpb64;                 // DAHITRA_DEC_BWD_MAXRPB64 (1024): rows per backward workgroup at MLP 64
+    bool balance;                     // DAHITRA_DEC_BALANCE=0: the per-job default plans for launches of several jobs too
+    int upb_fwd, upb_bwd;             // DAHITRA_DEC_UPB_FWD / _BWD=<n>: that block size for every job of a batched launch
+    bool balance_log, no_sort;        // DAHITRA_DEC_BALANCE_LOG, DAHITRA_DEC_NO_SORT (set, whatever the value)
+};
+static const DecSwitches& dec_sw() {
+    static const DecSwitches sw = [] {
+        const auto num = [](const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; };
+        return DecSwitches{num("DAHITRA_DEC_FWD_MINBLK", 1024), num("DAHITRA_DEC_BWD_MINBLK", 256), (int)num("DAHITRA_DEC_BWD_MAXRPB64", 1024),
+                           num("DAHITRA_DEC_BALANCE", 1) != 0, (int)num("DAHITRA_DEC_UPB_FWD", 0), (int)num("DAHITRA_DEC_UPB_BWD", 0),
+                           getenv("DAHITRA_DEC_BALANCE_LOG") != nullptr, getenv("DAHITRA_DEC_NO_SORT") != nullptr};
+    }();
+    return sw;
+}
 
-// ---- block sizes (DecArgs::upb / bpi) ---------------------------------------------------------------------------------
+// ---- the plan of one launch ---------------------------------------------------------------------------------------------
 // A plan cuts every image of a job into blocks of `upb` 64-row units.  The DEFAULT plans are the fixed rules of the first builds
 // (powers of two that divide an image); launches that hold several jobs (dh_decoder_batch_*: DAHiTra's three levels) are
-// re-planned as a whole by dec_balance when they are issued.
+// re-planned as a whole when they are issued (dec_plan_launch).
+struct DecShape { long rows; int rows_per_image, depth; };      // depth: layers a workgroup runs back to back (1: a single layer)
+struct DecJobPlan { int src, upb, bpi, first, blocks; };         // src: index of the job as it was given; workgroups [first, first + blocks)
+struct DecLaunchPlan {
+    bool bwd, stack, multi;           // which kernel: dec_{fwd,bwd}[_multi]_kernel<mlp, stack>
+    int mlp;
+    int n;
+    DecJobPlan job[DEC_MAXJ];         // in issue order
+    int grid, threads;
+    size_t lds;
+};
 struct DecPlan { int upb, bpi; };
 static inline DecPlan dec_plan(int rows_per_image, int upb) {
     const int upi = rows_per_image / 64;
     upb = std::max(1, std::min(upb, upi));
     return DecPlan{upb, (upi + upb - 1) / upb};
 }
+// The per-job default rule.
 // rows per forward workgroup: every workgroup stages the image's kq / voT and the two weight matrices first (a quarter of the
 // instructions of a 128-row workgroup), so large launches take more rows per workgroup while >= 1024 workgroups remain
-static inline DecPlan dec_fwd_default(long rows, int rows_per_image) {
-    static const long minblk = getenv("DAHITRA_DEC_FWD_MINBLK") ? atol(getenv("DAHITRA_DEC_FWD_MINBLK")) : 1024;
-    int rpb = 512;
-    while (rpb > 64 && (rows_per_image % rpb || rows / rpb < minblk)) rpb >>= 1;
-    return dec_plan(rows_per_image, rpb / 64);
-}
 // rows per backward workgroup: 512 at most (every workgroup writes a PL::SIZE partial), fewer while that leaves less than 256
 // workgroups; per layer a workgroup spends several microseconds outside its sub-tile loop (parking and reducing the
 // parameter-gradient partials, writing them: tools/dec_timeline.py), so the small levels of a staged launch want rows, not
 // workgroups.  MLP = 64 (one workgroup per CU at 344 registers: 256 resident) takes up to 1024 rows: 256 workgroups in ONE
 // round instead of 512 in two (+0.3 % on the s4 step; DAHITRA_DEC_BWD_MAXRPB64=512 restores the old rule)
-static inline DecPlan dec_bwd_default(long rows, int rows_per_image, int mlp) {
-    static const long minblk = getenv("DAHITRA_DEC_BWD_MINBLK") ? atol(getenv("DAHITRA_DEC_BWD_MINBLK")) : 256;
-    static const int max64 = getenv("DAHITRA_DEC_BWD_MAXRPB64") ? atoi(getenv("DAHITRA_DEC_BWD_MAXRPB64")) : 1024;
-    int rpb = mlp == 64 ? max64 : 512;
+static inline DecPlan dec_default(bool bwd, long rows, int rows_per_image, int mlp) {
+    const DecSwitches& sw = dec_sw();
+    const long minblk = bwd ? sw.bwd_minblk : sw.fwd_minblk;
+    int rpb = bwd && mlp == 64 ? sw.bwd_maxrpb64 : 512;
     while (rpb > 64 && (rows_per_image % rpb || rows / rpb < minblk)) rpb >>= 1;
     return dec_plan(rows_per_image, rpb / 64);
 }
 // the smallest backward block a re-plan may choose: the partial workspace (dh_decoder_layer_bwd_workspace_size) is sized for it
 static inline int dec_bwd_min_upb(long rows, int rows_per_image, int mlp) {
-    return std::max(1, dec_bwd_default(rows, rows_per_image, mlp).upb / 2);
-}
-// The plan a backward launch used, by the address of its partial workspace: the finalize (a separate call, possibly issued in a
-// later round of the batch) sums exactly the blocks that launch wrote.
-static thread_local std::unordered_map<const void*, DecPlan> g_bwd_plan;
-static void dec_remember_plan(const void* partial, DecPlan pl) {
-    if (g_bwd_plan.size() > 512) g_bwd_plan.clear();
-    g_bwd_plan[partial] = pl;
-}
-static DecPlan dec_recall_plan(const void* partial, long rows, int rows_per_image, int mlp) {
-    auto it = g_bwd_plan.find(partial);
-    return it != g_bwd_plan.end() ? it->second : dec_bwd_default(rows, rows_per_image, mlp);
+    return std::max(1, dec_default(true, rows, rows_per_image, mlp).upb / 2);
 }
 
-// dec_balance: block sizes for ALL jobs of one launch (dh_decoder_batch_*: DAHiTra's three levels).  These kernels are bound by
-// the vector ALU of a CU, not by resident workgroups: one backward workgroup alone on a CU takes ~1.75 us per 64-row unit, two
+// The whole launch: block sizes for ALL its jobs, then their order.  An eager launch (multi == false) is one job under the
+// default rule; the launches of a batch (dh_decoder_batch_*: DAHiTra's three levels) are balanced first -- dec_balance, as the
+// notes and the log line call it.  These kernels are bound by the vector ALU of a CU, not by resident workgroups: one backward workgroup alone on a CU takes ~1.75 us per 64-row unit, two
 // share it at ~3.5 us each -- the same throughput -- while every (workgroup, layer) pays for staging the layer's matrices and for
 // parking, reducing and writing 17 KB of parameter-gradient partials.  So: as FEW, LARGE blocks as keep every CU busy.  The job
 // with the most work gets the largest upb <= 16 that still leaves `per_cu` blocks per CU (backward 1, forward 2: its
@@ -1061,23 +1082,24 @@ static DecPlan dec_recall_plan(const void* partial, long rows, int rows_per_imag
 // 166 -> 160 us (32 images) against the per-job rules, forward 146 -> 139 and 76 -> 69 us; a list-scheduling model over
 // resident-workgroup slots (the first form of this function) predicted gains it did not deliver, because a slot is not a
 // processor.  DAHITRA_DEC_BALANCE=0: the per-job default plans.  DAHITRA_DEC_UPB_FWD / _BWD=<n>: that block size for every job.
-static void dec_balance(DecMulti& m, int n, bool bwd, int mlp, int cus) {
-    static const bool on = !(getenv("DAHITRA_DEC_BALANCE") && atoi(getenv("DAHITRA_DEC_BALANCE")) == 0);
-    static const int force_f = getenv("DAHITRA_DEC_UPB_FWD") ? atoi(getenv("DAHITRA_DEC_UPB_FWD")) : 0;
-    static const int force_b = getenv("DAHITRA_DEC_UPB_BWD") ? atoi(getenv("DAHITRA_DEC_UPB_BWD")) : 0;
-    int upb[DEC_MAXJ], lo[DEC_MAXJ];
+static DecLaunchPlan dec_plan_launch(bool bwd, bool stack, int mlp, bool multi, int n, const DecShape* s, int cus) {
+    const DecSwitches& sw = dec_sw();
+    DecLaunchPlan p = {};
+    p.bwd = bwd; p.stack = stack; p.multi = multi; p.mlp = mlp; p.n = n;
+    p.threads = 256;
+    p.lds = !bwd ? 0 : mlp == 64 ? bwd_lds_bytes<64>() : bwd_lds_bytes<32>();
+    int upb[DEC_MAXJ], dflt[DEC_MAXJ], lo[DEC_MAXJ];
     int big = 0;
     for (int j = 0; j < n; ++j) {
-        const DecArgs& a = m.a[j];
-        upb[j] = a.upb;
-        lo[j] = bwd ? dec_bwd_min_upb(a.rows, a.rows_per_image, mlp) : 1;
-        if ((a.depth > 1 ? a.depth : 1) * a.rows > (m.a[big].depth > 1 ? m.a[big].depth : 1) * m.a[big].rows) big = j;
+        upb[j] = dflt[j] = dec_default(bwd, s[j].rows, s[j].rows_per_image, mlp).upb;
+        lo[j] = bwd ? dec_bwd_min_upb(s[j].rows, s[j].rows_per_image, mlp) : 1;
+        if (s[j].depth * s[j].rows > s[big].depth * s[big].rows) big = j;
     }
-    const int force = bwd ? force_b : force_f;
-    if (force > 0) {
-        for (int j = 0; j < n; ++j) upb[j] = std::max(lo[j], std::min(force, m.a[j].rows_per_image / 64));
-    } else if (on && cus > 0 && n > 1) {
-        const DecArgs& a = m.a[big];
+    const int force = bwd ? sw.upb_bwd : sw.upb_fwd;
+    if (multi && force > 0) {
+        for (int j = 0; j < n; ++j) upb[j] = std::max(lo[j], std::min(force, s[j].rows_per_image / 64));
+    } else if (multi && sw.balance && cus > 0 && n > 1) {
+        const DecShape& a = s[big];
         const int upi = a.rows_per_image / 64, images = (int)(a.rows / a.rows_per_image), want = (bwd ? 1 : 2) * cus;
         // (block sizes that divide an image: a ragged last block is a short workgroup next to long ones)
         int u = std::min(16, upi);
@@ -1086,26 +1108,38 @@ static void dec_balance(DecMulti& m, int n, bool bwd, int mlp, int cus) {
         upb[big] = u;
         for (int j = 0; j < n; ++j)
             if (j != big) {
-                int v = std::min(std::min(16, m.a[j].rows_per_image / 64), std::max(u, 4));
-                while (v > lo[j] && (m.a[j].rows_per_image / 64) % v) --v;
+                int v = std::min(std::min(16, s[j].rows_per_image / 64), std::max(u, 4));
+                while (v > lo[j] && (s[j].rows_per_image / 64) % v) --v;
                 upb[j] = std::max(lo[j], v);
             }
     }
-    if (getenv("DAHITRA_DEC_BALANCE_LOG")) {
+    if (multi && sw.balance_log) {
         fprintf(stderr, "[dec_balance] %s mlp %d cus %d:", bwd ? "bwd" : "fwd", mlp, cus);
         for (int j = 0; j < n; ++j)
-            fprintf(stderr, "  (%ld x %d rows, depth %d) upb %d -> %d", m.a[j].rows / m.a[j].rows_per_image, m.a[j].rows_per_image, m.a[j].depth,
-                    m.a[j].upb, upb[j]);
+            fprintf(stderr, "  (%ld x %d rows, depth %d) upb %d -> %d", s[j].rows / s[j].rows_per_image, s[j].rows_per_image, s[j].depth,
+                    dflt[j], upb[j]);
         fprintf(stderr, "\n");
     }
-    m.first[0] = 0;
     for (int j = 0; j < n; ++j) {
-        const DecPlan pl = dec_plan(m.a[j].rows_per_image, upb[j]);
-        m.a[j].upb = pl.upb;
-        m.a[j].bpi = pl.bpi;
-        m.first[j + 1] = m.first[j] + (int)(m.a[j].rows / m.a[j].rows_per_image) * pl.bpi;
-        if (bwd) dec_remember_plan(m.a[j].partial, pl);
+        const DecPlan pl = dec_plan(s[j].rows_per_image, upb[j]);
+        p.job[j] = DecJobPlan{j, pl.upb, pl.bpi, 0, (int)(s[j].rows / s[j].rows_per_image) * pl.bpi};
     }
+    // Longest workgroups FIRST: the workgroups of a launch are dispatched in index order, and a workgroup of a layer-fused stack
+    // runs depth x (rows per workgroup / 64) sub-tile rounds back to back -- DAHiTra's 64 x 64 level: 4 layers x 8 sub-tiles, ~140 us
+    // of the backward, against 8 rounds for the other two levels.  Recorded in the order the levels run (16 x 16 first) the long
+    // workgroups started only when the short ones had drained and set the launch's length by themselves: 285 us for ~190 us of work.
+    if (multi && !sw.no_sort)
+        for (int i = 1; i < n; ++i)                      // insertion sort, stable: n <= 4
+            for (int j = i; j > 0; --j) {
+                const long wa = (long)s[p.job[j].src].depth * p.job[j].upb, wb = (long)s[p.job[j - 1].src].depth * p.job[j - 1].upb;
+                if (wa <= wb) break;
+                std::swap(p.job[j], p.job[j - 1]);
+            }
+    for (int j = 0; j < n; ++j) {
+        p.job[j].first = p.grid;
+        p.grid += p.job[j].blocks;
+    }
+    return p;
 }
 static int dec_cus() {
     static int cus = -1;
@@ -1118,111 +1152,220 @@ static int dec_cus() {
     return cus;
 }
 
-// ---- batched launches (dh_decoder_batch_*): index 0 = MLP 32, 1 = MLP 64; forward and backward each
+// The one launch site of the eight forward / backward kernels in their single (DecArgs) and multi (DecMulti) forms; a backward
+// kernel gets its dynamic LDS raised once.
+template <int MLP, bool STACK> static int dec_launch_as(const DecLaunchPlan& p, const DecArgs* a, const DecMulti* m, hipStream_t st) {
+    const dim3 grid(p.grid), threads(p.threads);
+    if (!p.bwd) {
+        if (p.multi) hipLaunchKernelGGL((dec_fwd_multi_kernel<MLP, STACK>), grid, threads, p.lds, st, *m);
+        else hipLaunchKernelGGL((dec_fwd_kernel<MLP, STACK>), grid, threads, p.lds, st, *a);
+        return 0;
+    }
+    static bool raised[2] = {false, false};
+    if (!raised[p.multi]) {
+        raised[p.multi] = true;
+        if (hipFuncSetAttribute(p.multi ? KERN(dec_bwd_multi_kernel<MLP, STACK>) : KERN(dec_bwd_kernel<MLP, STACK>),hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) {
+            (void)hipGetLastError();
+            DH_FAIL("decoder_layer_bwd: cannot raise dynamic LDS to %zu", p.lds);
+        }
+    }
+    if (p.multi) hipLaunchKernelGGL((dec_bwd_multi_kernel<MLP, STACK>), grid, threads, p.lds, st, *m);
+    else hipLaunchKernelGGL((dec_bwd_kernel<MLP, STACK>), grid, threads, p.lds, st, *a);
+    return 0;
+}
+static int dec_launch(const DecLaunchPlan& p, const DecArgs* a, const DecMulti* m, hipStream_t st) {
+    switch ((p.mlp == 64) + 2 * p.stack) {
+        case 0: return dec_launch_as<32, false>(p, a, m, st);
+        case 1: return dec_launch_as<64, false>(p, a, m, st);
+        case 2: return dec_launch_as<32, true>(p, a, m, st);
+        default: return dec_launch_as<64, true>(p, a, m, st);
+    }
+}
+
+extern "C" long dh_decoder_layer_bwd_workspace_size(long rows, int rows_per_image, int mlp) {
+    // (sized for the smallest block a re-planned launch may use, dec_plan_launch: up to twice the default plan's blocks)
+    const long nblk = (rows / rows_per_image) * dec_plan(rows_per_image, dec_bwd_min_upb(rows, rows_per_image, mlp)).bpi;
+    return nblk * (mlp == 64 ? PL<64>::SIZE : PL<32>::SIZE) * 4;
+}
+
+static inline long dec_layer_floats(long rows, int rows_per_image, int mlp) { return dh_decoder_layer_bwd_workspace_size(rows, rows_per_image, mlp) / 4; }
+
+// The finalize of a backward that wrote `bpi` blocks per image: what it reads and its grid
+struct FinGeom { int images, nblk, gx, grid; long pstride, kstride; };
+static FinGeom dec_fin_geom(long rows, int rows_per_image, int mlp, int depth, int bpi) {
+    FinGeom g;
+    g.images = (int)(rows / rows_per_image);
+    g.nblk = g.images * bpi;
+    g.gx = dh_cdiv(mlp == 64 ? PL<64>::KQ : PL<32>::KQ, 32);
+    g.grid = fin_blocks(g.gx, g.images, depth);
+    g.pstride = dec_layer_floats(rows, rows_per_image, mlp);
+    g.kstride = (long)g.images * 1024;
+    return g;
+}
+static inline void dec_fin_fill(FinArgs& fa, const FinGeom& g, int bpi) { fa.nblk = g.nblk; fa.bpi = bpi; fa.pstride = g.pstride; fa.kstride = g.kstride; }
+
+// ---- batched launches (dh_decoder_batch_*): forward and backward each
+// The blocks a re-planned backward launch of a batch wrote, by the workspace it wrote them to, until the finalize of that
+// workspace takes the entry, a later backward on it replaces it or dh_decoder_batch_abort drops it.  Only plans that differ
+// from the default are kept: the default is a pure function of (rows, rows per image, mlp), and an eager backward always
+// uses it.  Entries leave one by one, never wholesale; a full table is an error.
+struct DecWritten {
+    const float* partial;
+    int layers;                       // the launch wrote `layers` consecutive per-layer workspaces from `partial` on
+    long rows;
+    int rows_per_image, mlp, bpi;
+};
+constexpr int DEC_MAXWRITTEN = 64;
+struct DecFinJob { int depth, rows_per_image; long rows; };
 struct DecBatch {      // index = (MLP == 64) + 2 * (layer-fused stack)
     bool on = false;
     int nf[4] = {0, 0, 0, 0}, nb[4] = {0, 0, 0, 0};
     DecMulti f[4], b[4];
     int nfin[2] = {0, 0};      // recorded stack finalizes (MLP 32 / 64): issued after the backward launches
     FinMulti fin[2];
+    DecFinJob finjob[2][DEC_MAXJ];
+    int nw = 0;
+    DecWritten w[DEC_MAXWRITTEN];
 };
 static thread_local DecBatch g_db;
-template <int MLP> static int dec_set_bwd_lds(const void* kern, bool& done) {
-    if (!done) {
-        done = true;
-        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_lds_bytes<MLP>()) != hipSuccess) {
-            (void)hipGetLastError();
-            DH_FAIL("decoder_layer_bwd: cannot raise dynamic LDS to %zu", bwd_lds_bytes<MLP>());
-        }
+// removes what the table holds on the `layers` per-layer workspaces from `partial` on; bpi (a finalize asks): the blocks per image
+// the last backward wrote there
+static int dec_take_written(const float* partial, int layers, long rows, int rows_per_image, int mlp, int* bpi) {
+    DecBatch& d = g_db;
+    const float* end = partial + layers * dec_layer_floats(rows, rows_per_image, mlp);
+    int covered = 0;
+    if (bpi) *bpi = dec_default(true, rows, rows_per_image, mlp).bpi;
+    for (int i = d.nw - 1; i >= 0; --i) {
+        const DecWritten e = d.w[i];
+        if (e.partial < partial || e.partial >= end) continue;
+        d.w[i] = d.w[--d.nw];
+        if (!bpi) continue;                   // a backward rewrites the workspace: whatever was there is gone
+        DH_REQUIRE(e.rows == rows && e.rows_per_image == rows_per_image && e.mlp == mlp && (!covered || e.bpi == *bpi),
+                   "decoder_stack_bwd_finalize: the workspace was written by a backward of %ld rows, %d per image, mlp %d, %d blocks per image",
+                   e.rows, e.rows_per_image, e.mlp, e.bpi);
+        *bpi = e.bpi;
+        covered += e.layers;
     }
+    DH_REQUIRE(!covered || covered == layers, "decoder_stack_bwd_finalize: a re-planned launch wrote %d of the workspace's %d layers", covered, layers);
     return 0;
 }
-// Longest workgroups FIRST: the workgroups of a launch are dispatched in index order, and a workgroup of a layer-fused stack
-// runs depth x (rows per workgroup / 64) sub-tile rounds back to back -- DAHiTra's 64 x 64 level: 4 layers x 8 sub-tiles, ~140 us
-// of the backward, against 8 rounds for the other two levels.  Recorded in the order the levels run (16 x 16 first) the long
-// workgroups started only when the short ones had drained and set the launch's length by themselves: 285 us for ~190 us of work.
-static void dec_sort_jobs(DecMulti& m, int n) {
-    if (getenv("DAHITRA_DEC_NO_SORT")) return;
-    int nblk[DEC_MAXJ];
-    for (int j = 0; j < n; ++j) nblk[j] = m.first[j + 1] - m.first[j];
-    for (int i = 1; i < n; ++i)                      // insertion sort, stable: n <= 4
-        for (int j = i; j > 0; --j) {
-            const long wa = (long)(m.a[j].depth > 1 ? m.a[j].depth : 1) * m.a[j].upb;
-            const long wb = (long)(m.a[j - 1].depth > 1 ? m.a[j - 1].depth : 1) * m.a[j - 1].upb;
-            if (wa <= wb) break;
-            const DecArgs t = m.a[j]; m.a[j] = m.a[j - 1]; m.a[j - 1] = t;
-            const int tb = nblk[j]; nblk[j] = nblk[j - 1]; nblk[j - 1] = tb;
-        }
-    m.first[0] = 0;
-    for (int j = 0; j < n; ++j) m.first[j + 1] = m.first[j] + nblk[j];
+// a backward is about to write its per-layer workspaces from a.partial on in blocks of `bpi` per image
+static int dec_note_written(const DecArgs& a, int mlp, int bpi) {
+    DecBatch& d = g_db;
+    const int layers = a.depth > 1 ? a.depth : 1;
+    (void)dec_take_written(a.partial, layers, a.rows, a.rows_per_image, mlp, nullptr);
+    if (bpi == dec_default(true, a.rows, a.rows_per_image, mlp).bpi) return 0;
+    DH_REQUIRE(d.nw < DEC_MAXWRITTEN, "decoder_batch: %d re-planned backward launches wait for their dh_decoder_stack_bwd_finalize (at most %d)",
+               d.nw + 1, DEC_MAXWRITTEN);
+    d.w[d.nw++] = DecWritten{a.partial, layers, a.rows, a.rows_per_image, mlp, bpi};
+    return 0;
 }
+
 static int dec_batch_flush(hipStream_t st) {
     DecBatch& d = g_db;
-    static bool m32 = false, m64 = false, s32 = false, s64 = false;
-    for (int k = 0; k < 4; ++k) {
-        if (d.nf[k]) dec_balance(d.f[k], d.nf[k], false, k & 1 ? 64 : 32, dec_cus());
-        if (d.nb[k]) dec_balance(d.b[k], d.nb[k], true, k & 1 ? 64 : 32, dec_cus());
-        if (d.nf[k] > 1) dec_sort_jobs(d.f[k], d.nf[k]);
-        if (d.nb[k] > 1) dec_sort_jobs(d.b[k], d.nb[k]);
-        if (d.nf[k]) {
-            d.f[k].n = d.nf[k];
-            const int total = d.f[k].first[d.nf[k]];
-            if (k == 0) hipLaunchKernelGGL((dec_fwd_multi_kernel<32, false>), dim3(total), dim3(256), 0, st, d.f[k]);
-            else if (k == 1) hipLaunchKernelGGL((dec_fwd_multi_kernel<64, false>), dim3(total), dim3(256), 0, st, d.f[k]);
-            else if (k == 2) hipLaunchKernelGGL((dec_fwd_multi_kernel<32, true>), dim3(total), dim3(256), 0, st, d.f[k]);
-            else hipLaunchKernelGGL((dec_fwd_multi_kernel<64, true>), dim3(total), dim3(256), 0, st, d.f[k]);
-            d.nf[k] = 0;
-        }
-        if (d.nb[k]) {
-            d.b[k].n = d.nb[k];
-            const int total = d.b[k].first[d.nb[k]];
-            if (k == 0) {
-                if (dec_set_bwd_lds<32>(reinterpret_cast<const void*>(dec_bwd_multi_kernel<32, false>), m32)) return 1;
-                hipLaunchKernelGGL((dec_bwd_multi_kernel<32, false>), dim3(total), dim3(256), bwd_lds_bytes<32>(), st, d.b[k]);
-            } else if (k == 1) {
-                if (dec_set_bwd_lds<64>(reinterpret_cast<const void*>(dec_bwd_multi_kernel<64, false>), m64)) return 1;
-                hipLaunchKernelGGL((dec_bwd_multi_kernel<64, false>), dim3(total), dim3(256), bwd_lds_bytes<64>(), st, d.b[k]);
-            } else if (k == 2) {
-                if (dec_set_bwd_lds<32>(reinterpret_cast<const void*>(dec_bwd_multi_kernel<32, true>), s32)) return 1;
-                hipLaunchKernelGGL((dec_bwd_multi_kernel<32, true>), dim3(total), dim3(256), bwd_lds_bytes<32>(), st, d.b[k]);
-            } else {
-                if (dec_set_bwd_lds<64>(reinterpret_cast<const void*>(dec_bwd_multi_kernel<64, true>), s64)) return 1;
-                hipLaunchKernelGGL((dec_bwd_multi_kernel<64, true>), dim3(total), dim3(256), bwd_lds_bytes<64>(), st, d.b[k]);
+    for (int k = 0; k < 4; ++k)
+        for (int bwd = 0; bwd < 2; ++bwd) {
+            DecMulti& m = bwd ? d.b[k] : d.f[k];
+            int& n = bwd ? d.nb[k] : d.nf[k];
+            if (!n) continue;
+            const DecMulti rec = m;
+            DecShape s[DEC_MAXJ];
+            for (int j = 0; j < n; ++j) s[j] = DecShape{rec.a[j].rows, rec.a[j].rows_per_image, rec.a[j].depth > 1 ? rec.a[j].depth : 1};
+            const DecLaunchPlan p = dec_plan_launch(bwd, k >= 2, k & 1 ? 64 : 32, true, n, s, dec_cus());
+            m.n = n;
+            for (int j = 0; j < n; ++j) {
+                m.a[j] = rec.a[p.job[j].src];
+                m.a[j].upb = p.job[j].upb;
+                m.a[j].bpi = p.job[j].bpi;
+                m.first[j] = p.job[j].first;
+                if (bwd && dec_note_written(m.a[j], p.mlp, p.job[j].bpi)) return 1;
             }
-            d.nb[k] = 0;
+            m.first[n] = p.grid;
+            if (dec_launch(p, nullptr, &m, st)) return 1;
+            n = 0;
         }
-    }
     for (int k = 0; k < 2; ++k)
         if (d.nfin[k]) {
-            d.fin[k].n = d.nfin[k];
-            for (int j = 0; j < d.nfin[k]; ++j) {        // the blocks the backward launch of this workspace wrote (dec_balance)
-                FinArgs& fa = d.fin[k].a[j];
-                const int images = d.fin[k].gy[j] - 1;
-                const auto it = g_bwd_plan.find(fa.partial);
-                if (it != g_bwd_plan.end()) { fa.bpi = it->second.bpi; fa.nblk = images * fa.bpi; }
+            FinMulti& fm = d.fin[k];
+            fm.n = d.nfin[k];
+            fm.first[0] = 0;
+            for (int j = 0; j < fm.n; ++j) {        // the blocks the backward launch of this workspace wrote (dec_plan_launch)
+                const DecFinJob& fj = d.finjob[k][j];
+                int bpi;
+                if (dec_take_written(fm.a[j].partial, fj.depth, fj.rows, fj.rows_per_image, k ? 64 : 32, &bpi)) return 1;
+                const FinGeom g = dec_fin_geom(fj.rows, fj.rows_per_image, k ? 64 : 32, fj.depth, bpi);
+                dec_fin_fill(fm.a[j], g, bpi);
+                fm.gx[j] = g.gx; fm.gy[j] = 1 + g.images; fm.depth[j] = fj.depth;
+                fm.first[j + 1] = fm.first[j] + g.grid;
             }
-            const int total = d.fin[k].first[d.nfin[k]];
-            if (k == 0) hipLaunchKernelGGL(dec_bwd_finalize_multi_kernel<32>, dim3(total), dim3(256), 0, st, d.fin[k]);
-            else hipLaunchKernelGGL(dec_bwd_finalize_multi_kernel<64>, dim3(total), dim3(256), 0, st, d.fin[k]);
+            if (k == 0) hipLaunchKernelGGL(dec_bwd_finalize_multi_kernel<32>, dim3(fm.first[fm.n]), dim3(256), 0, st, fm);
+            else hipLaunchKernelGGL(dec_bwd_finalize_multi_kernel<64>, dim3(fm.first[fm.n]), dim3(256), 0, st, fm);
             d.nfin[k] = 0;
         }
     DH_CHECK_LAUNCH("decoder_batch");
-    return 0;
-}
-static int dec_batch_record(DecMulti* m, int* n, const DecArgs& a, int nblk, hipStream_t st) {
-    // (no flush on overflow: a recorded stack launch may depend on a recorded operand preparation of tokens.hip that only
-    // dh_xprep_batch_launch_fwd issues first -- more than DEC_MAXJ independent stacks per round is an error, not a reorder)
-    DH_REQUIRE(*n < DEC_MAXJ, "decoder_batch: more than %d stacks recorded in one round (dh_decoder_batch_launch first)", DEC_MAXJ);
-    if (*n == 0) m->first[0] = 0;
-    m->a[*n] = a;
-    m->first[*n + 1] = m->first[*n] + nblk;
-    ++*n;
     return 0;
 }
 
 static int check_common(long rows, int rows_per_image, int mlp) {
     DH_REQUIRE(mlp == 32 || mlp == 64, "decoder_fused: mlp_dim must be 32 or 64, got %d", mlp);
     DH_REQUIRE(rows_per_image % 128 == 0 && rows % rows_per_image == 0, "decoder_fused: rows per image (%d) must be a multiple of 128", rows_per_image);
+    return 0;
+}
+static int check_depth(const char* who, int depth, bool pointers) {
+    DH_REQUIRE(depth >= 1 && depth <= DEC_MAXDEPTH && pointers, "%s: bad arguments (depth %d, 1 .. %d supported)", who, depth, DEC_MAXDEPTH);
+    return 0;
+}
+static int check_jobs(int n) {
+    // (no flush on overflow: a recorded stack launch may depend on a recorded operand preparation of tokens.hip that only
+    // dh_xprep_batch_launch_fwd issues first -- more than DEC_MAXJ independent stacks per round is an error, not a reorder)
+    DH_REQUIRE(n < DEC_MAXJ, "decoder_batch: more than %d stacks recorded in one round (dh_decoder_batch_launch first)", DEC_MAXJ);
+    return 0;
+}
+
+// The arguments of the four entry points (layer / stack x forward / backward) as the kernels take them; depth 0: a single
+// layer.  upb / bpi come from the launch's plan.
+static DecArgs dec_args(const void* x, const void* ys, const void* dy, void* y, void* dwork, const void* kq, const void* voT, const void* vo,
+                        const void* kqT, const float* ln1_g, const float* ln1_b, const float* bo, const float* ln2_g, const float* ln2_b,
+                        const void* w1, const void* w1T, const float* b1, const void* w2, const void* w2T, const float* b2, int depth,
+                        long kq_lstride, long w_lstride, long par_lstride, long rows, int rows_per_image, int mlp, float eps, void* workspace) {
+    DecArgs a = {};
+    a.x = (const bf16*)x; a.ys = (bf16*)const_cast<void*>(ys); a.dy = (const bf16*)dy; a.y = (bf16*)y; a.dwork = (bf16*)dwork;
+    a.kq = (const bf16*)kq; a.voT = (const bf16*)voT; a.vo = (const bf16*)vo; a.kqT = (const bf16*)kqT;
+    a.w1 = (const bf16*)w1; a.w2 = (const bf16*)w2; a.w1T = (const bf16*)w1T; a.w2T = (const bf16*)w2T;
+    a.g1 = ln1_g; a.be1 = ln1_b; a.bo = bo; a.g2 = ln2_g; a.be2 = ln2_b; a.fb1 = b1; a.fb2 = b2;
+    a.partial = reinterpret_cast<float*>(workspace);
+    a.rows_per_image = rows_per_image; a.rows = rows; a.eps = eps;
+    if (depth) {
+        a.depth = depth; a.act_ls = rows * D; a.kq_ls = kq_lstride; a.w_ls = w_lstride; a.par_ls = par_lstride;
+        if (workspace) a.part_ls = dec_layer_floats(rows, rows_per_image, mlp);
+    }
+    return a;
+}
+// One call of an entry point: recorded into the open batch, or planned (an eager launch always takes the default plan, so an
+// older record of its workspace is dropped) and launched
+static int dec_issue(const char* who, bool bwd, bool stack, int mlp, DecArgs a, bool record, hipStream_t st) {
+    if (record) {
+        const int k = (mlp == 64) + 2 * stack;
+        DecMulti& m = bwd ? g_db.b[k] : g_db.f[k];
+        int& n = bwd ? g_db.nb[k] : g_db.nf[k];
+        if (check_jobs(n)) return 1;
+        m.a[n++] = a;
+        return 0;
+    }
+    const DecShape s = {a.rows, a.rows_per_image, a.depth > 1 ? a.depth : 1};
+    const DecLaunchPlan p = dec_plan_launch(bwd, stack, mlp, false, 1, &s, 0);
+    a.upb = p.job[0].upb; a.bpi = p.job[0].bpi;
+    if (bwd && dec_note_written(a, mlp, a.bpi)) return 1;
+    if (dec_launch(p, &a, nullptr, st)) return 1;
+    DH_CHECK_LAUNCH(who);
+    return 0;
+}
+static int dec_fin_launch(const char* who, FinArgs fa, int depth, long rows, int rows_per_image, int mlp, int bpi, hipStream_t st) {
+    const FinGeom g = dec_fin_geom(rows, rows_per_image, mlp, depth, bpi);
+    dec_fin_fill(fa, g, bpi);
+    if (mlp == 64) hipLaunchKernelGGL(dec_bwd_finalize_kernel<64>, dim3(g.grid), dim3(256), 0, st, fa, g.gx, g.images, depth);
+    else hipLaunchKernelGGL(dec_bwd_finalize_kernel<32>, dim3(g.grid), dim3(256), 0, st, fa, g.gx, g.images, depth);
+    DH_CHECK_LAUNCH(who);
     return 0;
 }
 
@@ -1232,38 +1375,22 @@ extern "C" int dh_decoder_layer_fwd(const void* x, void* y, const void* kq, cons
                                     const void* w1, const float* b1, const void* w2, const float* b2, long rows,
                                     int rows_per_image, int mlp, float eps, void* stream) {
     if (check_common(rows, rows_per_image, mlp)) return 1;
-    DecArgs a = {};
-    a.x = (const bf16*)x; a.y = (bf16*)y; a.kq = (const bf16*)kq; a.voT = (const bf16*)voT;
-    a.w1 = (const bf16*)w1; a.w2 = (const bf16*)w2;
-    a.g1 = ln1_g; a.be1 = ln1_b; a.bo = bo; a.g2 = ln2_g; a.be2 = ln2_b; a.fb1 = b1; a.fb2 = b2;
-    a.rows_per_image = rows_per_image; a.rows = rows; a.eps = eps;
-    const DecPlan pl = dec_fwd_default(rows, rows_per_image);
-    a.upb = pl.upb; a.bpi = pl.bpi;
-    const int grid = (int)(rows / rows_per_image) * pl.bpi;
-    if (g_db.on) return dec_batch_record(&g_db.f[mlp == 64], &g_db.nf[mlp == 64], a, grid, ST(stream));
-    if (mlp == 64) hipLaunchKernelGGL(dec_fwd_kernel<64>, dim3(grid), dim3(256), 0, ST(stream), a);
-    else hipLaunchKernelGGL(dec_fwd_kernel<32>, dim3(grid), dim3(256), 0, ST(stream), a);
-    DH_CHECK_LAUNCH("decoder_layer_fwd");
-    return 0;
+    const DecArgs a = dec_args(x, nullptr, nullptr, y, nullptr, kq, voT, nullptr, nullptr, ln1_g, ln1_b, bo, ln2_g, ln2_b, w1, nullptr, b1, w2, nullptr,
+                               b2, 0, 0, 0, 0, rows, rows_per_image, mlp, eps, nullptr);
+    return dec_issue("decoder_layer_fwd", false, false, mlp, a, g_db.on, ST(stream));
 }
 
 // Batched decoder layers: between dh_decoder_batch_begin() and _end(), dh_decoder_layer_fwd and the data-gradient-only form of
 // dh_decoder_layer_bwd (dw1 == NULL: partials left for dh_decoder_stack_bwd_finalize) only RECORD their launch (up to 4 per
-// direction and MLP width; a fifth issues the first four); dh_decoder_batch_launch(stream) issues the recorded layers of
+// direction and MLP width; a fifth is an error); dh_decoder_batch_launch(stream) issues the recorded layers of
 // INDEPENDENT stacks as one launch per direction and width.  Every buffer of a recorded call stays alive and unchanged until
-// then.  Per host thread; _abort drops the recorded calls.
+// then.  Per host thread; _abort drops the recorded calls and the remembered plans of re-planned backward launches.
 static void dec_batch_clear() { for (int k = 0; k < 4; ++k) g_db.nf[k] = g_db.nb[k] = 0; g_db.nfin[0] = g_db.nfin[1] = 0; }
 extern "C" int dh_decoder_batch_begin() { g_db.on = true; dec_batch_clear(); return 0; }
 extern "C" int dh_decoder_batch_pending() { int n = g_db.nfin[0] + g_db.nfin[1]; for (int k = 0; k < 4; ++k) n += g_db.nf[k] + g_db.nb[k]; return n; }
 extern "C" int dh_decoder_batch_launch(void* stream) { return dec_batch_flush(ST(stream)); }
 extern "C" int dh_decoder_batch_end(void* stream) { const int rc = dec_batch_flush(ST(stream)); g_db.on = false; return rc; }
-extern "C" int dh_decoder_batch_abort() { g_db.on = false; dec_batch_clear(); return 0; }
-
-extern "C" long dh_decoder_layer_bwd_workspace_size(long rows, int rows_per_image, int mlp) {
-    // (sized for the smallest block a re-planned launch may use, dec_balance: up to twice the default plan's blocks)
-    const long nblk = (rows / rows_per_image) * dec_plan(rows_per_image, dec_bwd_min_upb(rows, rows_per_image, mlp)).bpi;
-    return nblk * (mlp == 64 ? PL<64>::SIZE : PL<32>::SIZE) * 4;
-}
+extern "C" int dh_decoder_batch_abort() { g_db.on = false; dec_batch_clear(); g_db.nw = 0; return 0; }
 
 // dw1 == NULL: only the data-gradient launch runs and the per-workgroup partials stay in `workspace` -- the caller sums the
 // partials of all layers of a decoder stack with ONE dh_decoder_stack_bwd_finalize launch (32 finalize launches of 5.6 us sat on
@@ -1278,53 +1405,12 @@ extern "C" int dh_decoder_layer_bwd(const void* x, const void* dy, void* dx, con
                                     float* dln1_b, float* dln2_g, float* dln2_b, float* dkq, float* dvoT, long rows,
                                     int rows_per_image, int mlp, float eps, void* workspace, void* stream) {
     if (check_common(rows, rows_per_image, mlp)) return 1;
-    DecArgs a = {};
-    a.x = (const bf16*)x; a.dy = (const bf16*)dy; a.y = (bf16*)dx;
-    a.kq = (const bf16*)kq; a.voT = (const bf16*)voT; a.vo = (const bf16*)vo; a.kqT = (const bf16*)kqT;
-    a.w1 = (const bf16*)w1; a.w2 = (const bf16*)w2; a.w1T = (const bf16*)w1T; a.w2T = (const bf16*)w2T;
-    a.g1 = ln1_g; a.be1 = ln1_b; a.bo = bo; a.g2 = ln2_g; a.be2 = ln2_b; a.fb1 = b1; a.fb2 = b2;
-    a.partial = reinterpret_cast<float*>(workspace);
-    a.rows_per_image = rows_per_image; a.rows = rows; a.eps = eps;
-    const DecPlan pl = dec_bwd_default(rows, rows_per_image, mlp);
-    a.upb = pl.upb; a.bpi = pl.bpi;
-    const int images = (int)(rows / rows_per_image);
-    const int bpi = pl.bpi, nblk = images * bpi;
-    if (g_db.on && !dw1) return dec_batch_record(&g_db.b[mlp == 64], &g_db.nb[mlp == 64], a, nblk, ST(stream));
-    dec_remember_plan(a.partial, pl);
-    static bool attr64 = false, attr32 = false;
-    if (mlp == 64) {
-        const size_t lds = bwd_lds_bytes<64>();
-        if (!attr64) {
-            attr64 = true;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(dec_bwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                (void)hipGetLastError();
-                DH_FAIL("decoder_layer_bwd: cannot raise dynamic LDS to %zu", lds);
-            }
-        }
-        hipLaunchKernelGGL(dec_bwd_kernel<64>, dim3(nblk), dim3(256), lds, ST(stream), a);
-        if (dw1) {
-            const FinArgs fa = {a.partial, nblk, bpi, dw1, dw2, db1, db2, dbo, dln1_g, dln1_b, dln2_g, dln2_b, dkq, dvoT, 0L, 0L, 0L};
-            const int gx = dh_cdiv(PL<64>::KQ, 32);
-            hipLaunchKernelGGL(dec_bwd_finalize_kernel<64>, dim3(fin_blocks(gx, images, 1)), dim3(256), 0, ST(stream), fa, gx, images, 1);
-        }
-    } else {
-        const size_t lds = bwd_lds_bytes<32>();
-        if (!attr32) {
-            attr32 = true;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(dec_bwd_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                (void)hipGetLastError();
-                DH_FAIL("decoder_layer_bwd: cannot raise dynamic LDS to %zu", lds);
-            }
-        }
-        hipLaunchKernelGGL(dec_bwd_kernel<32>, dim3(nblk), dim3(256), lds, ST(stream), a);
-        if (dw1) {
-            const FinArgs fa = {a.partial, nblk, bpi, dw1, dw2, db1, db2, dbo, dln1_g, dln1_b, dln2_g, dln2_b, dkq, dvoT, 0L, 0L, 0L};
-            const int gx = dh_cdiv(PL<32>::KQ, 32);
-            hipLaunchKernelGGL(dec_bwd_finalize_kernel<32>, dim3(fin_blocks(gx, images, 1)), dim3(256), 0, ST(stream), fa, gx, images, 1);
-        }
-    }
-    DH_CHECK_LAUNCH("decoder_layer_bwd");
-    return 0;
+    const DecArgs a = dec_args(x, nullptr, dy, dx, nullptr, kq, voT, vo, kqT, ln1_g, ln1_b, bo, ln2_g, ln2_b, w1, w1T, b1, w2, w2T, b2, 0, 0, 0, 0, rows,
+                               rows_per_image, mlp, eps, workspace);
+    if (dec_issue("decoder_layer_bwd", true, false, mlp, a, g_db.on && !dw1, ST(stream))) return 1;
+    if (!dw1) return 0;
+    const FinArgs fa = {a.partial, 0, 0, dw1, dw2, db1, db2, dbo, dln1_g, dln1_b, dln2_g, dln2_b, dkq, dvoT, 0L, 0L, 0L};
+    return dec_fin_launch("decoder_layer_bwd", fa, 1, rows, rows_per_image, mlp, dec_default(true, rows, rows_per_image, mlp).bpi, ST(stream));
 }
 
 // A whole decoder stack (`depth` layers of the same shapes, one set of tokens) in ONE launch per direction: see DecArgs::depth.
@@ -1337,22 +1423,10 @@ extern "C" int dh_decoder_stack_fwd(const void* x, void* ys, const void* kq, con
                                     const float* bo, const float* ln2_g, const float* ln2_b, const void* w1, const float* b1,
                                     const void* w2, const float* b2, int depth, long kq_lstride, long w_lstride, long par_lstride,
                                     long rows, int rows_per_image, int mlp, float eps, void* stream) {
-    if (check_common(rows, rows_per_image, mlp)) return 1;
-    DH_REQUIRE(depth >= 1 && depth <= DEC_MAXDEPTH && x && ys, "decoder_stack_fwd: bad arguments (depth %d, 1 .. %d supported)", depth, DEC_MAXDEPTH);
-    DecArgs a = {};
-    a.x = (const bf16*)x; a.ys = (bf16*)ys; a.y = (bf16*)ys; a.kq = (const bf16*)kq; a.voT = (const bf16*)voT;
-    a.w1 = (const bf16*)w1; a.w2 = (const bf16*)w2;
-    a.g1 = ln1_g; a.be1 = ln1_b; a.bo = bo; a.g2 = ln2_g; a.be2 = ln2_b; a.fb1 = b1; a.fb2 = b2;
-    a.rows_per_image = rows_per_image; a.rows = rows; a.eps = eps;
-    a.depth = depth; a.act_ls = rows * D; a.kq_ls = kq_lstride; a.w_ls = w_lstride; a.par_ls = par_lstride;
-    const DecPlan pl = dec_fwd_default(rows, rows_per_image);
-    a.upb = pl.upb; a.bpi = pl.bpi;
-    const int grid = (int)(rows / rows_per_image) * pl.bpi;
-    if (g_db.on) return dec_batch_record(&g_db.f[2 + (mlp == 64)], &g_db.nf[2 + (mlp == 64)], a, grid, ST(stream));
-    if (mlp == 64) hipLaunchKernelGGL((dec_fwd_kernel<64, true>), dim3(grid), dim3(256), 0, ST(stream), a);
-    else hipLaunchKernelGGL((dec_fwd_kernel<32, true>), dim3(grid), dim3(256), 0, ST(stream), a);
-    DH_CHECK_LAUNCH("decoder_stack_fwd");
-    return 0;
+    if (check_common(rows, rows_per_image, mlp) || check_depth("decoder_stack_fwd", depth, x && ys)) return 1;
+    const DecArgs a = dec_args(x, ys, nullptr, ys, nullptr, kq, voT, nullptr, nullptr, ln1_g, ln1_b, bo, ln2_g, ln2_b, w1, nullptr, b1, w2, nullptr, b2,
+                               depth, kq_lstride, w_lstride, par_lstride, rows, rows_per_image, mlp, eps, nullptr);
+    return dec_issue("decoder_stack_fwd", false, true, mlp, a, g_db.on, ST(stream));
 }
 // Data gradient of the stack: dy [rows][32] = gradient of ys[depth - 1], dx [rows][32] = gradient of x, dwork [rows][32] bf16
 // scratch (the gradient between layers, rewritten in place); the per-workgroup partial sums of layer l land in workspace +
@@ -1363,64 +1437,60 @@ extern "C" int dh_decoder_stack_bwd(const void* x, const void* ys, const void* d
                                     const float* b1, const void* w2, const void* w2T, const float* b2, int depth, long kq_lstride,
                                     long w_lstride, long par_lstride, long rows, int rows_per_image, int mlp, float eps,
                                     void* workspace, void* stream) {
-    if (check_common(rows, rows_per_image, mlp)) return 1;
-    DH_REQUIRE(depth >= 1 && depth <= DEC_MAXDEPTH && x && (ys || depth == 1) && dy && dx && (dwork || depth == 1) && workspace,
-               "decoder_stack_bwd: bad arguments (depth %d, 1 .. %d supported)", depth, DEC_MAXDEPTH);
-    DecArgs a = {};
-    a.x = (const bf16*)x; a.ys = (bf16*)const_cast<void*>(ys); a.dy = (const bf16*)dy; a.y = (bf16*)dx; a.dwork = (bf16*)dwork;
-    a.kq = (const bf16*)kq; a.voT = (const bf16*)voT; a.vo = (const bf16*)vo; a.kqT = (const bf16*)kqT;
-    a.w1 = (const bf16*)w1; a.w2 = (const bf16*)w2; a.w1T = (const bf16*)w1T; a.w2T = (const bf16*)w2T;
-    a.g1 = ln1_g; a.be1 = ln1_b; a.bo = bo; a.g2 = ln2_g; a.be2 = ln2_b; a.fb1 = b1; a.fb2 = b2;
-    a.partial = reinterpret_cast<float*>(workspace);
-    a.rows_per_image = rows_per_image; a.rows = rows; a.eps = eps;
-    const DecPlan pl = dec_bwd_default(rows, rows_per_image, mlp);
-    a.upb = pl.upb; a.bpi = pl.bpi;
-    a.depth = depth; a.act_ls = rows * D; a.kq_ls = kq_lstride; a.w_ls = w_lstride; a.par_ls = par_lstride;
-    a.part_ls = dh_decoder_layer_bwd_workspace_size(rows, rows_per_image, mlp) / 4;
-    const int nblk = (int)(rows / rows_per_image) * pl.bpi;
-    if (g_db.on) return dec_batch_record(&g_db.b[2 + (mlp == 64)], &g_db.nb[2 + (mlp == 64)], a, nblk, ST(stream));
-    dec_remember_plan(a.partial, pl);
-    static bool m32 = false, m64 = false;
-    if (mlp == 64) {
-        if (dec_set_bwd_lds<64>(reinterpret_cast<const void*>(dec_bwd_kernel<64, true>), m64)) return 1;
-        hipLaunchKernelGGL((dec_bwd_kernel<64, true>), dim3(nblk), dim3(256), bwd_lds_bytes<64>(), ST(stream), a);
-    } else {
-        if (dec_set_bwd_lds<32>(reinterpret_cast<const void*>(dec_bwd_kernel<32, true>), m32)) return 1;
-        hipLaunchKernelGGL((dec_bwd_kernel<32, true>), dim3(nblk), dim3(256), bwd_lds_bytes<32>(), ST(stream), a);
-    }
-    DH_CHECK_LAUNCH("decoder_stack_bwd");
-    return 0;
+    if (check_common(rows, rows_per_image, mlp) ||
+        check_depth("decoder_stack_bwd", depth, x && (ys || depth == 1) && dy && dx && (dwork || depth == 1) && workspace))
+        return 1;
+    const DecArgs a = dec_args(x, ys, dy, dx, dwork, kq, voT, vo, kqT, ln1_g, ln1_b, bo, ln2_g, ln2_b, w1, w1T, b1, w2, w2T, b2, depth, kq_lstride,
+                               w_lstride, par_lstride, rows, rows_per_image, mlp, eps, workspace);
+    return dec_issue("decoder_stack_bwd", true, true, mlp, a, g_db.on, ST(stream));
 }
 
 // The finalize of `depth` layers at once: partials of layer l at workspace + l * dh_decoder_layer_bwd_workspace_size bytes,
 // gradients of layer l at (pointer of layer 0) + l * grad_stride floats, dkq / dvoT of layer l at + l * images * 1024 floats.
+// It sums the blocks the last backward on that workspace wrote: the default plan's, or those of a re-planned batch launch.
 extern "C" int dh_decoder_stack_bwd_finalize(const void* workspace, int depth, long rows, int rows_per_image, int mlp, float* dw1,
                                              float* dw2, float* db1, float* db2, float* dbo, float* dln1_g, float* dln1_b,
                                              float* dln2_g, float* dln2_b, long grad_stride, float* dkq, float* dvoT, void* stream) {
     if (check_common(rows, rows_per_image, mlp)) return 1;
     DH_REQUIRE(depth >= 1 && workspace && dw1 && dkq && dvoT, "decoder_stack_bwd_finalize: bad arguments (depth %d)", depth);
-    const float* partial = reinterpret_cast<const float*>(workspace);
-    const int images = (int)(rows / rows_per_image);
-    const int bpi = dec_recall_plan(partial, rows, rows_per_image, mlp).bpi, nblk = images * bpi;
-    const long pstride = dh_decoder_layer_bwd_workspace_size(rows, rows_per_image, mlp) / 4, kstride = (long)images * 1024;
-    const FinArgs fa = {partial, nblk, bpi, dw1, dw2, db1, db2, dbo, dln1_g, dln1_b, dln2_g, dln2_b, dkq, dvoT, pstride, grad_stride, kstride};
+    const FinArgs fa = {reinterpret_cast<const float*>(workspace), 0, 0, dw1, dw2, db1, db2, dbo, dln1_g, dln1_b, dln2_g, dln2_b, dkq, dvoT, 0L, grad_stride, 0L};
     if (g_db.on) {          // recorded: issued with the other stacks' finalizes, after the recorded backward launches
-        const int k = mlp == 64, gx = dh_cdiv(mlp == 64 ? PL<64>::KQ : PL<32>::KQ, 32);
-        DH_REQUIRE(g_db.nfin[k] < DEC_MAXJ, "decoder_batch: more than %d stack finalizes recorded in one round", DEC_MAXJ);
-        FinMulti& fm = g_db.fin[k];
+        const int k = mlp == 64;
         int& n = g_db.nfin[k];
-        if (n == 0) fm.first[0] = 0;
-        fm.a[n] = fa; fm.gx[n] = gx; fm.gy[n] = 1 + images; fm.depth[n] = depth;
-        fm.first[n + 1] = fm.first[n] + fin_blocks(gx, images, depth);
-        ++n;
+        DH_REQUIRE(n < DEC_MAXJ, "decoder_batch: more than %d stack finalizes recorded in one round", DEC_MAXJ);
+        g_db.fin[k].a[n] = fa;
+        g_db.finjob[k][n++] = DecFinJob{depth, rows_per_image, rows};
         return 0;
     }
-    if (mlp == 64)
-        hipLaunchKernelGGL(dec_bwd_finalize_kernel<64>, dim3(fin_blocks(dh_cdiv(PL<64>::KQ, 32), images, depth)), dim3(256), 0, ST(stream), fa,
-                           dh_cdiv(PL<64>::KQ, 32), images, depth);
-    else
-        hipLaunchKernelGGL(dec_bwd_finalize_kernel<32>, dim3(fin_blocks(dh_cdiv(PL<32>::KQ, 32), images, depth)), dim3(256), 0, ST(stream), fa,
-                           dh_cdiv(PL<32>::KQ, 32), images, depth);
-    DH_CHECK_LAUNCH("decoder_stack_bwd_finalize");
+    int bpi;
+    if (dec_take_written(fa.partial, depth, rows, rows_per_image, mlp, &bpi)) return 1;
+    return dec_fin_launch("decoder_stack_bwd_finalize", fa, depth, rows, rows_per_image, mlp, bpi, ST(stream));
+}
+
+// Host only: the plan of one launch (include/dahitra_hip.h has the layout of `out`)
+extern "C" int dh_decoder_plan_describe(int backward, int stack, int mlp, int batch_open, int njobs, const long* rows, const int* rows_per_image,
+                                        const int* depth, int cus, long* out) {
+    DH_REQUIRE(njobs >= 1 && rows && rows_per_image && depth && out, "decoder_plan_describe: bad arguments (%d jobs)", njobs);
+    DH_REQUIRE(batch_open || njobs == 1, "decoder_plan_describe: an eager launch is one job, got %d", njobs);
+    DecShape s[DEC_MAXJ];
+    for (int j = 0; j < njobs; ++j) {
+        if (check_jobs(j) || check_common(rows[j], rows_per_image[j], mlp)) return 1;
+        if (stack && check_depth(backward ? "decoder_stack_bwd" : "decoder_stack_fwd", depth[j], true)) return 1;
+        s[j] = DecShape{rows[j], rows_per_image[j], stack && depth[j] > 1 ? depth[j] : 1};
+    }
+    const DecLaunchPlan p = dec_plan_launch(backward, stack, mlp, batch_open, njobs, s, cus);
+    for (int i = 0; i < 41; ++i) out[i] = 0;
+    out[0] = (mlp == 64) + 2 * p.stack + 4 * p.multi;
+    out[1] = p.grid; out[2] = p.threads; out[3] = (long)p.lds; out[4] = p.n;
+    for (int j = 0; j < p.n; ++j) {
+        const DecJobPlan& jp = p.job[j];
+        long* o = out + 5 + 5 * j;
+        o[0] = jp.src; o[1] = jp.upb; o[2] = jp.bpi; o[3] = jp.first; o[4] = jp.blocks;
+        if (!backward) continue;
+        const int layers = depth[jp.src] > 1 ? depth[jp.src] : 1;
+        const FinGeom g = dec_fin_geom(rows[jp.src], rows_per_image[jp.src], mlp, layers, jp.bpi);
+        o = out + 25 + 4 * j;
+        o[0] = g.pstride * 4; o[1] = g.nblk; o[2] = jp.bpi; o[3] = g.grid;
+    }
     return 0;
 }

@@ -625,10 +625,14 @@ int dh_decoder_layer_bwd(const void* x, const void* dy, void* dx, const void* kq
  * [rows][32] bf16 scratch; partials of layer l at workspace + l * dh_decoder_layer_bwd_workspace_size bytes, for
  * dh_decoder_stack_bwd_finalize.  Bit-identical to `depth` dh_decoder_layer_fwd / _bwd calls; both join an open decoder batch.
  * depth <= 8 (a workgroup keeps every layer's parameter vectors in LDS).  A launch of SEVERAL recorded jobs sizes the pixel
- * blocks of each for the launch as a whole (csrc/decoder_fused.hip dec_balance; DAHITRA_DEC_BALANCE=0: the per-job rule): y / dx
+ * blocks of each for the launch as a whole (csrc/decoder_fused.hip dec_plan_launch; DAHITRA_DEC_BALANCE=0: the per-job rule): y / dx
  * do not depend on it, the partial sums -- hence the parameter gradients -- to fp32 summation order.  The workspace of
- * dh_decoder_layer_bwd_workspace_size holds the smallest blocks such a launch may choose (only the blocks written are read);
- * the finalize looks the layout up by the workspace's address, so it must follow the backward that filled that workspace. */
+ * dh_decoder_layer_bwd_workspace_size holds the smallest blocks such a launch may choose (only the blocks written are read).
+ * The finalize of a workspace sums exactly the blocks the LAST backward on it wrote, or fails: an eager backward always writes
+ * the default plan's blocks (a function of rows, rows_per_image and mlp alone); a batch launch that chose others keeps them,
+ * per host thread, until that workspace's finalize (on the same thread, eager or recorded, in that round or a later one)
+ * takes them, a later backward on the workspace replaces them, or dh_decoder_batch_abort drops them.  At most 64 such
+ * launches may wait for their finalize; a finalize whose rows, rows_per_image or mlp differ from its backward's is refused. */
 int dh_decoder_stack_fwd(const void* x, void* ys, const void* kq, const void* voT, const float* ln1_g, const float* ln1_b,
                          const float* bo, const float* ln2_g, const float* ln2_b, const void* w1, const float* b1, const void* w2,
                          const float* b2, int depth, long kq_lstride, long w_lstride, long par_lstride, long rows,
@@ -645,6 +649,19 @@ int dh_decoder_stack_bwd_finalize(const void* workspace, int depth, long rows, i
                                   float* db1, float* db2, float* dbo, float* dln1_g, float* dln1_b, float* dln2_g, float* dln2_b,
                                   long grad_stride, float* dkq, float* dvoT, void* stream);
 long dh_decoder_layer_bwd_workspace_size(long rows, int rows_per_image, int mlp);
+/* Host only (no launch, no device): the plan of ONE fused-decoder launch on a device of `cus` compute units.  backward: 0
+ * dh_decoder_layer_fwd / _stack_fwd, 1 _layer_bwd / _stack_bwd; stack: the layer-fused form; batch_open: the njobs (<= 4) calls
+ * recorded between dh_decoder_batch_begin and _launch, else one eager call (njobs == 1).  Job j has rows[j] pixel rows,
+ * rows_per_image[j] and (stacks) depth[j] layers.  out[41], unused fields 0:
+ *   [0]          kernel: (mlp == 64) + 2 * stack + 4 * (the multi-job form, which every launch of a batch takes)
+ *   [1..4]       grid, threads, dynamic LDS bytes, jobs
+ *   [5 + 5 j..]  job j in ISSUE order: its index as given, upb (64-row units per workgroup), bpi (workgroups per image), first
+ *                workgroup, workgroups
+ *   [25 + 4 j..] backward, the same job: bytes of one layer's workspace (dh_decoder_layer_bwd_workspace_size), and the nblk, bpi
+ *                and grid of its dh_decoder_stack_bwd_finalize over max(depth[j], 1) layers
+ * Returns non-zero, with dh_last_error set, where the calls themselves would be refused. */
+int dh_decoder_plan_describe(int backward, int stack, int mlp, int batch_open, int njobs, const long* rows, const int* rows_per_image,
+                             const int* depth, int cus, long* out);
 
 /* ---- loss, mask, optimizer (models/losses.py:106-196; trainer.py:39-40,170) ------------------- */
 int dh_focal_loss(const float* logits_nchw, const long long* target, int B, int C, long HW, float alpha,

@@ -2076,6 +2076,92 @@ def test_decoder_stack_in_one_launch_equals_layer_by_layer(ops, cfg):
     assert torch.equal(part, part_ref)
 
 
+def test_decoder_stacks_replanned_in_a_batch_and_finalized_in_the_next_round(ops):
+    """The path the DAHiTra step takes: the stack backwards of three independent levels recorded, re-planned as one launch
+    (csrc/decoder_fused.hip dec_plan_launch: the small levels get larger blocks than their own rule gives them) and launched; their
+    finalizes recorded in the NEXT round, where each must sum exactly the blocks its backward wrote.  Against the same calls
+    outside a batch: dx bit for bit, the gradients to fp32 summation order (1e-5 of the largest, as for the batched partials
+    above).  The workspaces start as NaN, so a finalize that read a block nobody wrote would show.  Repeated on the same
+    workspaces the batched pass gives the same bits (the recorded step replays exactly that), and an eager backward on a
+    workspace a batch wrote forgets that batch's blocks."""
+    import ctypes
+    from dahitra_amd import _lib
+    L = _lib.lib()
+    D, dt, depth = 32, torch.bfloat16, 2
+    cases = [(16, 4096, 32), (16, 1024, 32), (16, 256, 32), (3, 512, 64)]          # images, rows per image, mlp (the last: its own launch)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def bpis(batch, jobs):
+        n, out = len(jobs), (ctypes.c_long * 41)()
+        assert L.dh_decoder_plan_describe(1, 1, 32, batch, n, (ctypes.c_long * n)(*(im * rpi for im, rpi, _ in jobs)),
+                                          (ctypes.c_int * n)(*(rpi for _, rpi, _ in jobs)), (ctypes.c_int * n)(*[depth] * n), cus, out) == 0
+        return {out[5 + 5 * j]: out[7 + 5 * j] for j in range(n)}
+    together = bpis(1, cases[:3])
+    alone = {j: bpis(0, [c])[0] for j, c in enumerate(cases[:3])}
+    if together == alone:
+        pytest.fail("at %d CUs the batch keeps every job's own plan %s: the test would not see a re-planned finalize" % (cus, alone))
+
+    class Stack:
+        pass
+    data = []
+    for k, (images, rpi, mlp) in enumerate(cases):
+        g = torch.Generator(device="cuda").manual_seed(4100 + k)
+        rn = lambda *s, sc=1.0: torch.randn(*s, device="cuda", generator=g) * sc
+        rows = images * rpi
+        st = Stack()
+        st.layers = depth
+        kq, voT = rn(depth, images, 32, D, sc=0.3), rn(depth, images, D, 32, sc=0.3)
+        st.kq, st.voT = kq.to(dt), voT.to(dt)
+        st.vo, st.kqT = voT.transpose(2, 3).contiguous().to(dt), kq.transpose(2, 3).contiguous().to(dt)
+        PS = 7 * D + 2 * mlp + 5
+        arena = rn(depth, PS, sc=0.1)
+        arena[:, 0:D] += 1.0
+        arena[:, 3 * D:4 * D] += 1.0
+        params0 = tuple(arena[0, o:o + n] for o, n in ((0, D), (D, D), (2 * D, D), (3 * D, D), (4 * D, D), (5 * D, mlp), (5 * D + mlp, D)))
+        w1, w2 = rn(depth, mlp, D, sc=D ** -0.5), rn(depth, D, mlp, sc=mlp ** -0.5)
+        ws = (w1.to(dt).contiguous(), w1.transpose(1, 2).contiguous().to(dt), w2.to(dt).contiguous(), w2.transpose(1, 2).contiguous().to(dt))
+        x, dy = rn(rows, D).to(dt), rn(rows, D).to(dt)
+        ys = ops.decoder_stack_fwd(x, st, rpi, params0, ws[0], ws[2], PS, mlp)
+        part = torch.full((depth, ops.decoder_layer_bwd_partial_floats(rows, rpi, mlp)), float("nan"), dtype=torch.float32, device="cuda")
+        data.append((x, ys, dy, st, rpi, params0, ws, PS, mlp, part, images))
+    sizes = lambda mlp: (mlp * D, D * mlp, mlp, D, D, D, D, D, D)             # dw1, dw2, db1, db2, dbo, dln1_g / b, dln2_g / b
+
+    def run(batched, finalize=True):
+        grads = [torch.zeros(depth, sum(sizes(d[8])) + 3, device="cuda") for d in data]
+        dkv = [(torch.empty(depth, d[10], 32, 32, device="cuda"), torch.empty(depth, d[10], 32, 32, device="cuda")) for d in data]
+        with ops.EncoderBatch(decoder=batched) as eb:
+            dxs = [ops.decoder_stack_bwd(x, ys, dy, st, rpi, params0, ws[0], ws[1], ws[2], ws[3], PS, mlp, part)
+                   for (x, ys, dy, st, rpi, params0, ws, PS, mlp, part, images) in data]
+            assert L.dh_decoder_batch_pending() == (4 if batched else 0)
+            eb.launch()
+            if finalize:
+                for (x, ys, dy, st, rpi, params0, ws, PS, mlp, part, images), gr, (dkq, dvoT) in zip(data, grads, dkv):
+                    offs = np.cumsum((0,) + sizes(mlp))
+                    ops.decoder_stack_bwd_finalize(part, x.shape[0], rpi, mlp, tuple(gr[0, a:b] for a, b in zip(offs[:-1], offs[1:])), gr.shape[1], dkq, dvoT)
+                assert L.dh_decoder_batch_pending() == (4 if batched else 0)
+                eb.launch()
+        torch.cuda.synchronize()
+        each = [gr[l, a:b] for d, gr in zip(data, grads) for l in range(depth)               # every parameter's gradient by itself
+                for a, b in zip(np.cumsum((0,) + sizes(d[8]))[:-1], np.cumsum(sizes(d[8])))]
+        return dxs, each + [t for pair in dkv for t in pair]
+    ref, got, again = run(False), run(True), run(True)
+    for a, b, c in zip(ref[0], got[0], again[0]):
+        assert torch.equal(a, b) and torch.equal(a, c)
+    for i, (a, b, c) in enumerate(zip(ref[1], got[1], again[1])):
+        s = float(a.abs().max())
+        assert s > 0 and torch.isfinite(b).all()
+        assert float((a - b).abs().max()) <= 1e-5 * s, (i, float((a - b).abs().max()), s)
+        assert torch.equal(b, c), "the repeated batched pass differs (tensor %d)" % i
+    run(True, finalize=False)              # a batch's blocks, never finalized: a finalize of another shape is refused, not guessed ...
+    x, rpi, part = data[1][0], data[1][4], data[1][9]
+    gr, kv = torch.zeros(depth, sum(sizes(32)), device="cuda"), torch.empty(depth, 32, 32, 32, device="cuda")
+    offs = np.cumsum((0,) + sizes(32))
+    with pytest.raises(_lib.HipLibraryError, match="was written by a backward of"):
+        ops.decoder_stack_bwd_finalize(part, 2 * x.shape[0], rpi, 32, tuple(gr[0, a:b] for a, b in zip(offs[:-1], offs[1:])), gr.shape[1], kv, kv.clone())
+    eager = run(False)                     # ... and they are forgotten by the eager backward that rewrites the workspace
+    assert all(torch.equal(a, b) for a, b in zip(ref[1], eager[1]))
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("cfg", [dict(n=4, h=16, w=24, c=64, groups=2), dict(n=2, h=8, w=8, c=256, groups=1),
                                  dict(n=64, h=64, w=64, c=64, groups=2)])       # the last: the persistent one-launch form (bf16)
