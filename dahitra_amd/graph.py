@@ -371,6 +371,74 @@ class GraphedXbdEvalStep:
         return self.logits
 
 
+class GraphedXbdPredictStep:
+    """The prediction of one batch of pre / post pairs (xBD_code/predict_test_cls.py:62-94) as ONE HIP graph:
+    dh_xbd_tta_pack_u8 (the four flips of the normalised 6-channel image), the eval-mode forward at batch 4N and
+    dh_xbd_tta_merge_u8 (sigmoid, un-flip, float32 mean, uint8), no host read.
+
+        step = GraphedXbdPredictStep(net, pre_u8, post_u8)      # net.eval() is called here
+        msk = step(pre_u8, post_u8)                             # the static [N, H, W, 5] uint8 tensor, valid until the next replay
+
+    pre_u8, post_u8 [N, H, W, 3] uint8 on the device.  order: 'bgr' (default, the script as executed) or 'rgb', see
+    ops.xbd_tta_pack.  The shapes are static and CHECKED: a pair of another shape raises ValueError, nothing is broadcast.  The
+    parameters are read when the graph replays."""
+
+    def __init__(self, net, pre_u8, post_u8, order='bgr', warmup=2):
+        self.net, self.order = net, order
+        net.eval()
+        self.inp = ops.xbd_tta_pack(pre_u8, post_u8, order)          # validates the pair; the static input of the forward
+        self.pre, self.post = pre_u8.clone(), post_u8.clone()
+        N, H, W, _ = pre_u8.shape
+        self.out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=pre_u8.device)
+        net._ensure_arena(pre_u8.device)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self._body()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
+        ops.rekey_workspace(pre_u8.device, s, cs)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cs):
+            self.logits = self._body()
+        self._pinned = ops.pin_captured_buffers(net)
+        self._generation = net._arena.generation
+        torch.cuda.synchronize()
+
+    def _check(self, pre_u8, post_u8):
+        want = tuple(self.pre.shape)
+        for name, t in (("pre_u8", pre_u8), ("post_u8", post_u8)):
+            if not torch.is_tensor(t) or tuple(t.shape) != want or t.dtype != torch.uint8 or t.device != self.pre.device:
+                raise ValueError("GraphedXbdPredictStep: %s %s %s, the step holds uint8 %s on %s"
+                                 % (name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)), list(want), self.pre.device))
+
+    def _body(self):
+        ops.xbd_tta_pack(self.pre, self.post, self.order, out=self.inp)
+        with torch.no_grad():
+            logits = self.net(self.inp)
+        logits = logits.float().contiguous()
+        ops.xbd_tta_merge(logits, out=self.out)
+        return logits
+
+    def step(self, pre_u8=None, post_u8=None):
+        if self.net._arena.generation != self._generation:
+            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this prediction step was captured; "
+                               "build a new GraphedXbdPredictStep")
+        if self.net.training:
+            raise RuntimeError("dahitra_amd: GraphedXbdPredictStep replays the eval-mode forward; call net.eval() (a train-mode "
+                               "forward in between re-packs the weights for training)")
+        if pre_u8 is not None or post_u8 is not None:
+            self._check(pre_u8, post_u8)
+            self.pre.copy_(pre_u8, non_blocking=True)
+            self.post.copy_(post_u8, non_blocking=True)
+        self.graph.replay()
+        return self.out
+
+    __call__ = step
+
+
 class GraphedXbdStep(GraphedTrainStep):
     """The xBD step (xBD_code/train.py:331-374) as one HIP graph: forward of the 6-channel model, the five weighted
     ComboLoss terms, backward, clip_grad_norm_(0.999) and the hand-rolled AdamW.

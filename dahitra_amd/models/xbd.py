@@ -11,8 +11,10 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
     evaluate_val(data_val, best_score, model, ...)    xBD_code/train.py:293-307   (the snapshot of the best score)
         the reference reads `optimizer` and the snapshot's folder from globals; here they are arguments
     dice(im1, im2, empty_score=1.0)                   xBD_code/utils.py:124-154   as val_score's per-image term, on counts
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip + the shared model kernels); CPU tensors
-are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
+    predict_dir(model, test_dir, pred_folder)         xBD_code/predict_test_cls.py:58-97 (the 4-flip TTA loop and its files)
+        the reference reads the two folders and its list `models` from globals; here they are arguments
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip + the shared model
+kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
 import numpy as np
@@ -253,3 +255,102 @@ def evaluate_val(batches, best_score, model, optimizer, path, current_epoch, thr
         best_score = d
     print("score: {}\tscore_best: {}".format(d, best_score))
     return best_score
+
+
+# ---- prediction (xBD_code/predict_test_cls.py:58-97) --------------------------------------------------------
+def _one_model(model):
+    """the script's `models` list has one entry (predict_test_cls.py:39); an ensemble of snapshots is not on the executed path"""
+    if isinstance(model, (list, tuple)):
+        if len(model) != 1:
+            raise NotImplementedError("predict: the reference averages the flips of ONE snapshot (predict_test_cls.py:39); "
+                                      "got a list of %d models" % len(model))
+        model = model[0]
+    return model
+
+
+def _predict_step(model, pre_u8, post_u8, order):
+    """the model's recorded prediction step for this shape, order and device (kept on the model, as _eval_step does)"""
+    from ..graph import GraphedXbdPredictStep
+    steps = model.__dict__.setdefault('_xbd_predict_steps', {})
+    key = (tuple(pre_u8.shape), order, str(pre_u8.device))
+    step = steps.get(key)
+    if step is not None and step._generation != model._arena.generation:
+        step = None
+    if step is None:
+        step = steps[key] = GraphedXbdPredictStep(model, pre_u8, post_u8, order)
+    return step
+
+
+def predict_tta(model, pre_u8, post_u8, order='bgr', graph=True):
+    """The prediction of predict_test_cls.py:66-94 for a batch of pairs, on the device.  pre_u8, post_u8: [N, H, W, 3] uint8
+    RGB as a decoder stores them.  The four flips of the normalised 6-channel image go through the eval-mode model as one
+    batch of 4N; the sigmoids are flipped back, averaged in float32 in the reference's order and written as
+    uint8(mean * 255).  Returns the device tensor [N, H, W, 5] uint8, channels last, what the script saves per pair.
+    order: 'bgr' (default) is what the script executes: cv2.imread returns BGR, so the net sees each RGB triple reversed;
+    'rgb' is the order train.py's PIL loader, and this project's loader, feed the net.  A model trained through this project
+    has seen 'rgb'; the default stays with the script as written, the way validate's select='reference' does.
+    graph=True replays a GraphedXbdPredictStep recorded once per model, shape, order and device, and the returned tensor is
+    that step's static output: valid until the next call with this shape; graph=False runs the three stages eagerly into a new
+    tensor.  Both give the same bytes.  `model` may be the script's one-element list `models`; another length raises
+    NotImplementedError."""
+    model = _one_model(model)
+    if order not in ops.XBD_TTA_ORDER:
+        raise ValueError("predict_tta: order %r is not one of %s" % (order, sorted(ops.XBD_TTA_ORDER)))
+    for t in (pre_u8, post_u8):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback)")
+    model.eval()
+    if graph:
+        model._ensure_arena(pre_u8.device)          # a rebuilt arena shows here, before a stale step could be chosen
+        return _predict_step(model, pre_u8, post_u8, order).step(pre_u8, post_u8)
+    inp = ops.xbd_tta_pack(pre_u8, post_u8, order)
+    with torch.no_grad():
+        logits = model(inp)
+    return ops.xbd_tta_merge(logits.float().contiguous())
+
+
+def predict_names(f):
+    """The three file names predict_test_cls.py:95-97 writes for the pre image `f`, as written: '{0}.png'.format(f.replace(
+    '.png', '_full.png')) and np.save's own '.npy' give a doubled extension,
+        <stem>_full.png.png.npy, <stem>_part1.png.png, <stem>_part2.png.png
+    (the xBD scoring and visualize_results.py look for exactly these)."""
+    return ('{0}.png'.format(f.replace('.png', '_full.png')) + '.npy',
+            '{0}.png'.format(f.replace('.png', '_part1.png')),
+            '{0}.png'.format(f.replace('.png', '_part2.png')))
+
+
+def predict_dir(model, test_dir, pred_folder, order='bgr', graph=True):
+    """The loop of predict_test_cls.py:58-97: every name of sorted(listdir(test_dir)) that contains '_pre_' is paired with the
+    name where '_pre_' is replaced by '_post_'; a pair whose two shapes differ is skipped; each pair is predicted by predict_tta
+    and written to pred_folder (created) under predict_names(f):
+        the .npy          the [H, W, 5] uint8 array
+        the _part1 PNG    msk[..., :3]
+        the _part2 PNG    msk[..., 2:]
+    The images are decoded with PIL (RGB; order='bgr' hands the net what cv2.imread hands it in the script).  The PNGs are written
+    so that cv2.imread(..., IMREAD_UNCHANGED) returns exactly those arrays: cv2 stores and returns BGR, so the PIL image is built
+    from the channel-reversed slice.  PNG compression level 9; the pixel content is the contract, not the byte stream.
+    Returns the list of the pre names whose files were written."""
+    from PIL import Image
+    model = _one_model(model)
+    device = next(model.parameters()).device
+    if device.type != 'cuda':
+        raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback): move the model to the GPU")
+    os.makedirs(pred_folder, exist_ok=True)
+    written = []
+    for f in sorted(os.listdir(test_dir)):
+        if '_pre_' not in f:
+            continue
+        fn = os.path.join(test_dir, f)
+        img = np.array(Image.open(fn).convert('RGB'))
+        img2 = np.array(Image.open(fn.replace('_pre_', '_post_')).convert('RGB'))
+        if img.shape != img2.shape:
+            continue
+        pre, post = (torch.from_numpy(a).to(device).unsqueeze(0) for a in (img, img2))
+        msk = predict_tta(model, pre, post, order=order, graph=graph)[0].cpu().numpy()
+        full, part1, part2 = predict_names(f)
+        np.save(os.path.join(pred_folder, full), msk)
+        for name, part in ((part1, msk[..., :3]), (part2, msk[..., 2:])):
+            Image.fromarray(np.ascontiguousarray(part[..., ::-1])).save(os.path.join(pred_folder, name), format='PNG',
+                                                                        compress_level=9)
+        written.append(f)
+    return written

@@ -1901,6 +1901,65 @@ def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select=
           XBD_VAL_SELECT[select], P(image_counts), P(class_counts), S())
 
 
+# ---- xBD prediction: 4-flip test-time augmentation (csrc/xbd_predict.hip) ---------------------------------
+XBD_TTA_ORDER = {"rgb": 0, "bgr": 1}
+
+
+def _tta_tensor(what, name, t, dtype, shape_text, ok, device=None):
+    """one argument of the two calls below: ValueError, before any launch, for whatever the kernel cannot read as it lies"""
+    if not torch.is_tensor(t) or t.dtype != dtype or not ok(t):
+        raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
+                                                        str(dtype).replace("torch.", ""), shape_text))
+    if not t.is_cuda or (device is not None and t.device != device):
+        raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device" % (what, name, t.device))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
+
+
+def xbd_tta_pack(pre_u8, post_u8, order="bgr", out=None):
+    """The input batch of the reference's predictor (xBD_code/predict_test_cls.py:62-75) on the device.
+    pre_u8, post_u8 [N, H, W, 3] uint8 -> [4N, 6, H, W] float32: image 4n + k is flip_k of concat(pre_n, post_n), every byte as
+    float32(v) / 127 - 1; flip_0 identity, flip_1 rows reversed, flip_2 columns reversed, flip_3 both.
+    order: 'bgr' (default) reverses the three channels of pre and of post -- what the script executes, because cv2.imread
+    returns BGR while these sources hold RGB; 'rgb' keeps them, the order train.py's PIL loader and this project's loader feed
+    the net.  out: a [4N, 6, H, W] float32 buffer to write into.  ValueError, before any launch, for a wrong rank, dtype or
+    device, non-contiguous storage or an unknown order."""
+    if order not in XBD_TTA_ORDER:
+        raise ValueError("xbd_tta_pack: order %r is not one of %s" % (order, sorted(XBD_TTA_ORDER)))
+    _tta_tensor("xbd_tta_pack", "pre_u8", pre_u8, torch.uint8, "[N, H, W, 3]", lambda t: t.dim() == 4 and t.shape[3] == 3)
+    N, H, W, _ = pre_u8.shape
+    _tta_tensor("xbd_tta_pack", "post_u8", post_u8, torch.uint8, "[%d, %d, %d, 3] like pre_u8" % (N, H, W),
+                lambda t: t.shape == pre_u8.shape, pre_u8.device)
+    if out is None:
+        out = torch.empty(4 * N, 6, H, W, dtype=torch.float32, device=pre_u8.device)
+    else:
+        _tta_tensor("xbd_tta_pack", "out", out, torch.float32, "[%d, 6, %d, %d]" % (4 * N, H, W),
+                    lambda t: tuple(t.shape) == (4 * N, 6, H, W), pre_u8.device)
+    _call("dh_xbd_tta_pack_u8", _vp(pre_u8.data_ptr()), _vp(post_u8.data_ptr()), N, H, W, XBD_TTA_ORDER[order],
+          _vp(out.data_ptr()), S())
+    return out
+
+
+def xbd_tta_merge(logits, out=None):
+    """The merge of the reference's predictor (predict_test_cls.py:83-94) on the device.  logits [4N, 5, H, W] float32, image
+    4n + k the net's answer to flip_k -> [N, H, W, 5] uint8, channels last: sigmoid in float32, each map flipped back,
+    (((u_0 + u_1) + u_2) + u_3) / 4 in float32 in that order (numpy's mean over the stack), uint8(trunc(mean * 255)).  A NaN
+    logit gives 0.  out: a [N, H, W, 5] uint8 buffer to write into.  ValueError, before any launch, for a wrong rank, dtype or
+    device, non-contiguous storage or a batch that is no multiple of 4."""
+    _tta_tensor("xbd_tta_merge", "logits", logits, torch.float32, "[4N, 5, H, W]", lambda t: t.dim() == 4 and t.shape[1] == 5)
+    B, _, H, W = logits.shape
+    if B % 4:
+        raise ValueError("xbd_tta_merge: a batch of %d logits is not four flips per image" % B)
+    N = B // 4
+    if out is None:
+        out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=logits.device)
+    else:
+        _tta_tensor("xbd_tta_merge", "out", out, torch.uint8, "[%d, %d, %d, 5]" % (N, H, W),
+                    lambda t: tuple(t.shape) == (N, H, W, 5), logits.device)
+    _call("dh_xbd_tta_merge_u8", _vp(logits.data_ptr()), N, H, W, _vp(out.data_ptr()), S())
+    return out
+
+
 # ---- variants writing into caller-provided (contiguous) buffers ------------------------------------
 def stem_space_to_depth_into(x_nchw, out):
     N, C, H, W = x_nchw.shape

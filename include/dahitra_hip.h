@@ -729,6 +729,22 @@ int dh_adamw_xbd_step_graph(float* param, const float* grad, float* exp_avg, flo
 int dh_xbd_val_count(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl, int B,
                      int H, int W, float thr, int select, long long* image_counts, long long* class_counts, void* stream);
 
+/* ---- xBD prediction: the 4-flip test-time augmentation (xBD_code/predict_test_cls.py:60-94; csrc/xbd_predict.hip) ----------
+ * flip_0 = identity, flip_1 reverses the rows, flip_2 the columns, flip_3 both (each its own inverse).
+ * dh_xbd_tta_pack_u8: pre, post [N][H][W][3] uint8 -> inp [4N][6][H][W] fp32, inp[4n + k] = flip_k(concat(pre_n, post_n)) with
+ * every byte v normalised as (float)v / 127.f - 1.f (both operations rounded to float32).  bgr != 0 reverses each image's RGB
+ * triple (what cv2.imread gives the reference script), bgr == 0 keeps the stored order.  Every byte of inp is written.
+ * dh_xbd_tta_merge_u8: logits [4N][5][H][W] fp32 -> out [N][H][W][5] uint8 (channels last):
+ *   s_k = sigmoid(logits[4n + k]) in fp32, u_k = flip_k(s_k), mean = (((u_0 + u_1) + u_2) + u_3) / 4 in fp32, added in that
+ *   order (numpy's float32 mean over the stack), out = uint8(trunc(float32(mean * 255))).  A NaN logit gives 0 (the
+ *   reference's astype of a NaN is undefined).  Every byte of out is written.
+ * Both launch one kernel and nothing else (no memset or copy node in a recorded step).  pre / post / out may start at any byte;
+ * pointers that are not aligned to their vector, or a W that is no multiple of 4, take a scalar path with the same result.
+ * Refused (nothing is written): a null pointer, N < 1, 4 N > 65535, H < 1, W < 1, H * W >= 2^31. */
+int dh_xbd_tta_pack_u8(const unsigned char* pre, const unsigned char* post, int N, int H, int W, int bgr, float* inp,
+                       void* stream);
+int dh_xbd_tta_merge_u8(const float* logits, int N, int H, int W, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
