@@ -13,8 +13,11 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
     dice(im1, im2, empty_score=1.0)                   xBD_code/utils.py:124-154   as val_score's per-image term, on counts
     predict_dir(model, test_dir, pred_folder)         xBD_code/predict_test_cls.py:58-97 (the 4-flip TTA loop and its files)
         the reference reads the two folders and its list `models` from globals; here they are arguments
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip + the shared model
-kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
+    visualize_dir(model, test_dir, mask_dir, out_dir) xBD_code/visualize_results.py:171-223 (pre | post | truth | prediction PNGs)
+        damage_map / visual_grid are its lines 206-211 / 213-220 on device tensors; the folders are arguments here too, and
+        the localisation probability is channel 0 of the same prediction (the script's separate localisation net is not built)
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_visual.hip +
+the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
 import numpy as np
@@ -352,5 +355,90 @@ def predict_dir(model, test_dir, pred_folder, order='bgr', graph=True):
         for name, part in ((part1, msk[..., :3]), (part2, msk[..., 2:])):
             Image.fromarray(np.ascontiguousarray(part[..., ::-1])).save(os.path.join(pred_folder, name), format='PNG',
                                                                         compress_level=9)
+        written.append(f)
+    return written
+
+
+# ---- damage map and visual grid (xBD_code/visualize_results.py:171-223) ----------------------------------------------
+def damage_map(msk_u8, loc=None):
+    """The per-pixel damage class of visualize_results.py:206-211 from a prediction: msk_u8 [N, H, W, 5] uint8 (predict_tta's
+    tensor) -> [N, H, W] uint8 on the device, 1 .. 4 = 1 + the first maximum of channels 1 .. 4.  loc=None (default) is the script
+    as executed: no pixel is 0.  loc=(t0, t1, t2), or one float for all three, applies the script's three-threshold rule with
+    p = msk_u8[..., 0] / 255 and sets the dropped pixels to 0 (ops.xbd_damage_map; ops.XBD_LOC_THR is the script's _thr).  The
+    script reads p from a separate localisation net, which is not built here; channel 0 of the same prediction, the channel
+    validate thresholds, stands in for it."""
+    if not (torch.is_tensor(msk_u8) and msk_u8.is_cuda):
+        raise _lib.HipLibraryError("dahitra_amd xBD damage map runs on MI355X only (no CPU fallback)")
+    return ops.xbd_damage_map(msk_u8, loc)
+
+
+def _check_labels(gt_u8):
+    """the script's color_dict has the keys 0 .. 4: another label is its KeyError"""
+    top = int(gt_u8.max()) if gt_u8.numel() else 0
+    if top > 4:
+        raise KeyError(top)
+
+
+def visual_grid(model, pre_u8, post_u8, gt_u8, order='bgr', loc=None, graph=True):
+    """The picture of visualize_results.py:176-220 for a batch of pairs, on the device: predict_tta(model, pre_u8, post_u8, order,
+    graph), then ONE kernel that derives the damage class (damage_map's, with the same `loc`) and writes
+        pre | post | colour(gt_u8) | colour(class)          [N, H, 4W, 3] uint8, RGB
+    pre_u8, post_u8 [N, H, W, 3] uint8 RGB as a decoder stores them, gt_u8 [N, H, W] uint8 with the classes 0 .. 4.  The script's
+    array is BGR (cv2): this one with the last axis reversed.  Returns a new device tensor.  A label above 4 raises KeyError, as
+    the script's colour table does; CPU tensors are refused.  H and W are what the net takes: multiples of 64 (the decoder
+    attention batches the 1/16-scale map of each image in rows of 16; ops.linear asserts on anything else)."""
+    for t in (pre_u8, post_u8, gt_u8):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise _lib.HipLibraryError("dahitra_amd xBD visual grid runs on MI355X only (no CPU fallback)")
+    ops.xbd_loc_bounds(loc)                                  # a bad threshold shows before the forward runs
+    _check_labels(gt_u8)
+    msk = predict_tta(model, pre_u8, post_u8, order=order, graph=graph)
+    return ops.xbd_vis_grid(pre_u8, post_u8, gt_u8, msk, loc)
+
+
+def visual_name(f, model_str='TUNet'):
+    """The file name visualize_results.py:222 gives the picture of the pre image `f`, as written: '_pre_' becomes '_vis' (no
+    second underscore) and a '_part1.png' ending is folded to '.png',
+        x_pre_disaster.png -> TUNet_x_visdisaster.png"""
+    return model_str + "_" + f.replace('_pre_', '_vis').replace('_part1.png', '.png')
+
+
+def visualize_dir(model, test_dir, mask_dir, out_dir, model_str='TUNet', crop=512, order='bgr', loc=None, files=None):
+    """The loop of visualize_results.py:172-223: every name that contains '_pre_' is paired with the name where '_pre_' is
+    replaced by '_post_' and with the ground truth mask_dir/<post name>; the three are decoded with PIL (RGB; the mask as its
+    single channel), cut to [:crop, :crop] (crop=None: the whole tile), predicted and painted by visual_grid, and the
+    [H, 4W, 3] picture is written to out_dir (created) as visual_name(f, model_str).  The cut tile goes through the net, so its
+    sides must be multiples of 64 (see visual_grid): ValueError otherwise, before anything is predicted.
+    The script iterates sorted(listdir(test_dir)[100:150]), a slice of an UNSORTED listing, which no two machines need agree on;
+    here the default is every name of sorted(listdir(test_dir)), and `files` (any iterable of names) narrows it.
+    The PNG is written with PIL from the RGB grid at compress level 9, so cv2.imread returns the array the script hands to
+    cv2.imwrite (BGR).  The pixel content is the contract, not the byte stream.  ValueError if the three cropped shapes of a
+    pair differ; KeyError for a label above 4.  Returns the list of the pre names whose pictures were written."""
+    from PIL import Image
+    model = _one_model(model)
+    device = next(model.parameters()).device
+    if device.type != 'cuda':
+        raise _lib.HipLibraryError("dahitra_amd xBD visual grid runs on MI355X only (no CPU fallback): move the model to the GPU")
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for f in sorted(os.listdir(test_dir) if files is None else files):
+        if '_pre_' not in f:
+            continue
+        post_name = f.replace('_pre_', '_post_')
+        img = np.array(Image.open(os.path.join(test_dir, f)).convert('RGB'))[:crop, :crop]
+        img2 = np.array(Image.open(os.path.join(test_dir, post_name)).convert('RGB'))[:crop, :crop]
+        gt = np.array(Image.open(os.path.join(mask_dir, post_name)))
+        if gt.ndim != 2 or gt.dtype != np.uint8:
+            raise ValueError("visualize_dir: the mask %s is %s %s, expected one uint8 channel" % (post_name, gt.shape, gt.dtype))
+        gt = gt[:crop, :crop]
+        if not (img.shape == img2.shape == gt.shape + (3,)):
+            raise ValueError("visualize_dir: %s: pre %s, post %s and mask %s differ after the crop"
+                             % (f, img.shape, img2.shape, gt.shape))
+        if gt.shape[0] % 64 or gt.shape[1] % 64:
+            raise ValueError("visualize_dir: %s: the net takes tiles whose sides are multiples of 64, got %dx%d after crop=%r"
+                             % (f, gt.shape[0], gt.shape[1], crop))
+        pre, post, lab = (torch.from_numpy(np.ascontiguousarray(a)).to(device).unsqueeze(0) for a in (img, img2, gt))
+        grid = visual_grid(model, pre, post, lab, order=order, loc=loc)[0].cpu().numpy()
+        Image.fromarray(grid).save(os.path.join(out_dir, visual_name(f, model_str)), format='PNG', compress_level=9)
         written.append(f)
     return written

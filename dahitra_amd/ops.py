@@ -3,7 +3,9 @@
 torch is used for device memory and the current HIP stream only; every arithmetic result below is
 produced by a kernel of libdahitra_hip.so.  All activations are NHWC tensors of dtype float32
 (parity mode) or bfloat16 (throughput mode)."""
+import bisect
 import ctypes
+import math
 import os
 import sys
 
@@ -1957,6 +1959,100 @@ def xbd_tta_merge(logits, out=None):
         _tta_tensor("xbd_tta_merge", "out", out, torch.uint8, "[%d, %d, %d, 5]" % (N, H, W),
                     lambda t: tuple(t.shape) == (N, H, W, 5), logits.device)
     _call("dh_xbd_tta_merge_u8", _vp(logits.data_ptr()), N, H, W, _vp(out.data_ptr()), S())
+    return out
+
+
+# ---- xBD damage map and visual grid (csrc/xbd_visual.hip) --------------------------------------------------
+XBD_LOC_THR = (0.38, 0.13, 0.14)          # _thr of xBD_code/visualize_results.py
+
+
+_XBD_BYTE_P = [v / 255 for v in range(256)]          # the script's loc_preds for each byte, float64, increasing
+
+
+def xbd_loc_bounds(loc):
+    """The localisation rule of visualize_results.py:209 in the kernel's terms: (use_loc, b0, b1, b2).  loc None: no rule,
+    (0, 0, 0, 0).  loc one number t (a float, a 0-d array or tensor): (t, t, t); else three thresholds (t0, t1, t2).  b_i is the
+    smallest byte v with v / 255 > t_i in float64 -- the script's own comparison: the position of t_i among the 256 quotients,
+    which increase with v -- or 256 if no byte exceeds t_i, so that the kernel's v >= b_i is the script's v / 255 > t_i.
+    (Not ceil(t * 255): 0.2 * 255 rounds to 51.0 while 51 / 255 > 0.2 is false.)  ValueError for a non-finite threshold or
+    another count than three."""
+    if loc is None:
+        return (0, 0, 0, 0)
+    try:
+        thr = [float(t) for t in loc] if isinstance(loc, (tuple, list)) else [float(loc)] * 3
+    except (TypeError, ValueError):
+        try:
+            thr = [float(t) for t in loc]          # any other iterable of numbers, such as a 1-d array
+        except (TypeError, ValueError):
+            raise ValueError("xbd_loc_bounds: loc %r is neither None, a number nor three numbers" % (loc,))
+    if len(thr) != 3:
+        raise ValueError("xbd_loc_bounds: loc %r holds %d thresholds, the rule has three" % (loc, len(thr)))
+    if not all(math.isfinite(t) for t in thr):
+        raise ValueError("xbd_loc_bounds: loc %r holds a non-finite threshold" % (loc,))
+    return (1,) + tuple(bisect.bisect_right(_XBD_BYTE_P, t) for t in thr)
+
+
+def _vis_tensors(what, msk_u8, others, out, out_shape):
+    """the arguments of the two calls below: ValueError, before any launch.  Rank, dtype and agreement of the shapes are
+    checked on every argument first, then device and storage, so a wrong shape shows whatever device the tensors are on.
+    others: (name, tensor, trailing dims after [N, H, W]); out_shape: N, H, W -> the shape of `out`.  Returns N, H, W"""
+    def typed(name, t, text, ok):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or not ok(t):
+            raise ValueError("%s: %s %s %s is not uint8 %s" % (what, name, tuple(getattr(t, "shape", ())),
+                                                               getattr(t, "dtype", type(t)), text))
+    typed("msk_u8", msk_u8, "[N, H, W, 5]", lambda t: t.dim() == 4 and t.shape[3] == 5)
+    N, H, W = msk_u8.shape[:3]
+    checked = [("msk_u8", msk_u8)]
+    for name, t, tail in others:
+        want = (N, H, W) + tail
+        typed(name, t, "%s like msk_u8" % list(want), lambda t: tuple(t.shape) == want)
+        checked.append((name, t))
+    if out is not None:
+        want = out_shape(N, H, W)
+        typed("out", out, str(list(want)), lambda t: tuple(t.shape) == want)
+        checked.append(("out", out))
+    for name, t in checked:
+        if not t.is_cuda or t.device != msk_u8.device:
+            raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device" % (what, name, t.device))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
+    return N, H, W
+
+
+def xbd_damage_map(msk_u8, loc=None, out=None):
+    """The damage class of visualize_results.py:206-211 per pixel, on the device.  msk_u8 [N, H, W, 5] uint8, channels last
+    (what xbd_tta_merge returns) -> [N, H, W] uint8: 1 + the index of the first maximum of channels 1 .. 4, the script's
+    msk[..., 1:].argmax(axis=2) + 1, so 1 .. 4 and a tie goes to the lowest channel.
+    loc: None (default) stops there, as the script executes (its line 211 is commented out).  Three thresholds (t0, t1, t2), or
+    one float for all three, multiply the class by the script's rule with p = msk_u8[..., 0] / 255 in float64,
+        (p > t0) | ((p > t1) & (dmg > 1) & (dmg < 4)) | ((p > t2) & (dmg > 1)),
+    so a dropped pixel is class 0; XBD_LOC_THR holds the script's _thr.  The script takes p from a separate localisation net;
+    here it is channel 0 of the same prediction.  out: a [N, H, W] uint8 buffer to write into.  ValueError, before any launch,
+    for a wrong rank, dtype or device, non-contiguous storage or a non-finite threshold."""
+    use, b0, b1, b2 = xbd_loc_bounds(loc)
+    N, H, W = _vis_tensors("xbd_damage_map", msk_u8, (), out, lambda N, H, W: (N, H, W))
+    if out is None:
+        out = torch.empty(N, H, W, dtype=torch.uint8, device=msk_u8.device)
+    _call("dh_xbd_damage_map_u8", _vp(msk_u8.data_ptr()), N, H, W, use, b0, b1, b2, _vp(out.data_ptr()), S())
+    return out
+
+
+def xbd_vis_grid(pre_u8, post_u8, gt_u8, msk_u8, loc=None, out=None):
+    """The picture of visualize_results.py:213-220 on the device: [N, H, 4W, 3] uint8, RGB, the four panels side by side,
+        pre_u8 | post_u8 | colour(gt_u8) | colour(class of msk_u8)
+    pre_u8, post_u8 [N, H, W, 3] uint8 as stored; gt_u8 [N, H, W] uint8, classes 0 .. 4; msk_u8 [N, H, W, 5] uint8 and loc as in
+    xbd_damage_map (the class is computed inside the kernel, no class map is written).  Colours, RGB: 0 (0, 0, 0), 1 (0, 255, 0),
+    2 (255, 255, 0), 3 (255, 127, 0), 4 (255, 0, 0) -- the script's color_dict, which is in cv2's BGR; its array is this one with
+    the last axis reversed.  A label above 4, a KeyError in the script, is painted (255, 0, 255) here; models/xbd.visual_grid
+    raises.  out: a [N, H, 4W, 3] uint8 buffer to write into.  ValueError, before any launch, for a wrong rank, dtype or device,
+    non-contiguous storage, shapes that do not agree or a non-finite threshold."""
+    use, b0, b1, b2 = xbd_loc_bounds(loc)
+    N, H, W = _vis_tensors("xbd_vis_grid", msk_u8, (("pre_u8", pre_u8, (3,)), ("post_u8", post_u8, (3,)), ("gt_u8", gt_u8, ())),
+                           out, lambda N, H, W: (N, H, 4 * W, 3))
+    if out is None:
+        out = torch.empty(N, H, 4 * W, 3, dtype=torch.uint8, device=msk_u8.device)
+    _call("dh_xbd_vis_grid_u8", _vp(pre_u8.data_ptr()), _vp(post_u8.data_ptr()), _vp(gt_u8.data_ptr()), _vp(msk_u8.data_ptr()),
+          N, H, W, use, b0, b1, b2, _vp(out.data_ptr()), S())
     return out
 
 

@@ -745,6 +745,27 @@ int dh_xbd_tta_pack_u8(const unsigned char* pre, const unsigned char* post, int 
                        void* stream);
 int dh_xbd_tta_merge_u8(const float* logits, int N, int H, int W, unsigned char* out, void* stream);
 
+/* ---- xBD damage map and the 4-panel visual grid (xBD_code/visualize_results.py:204-220; csrc/xbd_visual.hip) ---------------
+ * msk [N][H][W][5] uint8, channels last: what dh_xbd_tta_merge_u8 writes.  All integer.
+ *   class: dmg = 1 + index of the first maximum of msk[1..4] (a tie goes to the lowest channel): 1 .. 4.
+ *   rule (use_loc != 0): keep = m0 >= b0 || (m0 >= b1 && 1 < dmg < 4) || (m0 >= b2 && dmg > 1) with m0 = msk[0]; the class is
+ *     keep ? dmg : 0.  b_i is the smallest byte v with v / 255 > the script's _thr[i] in float64, 256 if there is none; the caller
+ *     derives it.  use_loc == 0 applies no rule (the script as executed); the b_i are range-checked all the same.
+ *   colour: class 0 .. 4 -> RGB (0,0,0), (0,255,0), (255,255,0), (255,127,0), (255,0,0); any other byte -> (255,0,255).
+ * dh_xbd_damage_map_u8: out [N][H][W] uint8 = the class.
+ * dh_xbd_vis_grid_u8: pre, post [N][H][W][3] uint8, gt [N][H][W] uint8 -> grid [N][H][4W][3] uint8, RGB as pre and post store it:
+ *   columns [0, W) pre, [W, 2W) post, [2W, 3W) colour(gt), [3W, 4W) colour(class).  The class is computed in registers; no class
+ *   map is written.  (The script's BGR array is this one with the last axis reversed.)
+ * Both launch one kernel and nothing else and write every byte of their output.  Every pointer may start at any byte; sources
+ * that are not 16-byte aligned, an output not aligned to its vector store or a W that is no multiple of 4 (grid) take a
+ * pixel-by-pixel path with the same result.
+ * Refused (nothing is written): a null pointer, N < 1, H < 1, W < 1, H * W >= 2^31, a bound outside 0..256 and, for the grid,
+ * 4 * W * 3 * H >= 2^31. */
+int dh_xbd_damage_map_u8(const unsigned char* msk, int N, int H, int W, int use_loc, int b0, int b1, int b2, unsigned char* out,
+                         void* stream);
+int dh_xbd_vis_grid_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* gt, const unsigned char* msk,
+                       int N, int H, int W, int use_loc, int b0, int b1, int b2, unsigned char* grid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
