@@ -1061,12 +1061,17 @@ __global__ __launch_bounds__(256) void head_bwd_finalize_kernel(const float* __r
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// The statistics groups every BatchNorm entry point takes: bn_finalize_kernel shares its four wavefronts among 4 / G of them, and
+// the backward's 1024 / G chunks per group are whole only for these.
+#define DH_REQUIRE_BN_GROUPS(name, groups) \
+    DH_REQUIRE((groups) == 1 || (groups) == 2 || (groups) == 4, "%s: 1, 2 or 4 statistics groups, got %d", name, groups)
+
 extern "C" int dh_bn_finalize(const float* partial, int ntiles, int CP, int C, int groups, double count,
                               const float* gamma, const float* beta, float* running_mean, float* running_var,
                               float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
                               long long* num_batches_tracked, void* stream) {
-    DH_REQUIRE(groups > 0 && ntiles % groups == 0, "bn_finalize: ntiles=%d not divisible by groups=%d", ntiles, groups);
-    DH_REQUIRE(groups == 1 || groups == 2 || groups == 4, "bn_finalize: 1, 2 or 4 statistics groups, got %d", groups);
+    DH_REQUIRE_BN_GROUPS("bn_finalize", groups);
+    DH_REQUIRE(ntiles % groups == 0, "bn_finalize: ntiles=%d not divisible by groups=%d", ntiles, groups);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, ST(stream), partial, ntiles, CP, C, groups, count,
                        gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift,
                        num_batches_tracked);
@@ -1086,6 +1091,7 @@ extern "C" int dh_bn_eval_params(const float* gamma, const float* beta, const fl
 static int bn_apply_impl(int dtype, const void* x, const void* residual, void* y, const float* scale, const float* shift, long npix,
                          int C, int groups, int act, unsigned char* relu_bits, void* stream) {
     const int V = dtype == DH_DTYPE_BF16 ? 8 : 4;       // elements of one 16-byte piece
+    DH_REQUIRE_BN_GROUPS("bn_apply", groups);
     DH_REQUIRE(C % V == 0 && npix % groups == 0, "bn_apply: C=%d npix=%ld groups=%d", C, npix, groups);
     DH_REQUIRE(!relu_bits || act == DH_ACT_RELU, "bn_apply: the ReLU mask bytes go with act = DH_ACT_RELU");
     const long nvec = npix * C / V, gvec = nvec / groups;
@@ -1150,11 +1156,12 @@ static int bn_bwd_impl(int dtype, const void* dout, const void* out_relu, bool b
                        const float* invstd, const float* gamma, long npix, int C, int groups, void* dx,
                        void* dres, float* dgamma, float* dbeta, int accumulate, const float* mask_scale,
                        const float* mask_shift, void* workspace, void* stream) {
+    DH_REQUIRE_BN_GROUPS("bn_bwd", groups);
     DH_REQUIRE(!(out_relu && mask_scale), "bn_bwd: give the ReLU mask either as out_relu or as mask_scale/shift");
     DH_REQUIRE(!bits || out_relu, "bn_bwd: mask bytes missing");
     const int V = dtype == DH_DTYPE_BF16 ? 8 : 4;       // elements of one 16-byte piece
     DH_REQUIRE(C % V == 0 && (256 * V) % C == 0, "bn_bwd: unsupported C=%d", C);
-    DH_REQUIRE(npix % groups == 0 && groups <= BN_MAXG, "bn_bwd: npix %% groups, at most %d groups", BN_MAXG);
+    DH_REQUIRE(npix % groups == 0, "bn_bwd: npix=%ld not divisible by groups=%d", npix, groups);
     const int bpg = 1024 / groups;      // ~1024 workgroups in total (4 per CU)
     const long ppg = npix / groups;
     float* partial = reinterpret_cast<float*>(workspace);
@@ -1201,7 +1208,8 @@ extern "C" int dh_bn_bwd_from_partials(int dtype, const void* g, const void* x, 
                                        int groups, void* dx, float* dgamma, float* dbeta, int accumulate,
                                        void* workspace, void* stream) {
     const int V = dtype == DH_DTYPE_BF16 ? 8 : 4;
-    DH_REQUIRE(C % V == 0 && groups > 0 && ntiles % groups == 0 && npix % groups == 0,
+    DH_REQUIRE_BN_GROUPS("bn_bwd_from_partials", groups);
+    DH_REQUIRE(C % V == 0 && ntiles % groups == 0 && npix % groups == 0,
                "bn_bwd_from_partials: C=%d ntiles=%d npix=%ld groups=%d", C, ntiles, npix, groups);
     float* sums = reinterpret_cast<float*>(workspace);
     const long ppg = npix / groups, nvec = npix * C / V;

@@ -285,7 +285,8 @@ int dh_stem_pool_bn_bwd_plus(const unsigned char* argmax, const void* dpool, con
 int dh_stem_wgrad_bn(const void* xs16, const void* d, const void* y, const float* coef, int groups, int N, int OH, int OW,
                      float* dw2, int use_tr, void* workspace, void* stream);
 
-/* ---- BatchNorm2d (models/resnet.py:152,40-44; help_funcs.py:11) and LayerNorm(32) (help_funcs.py:34-49) */
+/* ---- BatchNorm2d (models/resnet.py:152,40-44; help_funcs.py:11) and LayerNorm(32) (help_funcs.py:34-49)
+ * groups (statistics groups of equal size, image order): 1, 2 or 4 in dh_bn_finalize / dh_bn_apply* / dh_bn_bwd* alike */
 int dh_bn_finalize(const float* partial, int ntiles, int CP, int C, int groups, double count, const float* gamma,
                    const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                    float* mean, float* invstd, float* scale, float* shift, long long* num_batches_tracked,
