@@ -4,7 +4,13 @@ Mirrored: __init__(args, dataloader) evaluator.py:25-63, _load_checkpoint :66-86
 checkpoint is missing), eval_models(checkpoint_name) :166-182 -> scores dict (acc / mIoU / mF1 / per-class,
 misc/metric_tool.py:96-138).  net.eval() folds every BatchNorm into its convolution; arg-max and the confusion
 matrix are one device kernel per batch (no per-step device->host copy, cf. evaluator.py:89-104,
-metric_tool.py:141-158).  The visualisation jpgs of evaluator.py:118-131 are host plumbing and not written."""
+metric_tool.py:141-158).
+
+The visualisation jpgs of evaluator.py:118-131 (A, B, prediction and ground truth as four make_grid bands, one
+vis_dir/eval_<batch_id>.jpg per batch) are opt-in: args.save_vis, default False, under which nothing is launched or written.
+With it, vis_picture() paints the batch in one kernel (ops.cd_eval_vis, byte-equal to what plt.imsave makes of the reference's
+float array), launched eagerly after the batch's forward -- recorded or eager -- on the same stream, and eval_models copies
+the uint8 picture to the host and saves it with PIL's default JPEG encoder, which decodes to the pixels of matplotlib's file."""
 import os
 
 import numpy as np
@@ -53,6 +59,8 @@ class CDEvaluator:
         # args.hip_graph = False / DAHITRA_NO_GRAPH=1, or a batch of another shape (the ragged last one): the eager forward
         self.use_graph = bool(getattr(args, "hip_graph", True)) and os.environ.get("DAHITRA_NO_GRAPH", "0") != "1"
         self._graph, self._graph_key = None, None
+        # evaluator.py:118-131 writes a picture per batch unconditionally; here it is asked for
+        self.save_vis = bool(getattr(args, "save_vis", False)) and bool(self.vis_dir)
 
     def _log(self, message):
         if self.logger is not None:
@@ -74,6 +82,22 @@ class CDEvaluator:
     def _visualize_pred(self):
         from .losses import argmax_mask
         return argmax_mask(self.G_pred).unsqueeze(1) * 255
+
+    def vis_picture(self):
+        """evaluator.py:118-128 for the current batch (self.batch, self.G_pred), on the device: [4 * rows * H, cols * W, 3] uint8
+        RGB, what plt.imsave makes of the reference's `vis`.  On the graph path G_pred is the recorded step's static output."""
+        if self.batch is None or self.G_pred is None:
+            raise RuntimeError("CDEvaluator.vis_picture: no batch has been evaluated yet")
+        a, b = (self.batch[k].to(self.device).float().contiguous() for k in ('A', 'B'))
+        lab = self.batch['L'].to(self.device).long().contiguous()
+        return ops.cd_eval_vis(a, b, self.G_pred.detach().float().contiguous(), lab)
+
+    def _save_vis(self):
+        """evaluator.py:129-131: vis_dir/eval_<batch_id>.jpg (a later evaluator with the same vis_dir overwrites it, as the
+        16-patch loop of eval_cd.py does)"""
+        from PIL import Image
+        Image.fromarray(self.vis_picture().cpu().numpy()).save(os.path.join(self.vis_dir, 'eval_%d.jpg' % self.batch_id),
+                                                               format='jpeg')
 
     def _forward_pass(self, batch):
         self.batch = batch
@@ -103,6 +127,8 @@ class CDEvaluator:
                 with torch.no_grad():
                     self._forward_pass(batch)
                 self._collect_running_batch_states()
+            if self.save_vis:
+                self._save_vis()
         return self._collect_epoch_states()
 
     def _graphed_batch(self, batch):

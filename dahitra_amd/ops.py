@@ -2056,6 +2056,53 @@ def xbd_vis_grid(pre_u8, post_u8, gt_u8, msk_u8, loc=None, out=None):
     return out
 
 
+# ---- the change-detection evaluator's picture (csrc/cd_visual.hip) -----------------------------------------
+def cd_vis_shape(N, H, W):
+    """the shape of the evaluator's picture of N images H x W: make_grid's min(8, N) tiles per row, padding 0, four bands"""
+    cols = min(8, N)
+    return (4 * ((N + cols - 1) // cols) * H, cols * W, 3)
+
+
+def cd_eval_vis(a, b, logits, label, out=None):
+    """The picture of the reference's models/evaluator.py:118-131 for one batch, on the device: [4 * rows * H, cols * W, 3] uint8
+    RGB (cd_vis_shape), the grids of A, B, the prediction and the ground truth stacked top to bottom, 8 images per row.
+    a, b float32 [N, 3, H, W] as the net receives them: byte = trunc(clip(x * 0.5 + 0.5, 0, 1) * 255), truncated as
+    plt.imsave truncates; logits float32 [N, C, H, W]: white where argmax_nchw's class is >= 1; label int64 [N, H, W] or
+    [N, 1, H, W]: white where it is >= 1.  Tile positions beyond N are black.  out: a uint8 buffer of that shape to write into.
+    One launch writes every byte.  ValueError, before any launch, for a wrong rank or dtype, shapes that do not agree, tensors
+    on different devices or non-contiguous storage; HipLibraryError for CPU tensors (there is no CPU path)."""
+    what = "cd_eval_vis"
+
+    def typed(name, t, dtype, text, ok):
+        if not torch.is_tensor(t) or t.dtype != dtype or not ok(t):
+            raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
+                                                            str(dtype).replace("torch.", ""), text))
+    typed("a", a, torch.float32, "[N, 3, H, W]", lambda t: t.dim() == 4 and t.shape[1] == 3 and t.numel() > 0)
+    N, _, H, W = a.shape
+    typed("b", b, torch.float32, "%s like a" % [N, 3, H, W], lambda t: tuple(t.shape) == (N, 3, H, W))
+    typed("logits", logits, torch.float32, "[%d, C, %d, %d] like a" % (N, H, W),
+          lambda t: t.dim() == 4 and t.shape[1] >= 1 and (t.shape[0],) + tuple(t.shape[2:]) == (N, H, W))
+    typed("label", label, torch.int64, "%s or %s like a" % ([N, H, W], [N, 1, H, W]),
+          lambda t: tuple(t.shape) in ((N, H, W), (N, 1, H, W)))
+    checked = [("a", a), ("b", b), ("logits", logits), ("label", label)]
+    want = cd_vis_shape(N, H, W)
+    if out is not None:
+        typed("out", out, torch.uint8, str(list(want)), lambda t: tuple(t.shape) == want)
+        checked.append(("out", out))
+    if not any(t.is_cuda for _, t in checked):
+        raise _lib.HipLibraryError("dahitra_amd %s runs on MI355X only (no CPU fallback): its tensors are on the CPU" % what)
+    for name, t in checked:
+        if not t.is_cuda or t.device != a.device:
+            raise ValueError("%s: %s is on %s and a on %s; the kernel takes all its tensors on one GPU" % (what, name, t.device, a.device))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
+    if out is None:
+        out = torch.empty(want, dtype=torch.uint8, device=a.device)
+    _call("dh_cd_eval_vis_u8", _vp(a.data_ptr()), _vp(b.data_ptr()), _vp(logits.data_ptr()), _vp(label.data_ptr()), N,
+          logits.shape[1], H, W, _vp(out.data_ptr()), S())
+    return out
+
+
 # ---- variants writing into caller-provided (contiguous) buffers ------------------------------------
 def stem_space_to_depth_into(x_nchw, out):
     N, C, H, W = x_nchw.shape

@@ -767,6 +767,19 @@ int dh_xbd_damage_map_u8(const unsigned char* msk, int N, int H, int W, int use_
 int dh_xbd_vis_grid_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* gt, const unsigned char* msk,
                        int N, int H, int W, int use_loc, int b0, int b1, int b2, unsigned char* grid, void* stream);
 
+/* ---- the change-detection evaluator's picture (models/evaluator.py:118-131; csrc/cd_visual.hip) ------------------------------
+ * dh_cd_eval_vis_u8: A, B [N][3][H][W] fp32 (as the net receives them), logits [N][C][H][W] fp32, label [N][H][W] int64 ->
+ * out [4 * rows * H][cols * W][3] uint8 RGB, cols = min(8, N), rows = ceil(N / cols) (make_grid, padding 0): four bands of
+ * rows * H lines, image n at tile (n / cols, n % cols) of each:
+ *   A and B: t = x * 0.5f + 0.5f in fp32, clipped to [0, 1], byte = trunc(t * 255) (the float64 product's truncation);
+ *   prediction: 255 on all three channels where dh_argmax_nchw's class (first maximum, a later one only if strictly greater)
+ *     is >= 1, else 0;  ground truth: 255 where label >= 1, else 0.  A tile position >= N is 0 in all four bands.
+ * One kernel and nothing else; it writes every byte of out.  W % 4 == 0 with A, B, logits, label 16-byte aligned and out 4-byte
+ * aligned takes 16-byte loads and dword stores; anything else goes pixel by pixel with the same result.  A NaN paints 0.
+ * Refused (nothing is written): a null pointer, N < 1, C < 1, H < 1, W < 1, H * W >= 2^31, 2^31 or more units of 1024 pixels. */
+int dh_cd_eval_vis_u8(const float* A, const float* B, const float* logits, const long long* label, int N, int C, int H, int W,
+                      unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
