@@ -73,6 +73,7 @@ class GpuPairPipeline:
         assert a_u8.is_cuda and a_u8.dtype == torch.uint8 and a_u8.shape == b_u8.shape and a_u8.shape[-1] == 3
         self.a, self.b, self.l = a_u8.contiguous(), b_u8.contiguous(), l_u8.contiguous()
         self.names = list(names) if names is not None else [str(i) for i in range(a_u8.shape[0])]
+        self._plan_params = {}          # TilePlan -> its [P, 4] rows on the device (window_batch)
 
     @classmethod
     def from_dataset_root(cls, root_dir, split='train', device='cuda:0', label_transform='norm', names=None):
@@ -125,6 +126,39 @@ class GpuPairPipeline:
             ops._call("dh_augment_pairs_blur_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params),
                       ops.P(table), n, H, W, h, w, ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
         return {'A': out_a, 'B': out_b, 'L': out_l, 'name': [self.names[i] for i in indices]}
+
+    def window_batch(self, index, plan, out=None):
+        """The P views of source pair `index` under `plan` (tiles.TilePlan): {'A', 'B' float32 [P, 3, h, w], 'L' uint8
+        [P, 1, h, w]}, view p cut at the plan's origin and flipped by its code -- dh_augment_pairs_u8 with the pair's index
+        repeated, one launch.  index: an int, or a device int32 tensor of one element (a recorded graph is re-aimed by writing
+        into it; it is NOT range-checked, the caller keeps it inside 0 .. len - 1).  out: a dict of such tensors to write into."""
+        S, H, W, _ = self.a.shape
+        dev = self.a.device
+        if (plan.H, plan.W) != (H, W):
+            raise ValueError("window_batch: the plan is for %dx%d tiles, the pipeline holds %dx%d" % (plan.H, plan.W, H, W))
+        P, h, w = plan.P, plan.h, plan.w
+        if torch.is_tensor(index):
+            if index.dtype != torch.int32 or index.numel() != 1 or index.device != dev:
+                raise ValueError("window_batch: index %s %s on %s is not one int32 on %s"
+                                 % (tuple(index.shape), index.dtype, index.device, dev))
+            idx = index.reshape(1).expand(P).contiguous()
+        else:
+            if not 0 <= int(index) < S:
+                raise ValueError("window_batch: pair %d of %d" % (index, S))
+            idx = torch.full((P,), int(index), dtype=torch.int32, device=dev)
+        params = self._plan_params.get(plan)
+        if params is None:
+            params = self._plan_params[plan] = torch.from_numpy(plan.params()).to(dev)
+        shapes = {'A': ((P, 3, h, w), torch.float32), 'B': ((P, 3, h, w), torch.float32), 'L': ((P, 1, h, w), torch.uint8)}
+        if out is None:
+            out = {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in shapes.items()}
+        for k, (s, d) in shapes.items():
+            t = out.get(k)
+            if not torch.is_tensor(t) or tuple(t.shape) != s or t.dtype != d or t.device != dev or not t.is_contiguous():
+                raise ValueError("window_batch: out[%r] is not a contiguous %s %s on %s" % (k, str(d).replace("torch.", ""), list(s), dev))
+        ops._call("dh_augment_pairs_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params), P, H, W,
+                  h, w, ops.P(out['A']), ops.P(out['B']), ops.P(out['L']), ops.S())
+        return out
 
     def batches(self, batch_size, img_size, train=True, generator=None, patch=None, drop_last=False, blur=False):
         """one epoch: shuffled with random flips (p = 0.5 each, as the reference's training augmentation) when `train`; with

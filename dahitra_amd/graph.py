@@ -290,6 +290,133 @@ class GraphedEvalStep:
         return self.logits
 
 
+def tile_chunk(P, cap=16):
+    """the default number of views per forward of a tile: the largest divisor of P up to `cap` (16 of 16 views, 7 of 49, 14 of
+    196; measured on newUNetTrans in bf16: 7 views per forward deliver 9.4 k views/s, 14 deliver 15.4 k, 16 deliver 17.8 k --
+    larger chunks are not measured, pass `chunk` to try them)"""
+    return max(c for c in range(1, min(P, cap) + 1) if P % c == 0)
+
+
+class TileBuffers:
+    """The static tensors of one tile's pass: the index of the source pair (device int32), the P cut views, the net's
+    [P, C, h, w] answers and what comes out of them.  GraphedTileStep records `run()`; models.tiles runs the same method eagerly,
+    so both paths make the same launches."""
+
+    def __init__(self, net, pipe, plan, confusion=None, chunk=None):
+        dev = pipe.a.device
+        S, H, W, _ = pipe.a.shape
+        if (plan.H, plan.W) != (H, W):
+            raise ValueError("tile step: the plan is for %dx%d tiles, the pipeline holds %dx%d" % (plan.H, plan.W, H, W))
+        P, h, w = plan.P, plan.h, plan.w
+        chunk = tile_chunk(P) if chunk is None else int(chunk)
+        if chunk < 1 or P % chunk:
+            raise ValueError("tile step: chunk %d does not divide the %d views of %r" % (chunk, P, plan))
+        self.net, self.pipe, self.plan, self.chunk, self.confusion = net, pipe, plan, chunk, confusion
+        self.index = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.views = {'A': torch.empty(P, 3, h, w, dtype=torch.float32, device=dev),
+                      'B': torch.empty(P, 3, h, w, dtype=torch.float32, device=dev),
+                      'L': torch.empty(P, 1, h, w, dtype=torch.uint8, device=dev)}
+        self.view_logits = self.mask = self.logits = None          # allocated by the first run(), which learns C from the net
+
+    def _allocate(self, C):
+        dev, plan = self.index.device, self.plan
+        want = (C, C) if plan.stitchable else (plan.P, C, C)
+        cf = self.confusion
+        if cf is not None and (tuple(cf.shape) != want or cf.dtype != torch.int64 or cf.device != dev or not cf.is_contiguous()):
+            raise ValueError("tile step: confusion %s %s is not a contiguous int64 %s on %s for %r"
+                             % (tuple(cf.shape), cf.dtype, list(want), dev, plan))
+        if not plan.stitchable and cf is None:
+            raise ValueError("tile step: %r only counts per view; give it a confusion buffer [%d, C, C]" % (plan, plan.P))
+        self.view_logits = torch.empty(plan.P, C, plan.h, plan.w, dtype=torch.float32, device=dev)
+        if plan.stitchable:
+            self.mask = torch.empty(plan.H, plan.W, dtype=torch.uint8, device=dev)
+            self.logits = torch.empty(C, plan.H, plan.W, dtype=torch.float32, device=dev)
+
+    def aim(self, index):
+        """name the source pair of the next run (range-checked here, on the host; one fill launch, no read)"""
+        if not 0 <= int(index) < len(self.pipe):
+            raise ValueError("tile step: pair %d of %d" % (index, len(self.pipe)))
+        self.index.fill_(int(index))
+
+    def run(self):
+        """cut the views of the pair `index` names, the eval-mode forward in chunks, then the stitch or the per-view counts"""
+        plan, v = self.plan, self.views
+        self.pipe.window_batch(self.index, plan, out=v)
+        with torch.no_grad():
+            for s in range(0, plan.P, self.chunk):
+                y = self.net(v['A'][s:s + self.chunk], v['B'][s:s + self.chunk])
+                if self.view_logits is None:
+                    self._allocate(y.shape[1])
+                want = (self.chunk,) + tuple(self.view_logits.shape[1:])
+                if tuple(y.shape) != want:                     # copy_ would broadcast a smaller answer over the chunk
+                    raise ValueError("tile step: the net answered %s to %d views, the step holds %s" % (tuple(y.shape), self.chunk, list(want)))
+                self.view_logits[s:s + self.chunk].copy_(y)
+        if plan.stitchable:
+            if self.confusion is None:
+                ops.cd_tile_stitch(self.view_logits, plan, out_logits=self.logits, out_mask=self.mask)
+            else:
+                ops.cd_tile_stitch(self.view_logits, plan, out_logits=self.logits, out_mask=self.mask, label=self.pipe.l,
+                                   counts=self.confusion, label_index=self.index)
+        else:
+            ops.cd_view_counts(self.view_logits, v['L'], self.confusion)
+        return self.mask, self.logits
+
+
+class GraphedTileStep:
+    """The change map of one whole tile as ONE HIP graph: dh_augment_pairs_u8 cuts the P views of `plan` (tiles.TilePlan) from
+    the pair a static device index names, the eval-mode forward runs over them in chunks of `chunk` views (back to back, into
+    one [P, C, h, w] buffer), and dh_cd_tile_stitch blends the answers into the [H, W] class map and [C, H, W] logits -- or, for
+    a TilePlan.eval_cd plan, dh_cd_view_counts counts the sixteen views against their own labels.  A tile is 16 to 196 eager
+    forwards otherwise, each bound by its launches from Python.
+
+        step = GraphedTileStep(net, pipe, plan)               # net.eval() is called here
+        mask, logits = step.step(index)                       # the static tensors, valid until the next replay
+
+    confusion: int64 [C, C] (stitchable plan: the stitched map against the tile's own label plane, accumulated) or [P, C, C]
+    (eval_cd plan, required).  chunk: views per forward, a divisor of P (default: the largest up to 16).  Another tile is another
+    value of the device index, not another recording.  The parameters are read when the graph replays."""
+
+    def __init__(self, net, pipe, plan, confusion=None, chunk=None, warmup=2):
+        net.eval()
+        self.net = net
+        self.buf = TileBuffers(net, pipe, plan, confusion, chunk)
+        dev = pipe.a.device
+        net._ensure_arena(dev)
+        conf0 = confusion.clone() if confusion is not None else None
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self.buf.run()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        if confusion is not None:
+            confusion.copy_(conf0)                            # the warm-up passes are not part of any count
+        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
+        ops.rekey_workspace(dev, s, cs)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cs):
+            self.buf.run()
+        self._pinned = ops.pin_captured_buffers(net)
+        self._generation = net._arena.generation
+        torch.cuda.synchronize()
+        if confusion is not None:
+            confusion.copy_(conf0)
+
+    def step(self, index):
+        if self.net._arena.generation != self._generation:
+            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this tile step was captured; "
+                               "build a new GraphedTileStep")
+        if self.net.training:
+            raise RuntimeError("dahitra_amd: GraphedTileStep replays the eval-mode forward; call net.eval() (a train-mode "
+                               "forward in between re-packs the weights for training)")
+        self.buf.aim(index)
+        self.graph.replay()
+        return self.buf.mask, self.buf.logits
+
+    __call__ = step
+
+
 class GraphedXbdEvalStep:
     """One validation batch of the xBD loop (xBD_code/train.py:259-279) as ONE HIP graph: the eval-mode weight re-pack, the
     forward of the 6-channel model and dh_xbd_val_count on its logits -- sigmoid, threshold, arg-max and the tp / fn / fp and

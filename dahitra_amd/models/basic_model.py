@@ -60,3 +60,10 @@ class CDEvaluator:
             if "." not in os.path.basename(file_name):
                 file_name += ".png"
             save_image(pred[0].to(torch.uint8).cpu().numpy(), file_name)
+
+    def predict_tiles(self, pipe, plan=None, graph=True, chunk=None):
+        """whole-tile predictions of every pair of `pipe` (a GpuPairPipeline) with the loaded net, written into pred_dir: one
+        0 / 255 PNG per pair, named as _save_predictions names them (models/tiles.predict_tiles).  Returns the names."""
+        from .tiles import predict_tiles
+        self.eval()
+        return predict_tiles(self.net_G, pipe, self.pred_dir, plan=plan, graph=graph, chunk=chunk)

@@ -2103,6 +2103,119 @@ def cd_eval_vis(a, b, logits, label, out=None):
     return out
 
 
+# ---- whole-tile change maps (tiles.TilePlan; csrc/cd_tile.hip) -----------------------------------------------
+_TILE_TABLES = {}        # (plan, device) -> the plan's tables on that device, built once
+
+
+def tile_tables(plan, device):
+    """The tables dh_cd_tile_stitch reads for `plan`, on `device`: {'ys', 'xs', 'flips', 'rows', 'cols'} int32 and {'wy', 'wx'}
+    float32, views into one buffer each, built on the host from the plan once per (plan, device) and kept."""
+    key = (plan, str(torch.device(device)))
+    t = _TILE_TABLES.get(key)
+    if t is None:
+        import numpy as np
+        rows, cols = plan.cover()
+        wy, wx = plan.weights()
+        ints = [("ys", np.asarray(plan.ys, dtype=np.int32)), ("xs", np.asarray(plan.xs, dtype=np.int32)),
+                ("flips", np.asarray(plan.flips, dtype=np.int32)), ("rows", rows.reshape(-1)), ("cols", cols.reshape(-1))]
+        flat_i = torch.from_numpy(np.concatenate([a for _, a in ints])).to(device)
+        flat_f = torch.from_numpy(np.concatenate([wy, wx])).to(device)
+        t, o = {"_keep": (flat_i, flat_f)}, 0
+        for name, a in ints:
+            t[name] = flat_i[o:o + a.size]
+            o += a.size
+        t["wy"], t["wx"] = flat_f[:plan.h], flat_f[plan.h:]
+        _TILE_TABLES[key] = t
+    return t
+
+
+def _tile_checker(what):
+    checked = []
+
+    def typed(name, t, dtype, text, ok):
+        if not torch.is_tensor(t) or t.dtype != dtype or not ok(t):
+            raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
+                                                            str(dtype).replace("torch.", ""), text))
+        checked.append((name, t))
+
+    def placed():
+        first = checked[0][1]
+        if not any(t.is_cuda for _, t in checked):
+            raise _lib.HipLibraryError("dahitra_amd %s runs on MI355X only (no CPU fallback): its tensors are on the CPU" % what)
+        for name, t in checked:
+            if not t.is_cuda or t.device != first.device:
+                raise ValueError("%s: %s is on %s and %s on %s; the kernel takes all its tensors on one GPU"
+                                 % (what, name, t.device, checked[0][0], first.device))
+            if not t.is_contiguous():
+                raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
+    return typed, placed
+
+
+def cd_tile_stitch(logits, plan, out_logits=None, out_mask=None, label=None, counts=None, label_index=None):
+    """The change map of a whole tile from the net's answers to its windows (tiles.TilePlan), on the device.
+    logits float32 [P, C, h, w], view p of `plan` each, still flipped -> (mask uint8 [H, W], blended logits float32 [C, H, W]).
+    Per pixel and class the covering views are taken iy ascending, ix ascending, f in plan order: acc = acc + g * v,
+    ws = ws + g with g = wy[ly] * wx[lx] at the view's un-flipped position, every operation rounded to float32 on its own,
+    out = acc / ws; the mask is argmax_nchw's rule on out.  One gathering launch, no floating-point atomics: the same bits on
+    every run.  out_logits, out_mask: buffers to write into (every element is written).  label uint8 [H, W] with counts int64
+    [C, C]: counts[label, class] += 1 per pixel (confusion_matrix's orientation), accumulated.  label_index: a device int32
+    tensor of one element; label is then [S, H, W] and that plane is read (a recorded graph follows its tile).  Its VALUE is
+    on the device and is not range-checked: the caller keeps it inside 0 .. S - 1 (graph.TileBuffers.aim checks on the host).
+    ValueError, before any launch, for a plan that is not stitchable, a wrong rank, dtype or shape, tensors on different
+    devices or non-contiguous storage; HipLibraryError for CPU tensors (there is no CPU path)."""
+    what = "cd_tile_stitch"
+    plan._need_stitchable(what)
+    typed, placed = _tile_checker(what)
+    P, h, w, H, W = plan.P, plan.h, plan.w, plan.H, plan.W
+    typed("logits", logits, torch.float32, "[%d, C <= 8, %d, %d] as the plan has it" % (P, h, w),
+          lambda t: t.dim() == 4 and 1 <= t.shape[1] <= 8 and (t.shape[0],) + tuple(t.shape[2:]) == (P, h, w))
+    C = logits.shape[1]
+    if out_logits is not None:
+        typed("out_logits", out_logits, torch.float32, str([C, H, W]), lambda t: tuple(t.shape) == (C, H, W))
+    if out_mask is not None:
+        typed("out_mask", out_mask, torch.uint8, str([H, W]), lambda t: tuple(t.shape) == (H, W))
+    if (label is None) != (counts is None):
+        raise ValueError("%s: a label tile and counts come together" % what)
+    if label_index is not None and label is None:
+        raise ValueError("%s: a label index without labels" % what)
+    if label is not None:
+        if label_index is None:
+            typed("label", label, torch.uint8, str([H, W]), lambda t: tuple(t.shape) == (H, W))
+        else:
+            typed("label", label, torch.uint8, "[S, %d, %d]" % (H, W), lambda t: t.dim() == 3 and tuple(t.shape[1:]) == (H, W))
+            typed("label_index", label_index, torch.int32, "of one element", lambda t: t.numel() == 1)
+        typed("counts", counts, torch.int64, str([C, C]), lambda t: tuple(t.shape) == (C, C))
+    placed()
+    dev = logits.device
+    if out_logits is None:
+        out_logits = torch.empty(C, H, W, dtype=torch.float32, device=dev)
+    if out_mask is None:
+        out_mask = torch.empty(H, W, dtype=torch.uint8, device=dev)
+    t = tile_tables(plan, dev)
+    vp = lambda x: _vp(x.data_ptr()) if x is not None else _vp(0)
+    _call("dh_cd_tile_stitch", vp(logits), P, C, h, w, vp(t["ys"]), plan.ny, vp(t["xs"]), plan.nx, vp(t["flips"]), plan.nf,
+          vp(t["wy"]), vp(t["wx"]), vp(t["rows"]), vp(t["cols"]), plan.x_align(), H, W, vp(out_logits), vp(out_mask), vp(label),
+          vp(label_index), vp(counts), S())
+    return out_mask, out_logits
+
+
+def cd_view_counts(logits, labels, counts):
+    """counts int64 [P, C, C] += the confusion matrix of each view: logits float32 [P, C, h, w] against labels uint8 [P, h, w] or
+    [P, 1, h, w] (what GpuPairPipeline.window_batch cuts; no int64 copy), class by argmax_nchw's rule, confusion_matrix's
+    orientation counts[p, label, class].  One launch for what P evaluators each keep.  ValueError, before any launch, for a
+    wrong rank, dtype or shape, tensors on different devices or non-contiguous storage; HipLibraryError for CPU tensors."""
+    what = "cd_view_counts"
+    typed, placed = _tile_checker(what)
+    typed("logits", logits, torch.float32, "[P, C <= 8, h, w]", lambda t: t.dim() == 4 and 1 <= t.shape[1] <= 8 and t.numel() > 0)
+    P, C, h, w = logits.shape
+    typed("labels", labels, torch.uint8, "%s or %s like logits" % ([P, h, w], [P, 1, h, w]),
+          lambda t: tuple(t.shape) in ((P, h, w), (P, 1, h, w)))
+    typed("counts", counts, torch.int64, str([P, C, C]), lambda t: tuple(t.shape) == (P, C, C))
+    placed()
+    _call("dh_cd_view_counts", _vp(logits.data_ptr()), _vp(labels.data_ptr()), P, C, h, w, _vp(counts.data_ptr()), S())
+    return counts
+
+
 # ---- variants writing into caller-provided (contiguous) buffers ------------------------------------
 def stem_space_to_depth_into(x_nchw, out):
     N, C, H, W = x_nchw.shape

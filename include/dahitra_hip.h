@@ -780,6 +780,33 @@ int dh_xbd_vis_grid_u8(const unsigned char* pre, const unsigned char* post, cons
 int dh_cd_eval_vis_u8(const float* A, const float* B, const float* logits, const long long* label, int N, int C, int H, int W,
                       unsigned char* out, void* stream);
 
+/* ---- whole-tile change maps (dahitra_amd/tiles.py TilePlan; csrc/cd_tile.hip) ------------------------------------------------
+ * dh_cd_tile_stitch: logits [P][C][h][w] fp32, the net's answer to the P = ny * nx * nf views of one H x W tile, view
+ * p = (iy * nx + ix) * nf + f the window at (ys[iy], xs[ix]) under flip code flips[f] (bit 0: rows reversed, bit 1: columns
+ * reversed), still flipped -> out_logits [C][H][W] fp32 (or NULL) and out_mask [H][W] uint8.  Per pixel (Y, X) and class, over
+ * the covering iy ascending, ix ascending, f in table order: ly = Y - ys[iy], lx = X - xs[ix], g = wy[ly] * wx[lx],
+ * v = the view's element at (bit 0 ? h - 1 - ly : ly, bit 1 ? w - 1 - lx : lx), acc = acc + g * v, ws = ws + g, each operation
+ * rounded to fp32 on its own (no fused multiply-add); out = acc / ws, correctly rounded.  out_mask is dh_argmax_nchw's rule on
+ * out (first maximum).  One thread per pixel (or per 4 columns) gathers: no floating-point atomics, the same bits on every run.
+ * Tables, all in DEVICE memory and trusted as the plan built them: ys [ny], xs [nx] ascending origins with origin + window
+ * inside the tile; flips [nf] codes 0 .. 3; wy [h], wx [w]; row_cover [H][2] = (first iy, count) of the windows over a row,
+ * col_cover [W][2] the same per column.  x_align: 4 states that W, w and every xs[ix] are multiples of 4 (then, with logits and
+ * out_logits 16-byte and out_mask / label 4-byte aligned, a thread takes 4 columns with 16-byte loads and stores), else 1.
+ * label [H][W] uint8 with counts [C][C] int64 (both or neither): counts[label * C + class] += 1 per pixel, a label >= C counts
+ * nowhere.  label_index (device int, or NULL): label is then [S][H][W] and plane label_index[0] is read, so that a recorded
+ * graph follows the tile it is aimed at.
+ * Refused (nothing is launched): a null pointer among the required ones, label without counts or the reverse, C outside
+ * 1 .. 8, a window larger than the tile, H * W >= 2^31, P != ny * nx * nf, nf outside 1 .. 4, x_align not 1 or 4.
+ * dh_cd_view_counts: logits [P][C][h][w] fp32, labels [P][h][w] uint8 -> counts [P][C][C] int64,
+ * counts[p][label * C + class] += 1 with the same arg-max rule: P confusion matrices in one launch.  Refused: a null pointer,
+ * C outside 1 .. 8, P outside 1 .. 65535, an empty view, h * w >= 2^31. */
+int dh_cd_tile_stitch(const float* logits, int P, int C, int h, int w, const int* ys, int ny, const int* xs, int nx,
+                      const int* flips, int nf, const float* wy, const float* wx, const int* row_cover, const int* col_cover,
+                      int x_align, int H, int W, float* out_logits, unsigned char* out_mask, const unsigned char* label,
+                      const int* label_index, long long* counts, void* stream);
+int dh_cd_view_counts(const float* logits, const unsigned char* labels, int P, int C, int h, int w, long long* counts,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
