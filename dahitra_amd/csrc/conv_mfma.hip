@@ -133,10 +133,15 @@ constexpr int CONV_NO_FAMILY = -1;
 static int conv_plan(const ConvArgs& a, int ks, int stride, int dtype, int cus, unsigned admit, ConvPlan& p) {
     p = ConvPlan{};
     p.tilesX = a.tilesX; p.tilesY = a.tilesY; p.rw = a.rw;
-    if ((admit >> CONV_GEMM1X1 & 1) && dh_conv1x1_gemm_plan(a, ks, stride, dtype, p)) return 0;
-    if ((admit & CONV_WREG) && dh_conv_wreg_plan(a, ks, stride, dtype, cus, p)) return 0;
+    // ConvArgs::res_bits: the 64 / 128 / 256-channel stream kernels and the tap kernel's compact epilogue at 3x3 / stride 1 apply
+    // the mask; no other family reads it, so every other plan is refused rather than served with an unmasked sum
+    if (a.res_bits && (!a.res || ks != 3 || stride != 1 || a.phase_mode)) return CONV_NO_FAMILY;
+    if ((admit >> CONV_GEMM1X1 & 1) && dh_conv1x1_gemm_plan(a, ks, stride, dtype, p)) return a.res_bits ? CONV_NO_FAMILY : 0;
+    if ((admit & CONV_WREG) && dh_conv_wreg_plan(a, ks, stride, dtype, cus, p))
+        return a.res_bits && (p.family == CONV_WREG32 || p.family == CONV_WREG32_UP4) ? CONV_NO_FAMILY : 0;
     if (!(admit & CONV_TAP)) return CONV_NO_FAMILY;
-    return tap_plan(a, ks, stride, dtype, p);
+    if (int e = tap_plan(a, ks, stride, dtype, p)) return e;
+    return a.res_bits && !p.FAST ? CONV_NO_FAMILY : 0;
 }
 // the CU count the persistent grids are sized for: asked once, 256 where there is no answer
 static int device_cus() {
@@ -251,6 +256,44 @@ extern "C" int dh_conv3x3_split_fwd(const void* x, long x_split_bytes, const voi
     return e;
 }
 
+// 3x3 / stride 1 / pad 1 convolution + MASKED residual, y = conv(x) + (bit ? residual : 0) with the bits in res_bits (ConvArgs::
+// res_bits: the relu_bits of dh_bn_apply_bits for the [N][H][W][Cout] residual).  The data gradient of conv1 of a residual block
+// without a downsample: residual = the gradient of the block's output, res_bits = the ReLU mask of that output -- the masked
+// copy of the gradient (dres of dh_bn_bwd*) is then never written.  Same bits as dh_conv2d_fwd with that copy as residual.
+// No bias, activation or statistics.  dh_conv3x3_res_bits_supported: 1 where a kernel family applies the mask for this shape
+// (and the shape would not otherwise run the 32-channel stream kernel, which does not); callers keep the copy elsewhere.
+static ConvArgs res_bits_conv_args(int dtype, const void* w_frag, int N, int H, int W, int Cin, int Cout, int CoutPad) {
+    ConvArgs a = conv_args(dtype, N, H, W, Cin, H, W, Cout, CoutPad, 3, 1, 1, DH_ACT_NONE);
+    a.w_frag = dtype == DH_DTYPE_BF16 && Cin % 32 == 0 ? w_frag : nullptr;
+    return a;
+}
+extern "C" int dh_conv3x3_res_bits_supported(int dtype, int N, int H, int W, int Cin, int Cout, int CoutPad, int has_frag) {
+    const int esz = dtype == DH_DTYPE_BF16 ? 2 : 4;
+    if ((dtype != DH_DTYPE_F32 && dtype != DH_DTYPE_BF16) || N <= 0 || H <= 0 || W <= 0 || (Cin * esz) % 64 || CoutPad % 16 ||
+        CoutPad < Cout || Cout % (16 / esz))
+        return 0;
+    ConvPlan p;
+    ConvArgs a = res_bits_conv_args(dtype, has_frag ? &p : nullptr, N, H, W, Cin, Cout, CoutPad);     // (&p: presence only)
+    a.res = &p; a.res_bits = reinterpret_cast<const unsigned char*>(&p);
+    return conv_plan(a, 3, 1, dtype, device_cus(), CONV_WREG | CONV_TAP, p) == 0 ? 1 : 0;
+}
+extern "C" int dh_conv3x3_res_bits_fwd(int dtype, const void* x, const void* w_packed, const void* w_frag, const void* residual,
+                                       const unsigned char* res_bits, void* y, int N, int H, int W, int Cin, int Cout, int CoutPad,
+                                       void* stream) {
+    const int esz = dtype == DH_DTYPE_BF16 ? 2 : 4;
+    DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "conv3x3_res_bits_fwd: bad dtype %d", dtype);
+    DH_REQUIRE(x && w_packed && residual && res_bits && y && N > 0 && H > 0 && W > 0, "conv3x3_res_bits_fwd: bad arguments");
+    DH_REQUIRE((Cin * esz) % 64 == 0 && CoutPad % 16 == 0 && CoutPad >= Cout && Cout % (16 / esz) == 0,
+               "conv3x3_res_bits_fwd: Cin=%d Cout=%d CoutPad=%d", Cin, Cout, CoutPad);
+    ConvArgs a = res_bits_conv_args(dtype, w_frag, N, H, W, Cin, Cout, CoutPad);
+    a.x = x; a.w = w_packed; a.y = y; a.res = residual; a.res_bits = res_bits;
+    const int e = conv_issue(a, 3, 1, dtype, CONV_WREG | CONV_TAP, stream);
+    if (e == CONV_NO_FAMILY)
+        DH_FAIL("conv3x3_res_bits_fwd: no kernel family applies the residual's mask bytes for %d x %dx%d, %d -> %d channels "
+                "(dh_conv3x3_res_bits_supported)", N, H, W, Cin, Cout);
+    return e;
+}
+
 // The class head (3x3, pad 1, <= 16 classes) with fp32 NCHW logits written by the convolution itself: see ConvArgs::y_nchw.
 extern "C" int dh_conv3x3_head_fwd(int dtype, const void* x, const void* w_packed, const float* bias, int N, int H, int W, int Cin,
                                    int Cout, const float* in_scale, const float* in_shift, int in_groups,
@@ -329,7 +372,9 @@ extern "C" int dh_conv2d_fwd_describe(int entry, int dtype, int N, int H, int W,
         case 2: e = dh_conv3x3_split_fwd(on, xs, on, frag, on, ys, stats, N, H, W, Cin, Cout, nullptr); break;
         case 3: e = dh_conv3x3_up4_fwd(on, on, on, present, act, on, stats, N, H, W, nullptr); break;
         case 4: e = dh_conv3x3_dgrad_up4(dtype, on, on, N, H, W, Cin, present, nullptr); break;
-        default: dh_set_error("conv2d_fwd_describe: entry (0 dh_conv2d_fwd, 1 head, 2 split, 3 up4 fwd, 4 dgrad up4)");
+        case 5: e = dh_conv3x3_res_bits_fwd(dtype, on, on, frag, on, reinterpret_cast<const unsigned char*>(present), on, N, H, W, Cin, Cout,
+                                            CoutPad, nullptr); break;
+        default: dh_set_error("conv2d_fwd_describe: entry (0 dh_conv2d_fwd, 1 head, 2 split, 3 up4 fwd, 4 dgrad up4, 5 res_bits fwd)");
     }
     t_describe = nullptr;
     return e;

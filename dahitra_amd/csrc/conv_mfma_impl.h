@@ -108,6 +108,12 @@ struct ConvArgs {
     // written or read.  H, W stay the FINE sizes.
     const void* up4_a;
     const void* up4_b;
+    // ReLU mask BYTES that go with `res` (the layout of dh_bn_apply_bits's relu_bits: byte i covers the 16-byte piece i of the
+    // [N][OH][OW][Cout] residual tensor, bit j its element j), or null.  With them the epilogue adds (bit ? res : 0): the skip
+    // gradient dout * relu_mask of a residual block, formed from dout itself instead of from a masked copy of it.  Implemented by
+    // conv3x3_wreg_kernel (64 / 128 / 256 input channels) and the compact epilogue of conv_mfma_kernel at 3x3 / stride 1;
+    // conv_plan refuses it everywhere else (dh_conv3x3_res_bits_fwd).
+    const unsigned char* res_bits;
 };
 
 // The whole host-side decision of one forward / data-gradient launch (conv_plan, conv_mfma.hip): made once per call from the
@@ -575,6 +581,14 @@ __global__ __launch_bounds__(256, conv_min_wgs<T>()) void conv_mfma_kernel(ConvA
                             const size_t roff = (KS == 2 && p.phase_mode == 1) ? (size_t)(oy * p.OW + ox) * NT + (c - co0)
                                                                               : (size_t)(oy * p.OW + ox) * p.Cout + c;
                             ld4(rin + roff, rr);
+                            if constexpr (KS == 3 && STRIDE == 1) {
+                                if (p.res_bits) {     // these 4 channels are half a 16-byte piece (bf16) or a whole one (fp32)
+                                    const size_t e = (size_t)n * p.OH * p.OW * p.Cout + roff;
+                                    const unsigned m = p.res_bits[e / PIECE] >> (e % PIECE);
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) rr[j] = (m >> j & 1u) ? rr[j] : 0.f;
+                                }
+                            }
 #pragma unroll
                             for (int j = 0; j < 4; ++j) v[j] += rr[j];
                         }

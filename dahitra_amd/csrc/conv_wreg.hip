@@ -59,6 +59,15 @@ template <int N>
 __device__ __forceinline__ void wr_wait_for(unsigned long long& d) {
     asm volatile("s_waitcnt vmcnt(%1)" : "+a"(d) : "n"(N) : "memory");
 }
+// the same pair for the one mask byte that goes with a residual row (ConvArgs::res_bits): the byte is requested right after its
+// row, so the wait that covers it covers the row as well -- it takes both destinations
+__device__ __forceinline__ void wr_gload1(const void* src, unsigned& d) {
+    asm volatile("global_load_ubyte %0, %1, off" : "=a"(d) : "v"(src) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wr_wait_for2(unsigned long long& d, unsigned& m) {
+    asm volatile("s_waitcnt vmcnt(%2)" : "+a"(d), "+a"(m) : "n"(N) : "memory");
+}
 // hide a loop-invariant value from the optimiser, so that what is derived from it is recomputed where it is used instead of
 // being hoisted into (scarce) registers for the life of the stream loop
 __device__ __forceinline__ int wr_opaque(int v) { asm volatile("" : "+v"(v)); return v; }
@@ -98,8 +107,9 @@ struct WrTile {       // one 8x16 tile of the stream: per-lane source offsets of
 };
 static_assert(WR_NI == 3, "WrTile carries three piece offsets");
 
-template <int NSUB, int NCH, int D, int PFD, bool INBN, int WPS, bool RES, bool RELU>
+template <int NSUB, int NCH, int D, int PFD, bool INBN, int WPS, bool RES, bool RELU, bool RBITS = false>
 __global__ __launch_bounds__(256, WPS) void conv3x3_wreg_kernel(WrArgs a) {
+    static_assert(!RBITS || (RES && !RELU && NSUB == 1), "the residual's mask bytes: one byte covers a lane's row of one sub-block");
     // One tile = NCH stages (one 32-channel chunk image each) = NCH * 30 steps; a step = one halo fragment (kernel column kw,
     // halo row h) read from LDS and the <= 3 * NSUB MFMAs it feeds.  The steps of the whole stream form ONE software pipeline:
     // the fragment of step g + PFD is read before the MFMAs of step g, across stage and tile boundaries, so the matrix pipe
@@ -306,13 +316,22 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_wreg_kernel(WrArgs a) {
     for (int s = 0; s < NSUB; ++s)
 #pragma unroll
         for (int r = 0; r < WR_TH; ++r) rr[s][r] = 0;
+    // RBITS: the mask byte of each residual row (this lane's 4 channels are one nibble of it), requested right after its row -- a
+    // row and its byte land together, so row 0 waits for two loads and not for all of them; every younger row counts twice
+    unsigned rm[RBITS ? WR_TH : 1];
+#pragma unroll
+    for (int r = 0; r < (RBITS ? WR_TH : 1); ++r) rm[r] = 0;
     auto res_issue = [&](const WrTile& t) {
         const bf16* rin = reinterpret_cast<const bf16*>(p.res) + (size_t)t.n * p.OH * p.OW * p.Cout;
+        const unsigned char* bin = RBITS ? p.res_bits + (((size_t)t.n * p.OH * p.OW * p.Cout) >> 3) : nullptr;
 #pragma unroll
-        for (int r = 0; r < WR_TH; ++r)
+        for (int r = 0; r < WR_TH; ++r) {
 #pragma unroll
             for (int s = 0; s < NSUB; ++s)
                 wr_gload8(rin + (size_t)((t.oy0 + r) * p.OW + t.ox0 + pl) * p.Cout + co_w + s * 16 + wr_opaque(g) * 4, rr[s][r]);
+            if constexpr (RBITS)
+                wr_gload1(bin + (((size_t)((t.oy0 + r) * p.OW + t.ox0 + pl) * p.Cout + co_w + wr_opaque(g) * 4) >> 3), rm[r]);
+        }
     };
     int en = 0, eoy0 = 0, eox0 = 0;                        // the tile whose epilogue is pending
     constexpr int NST = WR_TH * TW * PPR / 256;            // cooperative store rounds
@@ -322,7 +341,18 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_wreg_kernel(WrArgs a) {
         for (int s = 0; s < NSUB; ++s) {
             float v[4], res4[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (has_res) {
-                if (s == 0) {                              // row r of every sub-block has landed
+                if constexpr (RBITS) {                     // row r and its mask byte have landed
+                    switch (r) {
+                    case 0: wr_wait_for2<14 + WR_NI>(rr[0][0], rm[0]); break;
+                    case 1: wr_wait_for2<12 + WR_NI>(rr[0][1], rm[1]); break;
+                    case 2: wr_wait_for2<10 + WR_NI>(rr[0][2], rm[2]); break;
+                    case 3: wr_wait_for2<8 + WR_NI>(rr[0][3], rm[3]); break;
+                    case 4: wr_wait_for2<6 + WR_NI>(rr[0][4], rm[4]); break;
+                    case 5: wr_wait_for2<4 + WR_NI>(rr[0][5], rm[5]); break;
+                    case 6: wr_wait_for2<2 + WR_NI>(rr[0][6], rm[6]); break;
+                    default: wr_wait_for2<WR_NI>(rr[0][7], rm[7]); break;
+                    }
+                } else if (s == 0) {                       // row r of every sub-block has landed
                     switch (r) {
                     case 0: wr_wait_for<7 * NSUB + WR_NI>(rr[0][0]); break;
                     case 1: wr_wait_for<6 * NSUB + WR_NI>(rr[0][1]); break;
@@ -337,6 +367,12 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_wreg_kernel(WrArgs a) {
                 const unsigned lo = (unsigned)rr[s][r], hi = (unsigned)(rr[s][r] >> 32);
                 res4[0] = __uint_as_float(lo << 16); res4[1] = __uint_as_float(lo & 0xffff0000u);
                 res4[2] = __uint_as_float(hi << 16); res4[3] = __uint_as_float(hi & 0xffff0000u);
+                if constexpr (RBITS) {                     // lane group g holds channels 4 g .. 4 g + 3: the low or the high nibble
+                    const unsigned m = rm[RBITS ? r : 0] >> ((wr_opaque(g) & 1) * 4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)          // bit j spread over the word (one v_bfe_i32), then one AND per element
+                        res4[j] = __uint_as_float(__float_as_uint(res4[j]) & (unsigned)((int)(m << (31 - j)) >> 31));
+                }
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -409,7 +445,7 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_wreg_kernel(WrArgs a) {
                 // output tile of the one before --, then refill the slot of stage st - 1
                 if constexpr (INBN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the transform's writes
                 else {
-                    if constexpr (has_res) { if (st == NCH - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((D - 3) * WR_NI + WR_TH * NSUB) : "memory"); }
+                    if constexpr (has_res) { if (st == NCH - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((D - 3) * WR_NI + WR_TH * NSUB + (RBITS ? WR_TH : 0)) : "memory"); }
                     if (!(has_res && st == NCH - 1)) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((D - 3) * WR_NI) : "memory");
                     if (st == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // the epilogue rows' writes
                 }
@@ -488,15 +524,19 @@ int wr_issue(K kern, bool& attr_done, const char* name, const char* no_lds, cons
     return 0;
 }
 
-template <int NSUB, int NCH, int D, int PFD, bool INBN, int WPS, bool RES, bool RELU>
+template <int NSUB, int NCH, int D, int PFD, bool INBN, int WPS, bool RES, bool RELU, bool RBITS = false>
 int wr_launch(const ConvArgs& c, const ConvPlan& p, hipStream_t st) {
     static bool attr_done = false;
-    return wr_issue(conv3x3_wreg_kernel<NSUB, NCH, D, PFD, INBN, WPS, RES, RELU>, attr_done, "conv_wreg", "conv_wreg: cannot raise dynamic LDS to 160 KB", c, p, st);
+    return wr_issue(conv3x3_wreg_kernel<NSUB, NCH, D, PFD, INBN, WPS, RES, RELU, RBITS>, attr_done, "conv_wreg", "conv_wreg: cannot raise dynamic LDS to 160 KB", c, p, st);
 }
 
 template <int NSUB, int NCH, int D, int PFD, int WPS>
 int wr_launch_bn(const ConvArgs& c, const ConvPlan& p, hipStream_t st) {
     if (p.WINBN) return wr_launch<NSUB, NCH, D, PFD, true, WPS, false, false>(c, p, st);     // (never with residual or ReLU: the plan refuses)
+    if (c.res_bits) {                                       // (the plan admits the mask bytes with a residual and no ReLU only)
+        if (!p.RES || p.RELU) DH_FAIL("conv_wreg: the residual's mask bytes need a residual and no activation");
+        return wr_launch<NSUB, NCH, D, PFD, false, WPS, true, false, true>(c, p, st);
+    }
     if (p.RES) return p.RELU ? wr_launch<NSUB, NCH, D, PFD, false, WPS, true, true>(c, p, st)
                              : wr_launch<NSUB, NCH, D, PFD, false, WPS, true, false>(c, p, st);
     return p.RELU ? wr_launch<NSUB, NCH, D, PFD, false, WPS, false, true>(c, p, st)
@@ -1100,6 +1140,7 @@ bool dh_conv_wreg_plan(const ConvArgs& a, int ks, int stride, int dtype, int cus
         if (a.OH % (a.rw == 4 ? 16 : 8) || a.OW % 16) return false;
         if (a.in_scale && (a.in_groups > 4 || a.res || a.act == DH_ACT_RELU)) return false;
         if ((a.x_split && (a.Cin % 128 || a.in_scale)) || (a.y_split && (a.Cout % 128 || a.res))) return false;   // halves = whole chunks / blocks
+        if (a.res_bits && (!a.res || a.in_scale || a.act != DH_ACT_NONE)) return false;      // mask bytes: the RES, no-ReLU form only
         if (g_wreg_mode != 1) {
             // measured (tools/wreg_bench.py, 64 images, gpurun_out/wreg_bench_{9,10}*.txt): the shapes on which this kernel is the
             // faster one -- the 64-channel layers (x1.16 with BatchNorm on load, x1.26 - 1.30 without) and, given the

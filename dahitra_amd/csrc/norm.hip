@@ -96,10 +96,16 @@ template <int V> __device__ __forceinline__ unsigned relu_mask_byte(const float 
     for (int j = 0; j < V; ++j) m |= (v[j] > 0.f ? 1u : 0u) << j;
     return m;
 }
-template <typename T>
+// RA (residual affine): the residual is itself a BatchNorm output that was never written -- the shortcut of a block with a
+// downsample -- and is formed here as T(res * res_scale[g][c] + res_shift[g][c]): the same expression and the same rounding
+// through the tensor's type as the bn_apply launch that used to store it, so y keeps its bits (res_round below)
+__device__ __forceinline__ float res_round(float v, const float*) { return v; }
+__device__ __forceinline__ float res_round(float v, const bf16*) { return bf2f(f2bf(v)); }
+template <typename T, bool RA>
 __global__ void bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
                                 const float* __restrict__ scale, const float* __restrict__ shift, long nvec,
-                                int C, long group_vec, int act, unsigned char* __restrict__ relu_bits) {
+                                int C, long group_vec, int act, unsigned char* __restrict__ relu_bits,
+                                const float* __restrict__ res_scale, const float* __restrict__ res_shift) {
     constexpr int V = V16<T>::N;        // one 16-byte piece per lane
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)((i * V) % C);
@@ -111,6 +117,10 @@ __global__ void bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ r
         if (res) {
             float r[V];
             ldv(res + i * V, r);
+            if constexpr (RA) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) r[j] = res_round(r[j] * res_scale[g * C + c + j] + res_shift[g * C + c + j], res);
+            }
 #pragma unroll
             for (int j = 0; j < V; ++j) v[j] += r[j];
         }
@@ -126,11 +136,13 @@ __global__ void bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ r
 // Same map when 256*V is a multiple of C (every power-of-two width up to 2048): a thread's channel piece is the same in
 // every iteration, so its scale / shift are loaded ONCE (the generic kernel spends 2-7 coefficient loads per data
 // load in the vector cache).  grid = (workgroups per group, groups); two independent pieces in flight per thread.
-template <typename T>
+template <typename T, bool RA>
 __global__ __launch_bounds__(256) void bn_apply_hoist_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                              T* __restrict__ y, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, int C, long group_vec,
-                                                             int act, unsigned char* __restrict__ relu_bits) {
+                                                             int act, unsigned char* __restrict__ relu_bits,
+                                                             const float* __restrict__ res_scale,
+                                                             const float* __restrict__ res_shift) {
     constexpr int V = V16<T>::N;
     const int g = blockIdx.y;
     const long stride = (long)gridDim.x * 256;
@@ -139,6 +151,11 @@ __global__ __launch_bounds__(256) void bn_apply_hoist_kernel(const T* __restrict
     float sc[V], sh[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) { sc[j] = scale[g * C + c + j]; sh[j] = shift[g * C + c + j]; }
+    float rsc[RA ? V : 1], rsh[RA ? V : 1];              // RA: the residual's own coefficient pair, once per thread as well
+    if constexpr (RA) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) { rsc[j] = res_scale[g * C + c + j]; rsh[j] = res_shift[g * C + c + j]; }
+    }
     const size_t base = (size_t)g * group_vec * V;
     x += base; y += base;
     if (res) res += base;
@@ -151,6 +168,10 @@ __global__ __launch_bounds__(256) void bn_apply_hoist_kernel(const T* __restrict
         if (res) { ldv(res + i * V, ra); ldv(res + (i + stride) * V, rb); }
 #pragma unroll
         for (int j = 0; j < V; ++j) {
+            if constexpr (RA) {
+                ra[j] = res_round(ra[j] * rsc[j] + rsh[j], res);
+                rb[j] = res_round(rb[j] * rsc[j] + rsh[j], res);
+            }
             a[j] = a[j] * sc[j] + sh[j];
             b[j] = b[j] * sc[j] + sh[j];
             if (res) { a[j] += ra[j]; b[j] += rb[j]; }
@@ -166,6 +187,7 @@ __global__ __launch_bounds__(256) void bn_apply_hoist_kernel(const T* __restrict
         if (res) ldv(res + i * V, ra);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
+            if constexpr (RA) ra[j] = res_round(ra[j] * rsc[j] + rsh[j], res);
             a[j] = a[j] * sc[j] + sh[j];
             if (res) a[j] += ra[j];
             if (relu) a[j] = fmaxf(a[j], 0.f);
@@ -523,17 +545,25 @@ void launch_bn_bwd_reduce(const void* dout, const void* out_relu, const void* x,
 #undef DH_BWD_REDUCE
 }
 
-template <typename T>
-void launch_bn_apply(const void* x, const void* residual, void* y, const float* scale, const float* shift, long nvec, int C,
-                     int groups, int act, hipStream_t st, unsigned char* relu_bits = nullptr) {
+template <typename T, bool RA>
+void launch_bn_apply_ra(const void* x, const void* residual, void* y, const float* scale, const float* shift, long nvec, int C,
+                        int groups, int act, hipStream_t st, unsigned char* relu_bits, const float* res_scale,
+                        const float* res_shift) {
     constexpr int V = V16<T>::N;
     const long gvec = nvec / groups;
     if ((256 * V) % C == 0)
-        hipLaunchKernelGGL(bn_apply_hoist_kernel<T>, dim3(hoist_grid(gvec, groups), groups), dim3(256), 0, st, (const T*)x,
-                           (const T*)residual, (T*)y, scale, shift, C, gvec, act, relu_bits);
+        hipLaunchKernelGGL((bn_apply_hoist_kernel<T, RA>), dim3(hoist_grid(gvec, groups), groups), dim3(256), 0, st, (const T*)x,
+                           (const T*)residual, (T*)y, scale, shift, C, gvec, act, relu_bits, res_scale, res_shift);
     else
-        hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(ew_grid(nvec, 256)), dim3(256), 0, st, (const T*)x, (const T*)residual,
-                           (T*)y, scale, shift, nvec, C, gvec, act, relu_bits);
+        hipLaunchKernelGGL((bn_apply_kernel<T, RA>), dim3(ew_grid(nvec, 256)), dim3(256), 0, st, (const T*)x, (const T*)residual,
+                           (T*)y, scale, shift, nvec, C, gvec, act, relu_bits, res_scale, res_shift);
+}
+template <typename T>
+void launch_bn_apply(const void* x, const void* residual, void* y, const float* scale, const float* shift, long nvec, int C,
+                     int groups, int act, hipStream_t st, unsigned char* relu_bits = nullptr, const float* res_scale = nullptr,
+                     const float* res_shift = nullptr) {
+    if (res_scale) launch_bn_apply_ra<T, true>(x, residual, y, scale, shift, nvec, C, groups, act, st, relu_bits, res_scale, res_shift);
+    else launch_bn_apply_ra<T, false>(x, residual, y, scale, shift, nvec, C, groups, act, st, relu_bits, nullptr, nullptr);
 }
 
 
@@ -1089,15 +1119,18 @@ extern "C" int dh_bn_eval_params(const float* gamma, const float* beta, const fl
 }
 
 static int bn_apply_impl(int dtype, const void* x, const void* residual, void* y, const float* scale, const float* shift, long npix,
-                         int C, int groups, int act, unsigned char* relu_bits, void* stream) {
+                         int C, int groups, int act, unsigned char* relu_bits, void* stream, const float* res_scale = nullptr,
+                         const float* res_shift = nullptr) {
     const int V = dtype == DH_DTYPE_BF16 ? 8 : 4;       // elements of one 16-byte piece
     DH_REQUIRE_BN_GROUPS("bn_apply", groups);
     DH_REQUIRE(C % V == 0 && npix % groups == 0, "bn_apply: C=%d npix=%ld groups=%d", C, npix, groups);
     DH_REQUIRE(!relu_bits || act == DH_ACT_RELU, "bn_apply: the ReLU mask bytes go with act = DH_ACT_RELU");
+    DH_REQUIRE(!res_scale == !res_shift && (!res_scale || residual), "bn_apply: res_scale and res_shift go together, with a residual");
     const long nvec = npix * C / V, gvec = nvec / groups;
     (void)gvec;
-    if (dtype == DH_DTYPE_BF16) launch_bn_apply<bf16>(x, residual, y, scale, shift, nvec, C, groups, act, ST(stream), relu_bits);
-    else launch_bn_apply<float>(x, residual, y, scale, shift, nvec, C, groups, act, ST(stream), relu_bits);
+    if (dtype == DH_DTYPE_BF16)
+        launch_bn_apply<bf16>(x, residual, y, scale, shift, nvec, C, groups, act, ST(stream), relu_bits, res_scale, res_shift);
+    else launch_bn_apply<float>(x, residual, y, scale, shift, nvec, C, groups, act, ST(stream), relu_bits, res_scale, res_shift);
     DH_CHECK_LAUNCH("bn_apply");
     return 0;
 }
@@ -1111,6 +1144,16 @@ extern "C" int dh_bn_apply_bits(int dtype, const void* x, const void* residual, 
                                 long npix, int C, int groups, int act, unsigned char* relu_bits, void* stream) {
     DH_REQUIRE(relu_bits, "bn_apply_bits: relu_bits missing");
     return bn_apply_impl(dtype, x, residual, y, scale, shift, npix, C, groups, act, relu_bits, stream);
+}
+
+// ... with the residual given as the pre-BatchNorm output of the shortcut's convolution + that BatchNorm's res_scale / res_shift
+// [groups][C]: the residual value is T(residual * res_scale + res_shift), what dh_bn_apply(residual, res_scale, res_shift) would
+// have stored -- y and relu_bits (optional here) keep their bits, the shortcut's tensor is neither written nor read back
+extern "C" int dh_bn_apply_res_affine(int dtype, const void* x, const void* residual, const float* res_scale, const float* res_shift,
+                                      void* y, const float* scale, const float* shift, long npix, int C, int groups, int act,
+                                      unsigned char* relu_bits, void* stream) {
+    DH_REQUIRE(residual && res_scale && res_shift, "bn_apply_res_affine: residual, res_scale and res_shift are all required");
+    return bn_apply_impl(dtype, x, residual, y, scale, shift, npix, C, groups, act, relu_bits, stream, res_scale, res_shift);
 }
 
 // workspace: partial [groups*bpg][2][C] floats + sums [groups][2][C] floats

@@ -69,6 +69,15 @@ class CoarseRes:
         self.t = t
 
 
+class MaskedRes:
+    """the skip gradient of a residual block as (gradient of the block's output, ReLU mask bytes of that output): the data
+    gradient that adds it selects (bit ? t : 0) itself (ops.conv2d(res_bits=...)), the masked copy is never written"""
+    __slots__ = ("t", "bits")
+
+    def __init__(self, t, bits):
+        self.t, self.bits = t, bits
+
+
 class Engine:
     def __init__(self, net_G, dtype=torch.float32, use_tr=True, attn_fp8=False, mma_x3=False):
         self.net_G = net_G
@@ -150,6 +159,16 @@ class Engine:
         # gradient then materialises the map itself).  DESIGN.md section 6e.
         self.fused_up4_fwd = os.environ.get("DAHITRA_FUSED_UP4_FWD", "0") == "1"
         self.use_side = os.environ.get("DAHITRA_SIDE_STREAM", "0") == "1"
+        # Residual blocks keep two tensors out of HBM that had one reader each.  (1) The BatchNorm output of a shortcut with a
+        # downsample: the bn_apply of bn2 / bn3 forms it from the shortcut conv's output while it loads its residual
+        # (ops.BnResidual, dh_bn_apply_res_affine) -- one launch and one write + read of the tensor less.  (2) The masked copy
+        # `dres` of the block's output gradient, which bn2's backward used to write for its one reader: with a downsample the
+        # shortcut's BatchNorm backward reads the gradient itself with bn2's ReLU mask bytes (the mask-bytes form of ops.bn_bwd);
+        # without one conv1's data gradient adds (bit ? gradient : 0) in its epilogue (MaskedRes, dh_conv3x3_res_bits_fwd) where
+        # a kernel family does that (3x3 stride 1: every BasicBlock; the Bottleneck's 1x1 conv1 keeps the copy).  Exact
+        # selections of the same roundings: results keep their bits.  DAHITRA_BLOCK_COPIES=1 restores both tensors (one switch,
+        # for tests).  Measured: DESIGN.md section 6i, "Residual blocks without their single-reader tensors".
+        self.block_copies = os.environ.get("DAHITRA_BLOCK_COPIES", "0") == "1"
         self.pack_side = os.environ.get("DAHITRA_PACK_SIDE", "0") == "1"
         self._pack_stream = None
         self.side = None
@@ -283,6 +302,10 @@ class Engine:
                 return ops.conv3x3s2_dgrad(dy, wph, Cin, residual.t if residual is not None else None, alg_flops=flops)
             return ops.add(ops.conv3x3s2_dgrad(dy, wph, Cin, None, alg_flops=flops), residual)
         assert not isinstance(residual, CoarseRes)
+        if isinstance(residual, MaskedRes):
+            assert gate is None and ks == 3 and stride == 1 and pad == 1 and dilation == 1
+            return ops.conv2d(dy, self.pk[wkey].dgrad, Cin, 3, 1, 1, residual=residual.t, res_bits=residual.bits, alg_flops=flops,
+                              w_frag=self.pk[wkey].dgrad_frag)
         if stride == 2:
             dy = ops.zero_insert2(dy, H, W)
         r = ops.conv2d(dy, self.pk[wkey].dgrad, Cin, ks, 1, dilation * (ks - 1) - pad, residual=residual,
@@ -290,12 +313,16 @@ class Engine:
                        w_frag=self.pk[wkey].dgrad_frag if stride == 1 else None)
         return Gated(*r) if gate is not None else r
 
-    def conv_bn(self, x, wkey, bnkey, ks, stride, pad, groups, relu, residual=None, dilation=1, lazy=False, side_wgrad=False):
+    def conv_bn(self, x, wkey, bnkey, ks, stride, pad, groups, relu, residual=None, dilation=1, lazy=False, side_wgrad=False,
+                lazy_res=False):
         """conv + BatchNorm (+ residual) (+ ReLU).  x may be an ops.BnInput (the previous layer's lazy output).
         lazy=True (train mode, ReLU, no residual; the ONLY consumer must be a 3x3 stride-1 convolution and its weight
         gradient): the normalised activation is never written -- the call returns an ops.BnInput (pre-BN conv output +
         scale / shift) and the consumer applies relu(y * scale + shift) while it loads (the bn_apply pass, one read
-        and one write of the activation, disappears)."""
+        and one write of the activation, disappears).
+        lazy_res=True (train mode, no ReLU, no residual: a block's shortcut, whose ONLY consumer is the residual input of
+        bn2 / bn3's bn_apply): the call returns an ops.BnResidual and that bn_apply normalises while it loads.
+        residual may be an ops.BnResidual (train mode)."""
         cout = self.shapes[wkey][0]
         lazy = lazy and self.training and self.lazy_bn and relu and residual is None and not self.fused_bn_bwd
         gamma, beta = self.p[bnkey + ".weight"], self.p[bnkey + ".bias"]
@@ -316,6 +343,10 @@ class Engine:
                                                          BN_MOMENTUM, BN_EPS, nbt=self.p[bnkey + ".num_batches_tracked"])
             if lazy:
                 out = ops.BnInput(y, scale, shift, groups)
+            elif lazy_res and not relu and residual is None:
+                out = ops.BnResidual(y, scale, shift, groups)
+                if self.block_copies:
+                    out = out.materialize()
             elif relu and residual is not None and self.need_grad:
                 # BatchNorm + residual + ReLU: the backward needs the ReLU mask only -- written here as one byte per 8 elements
                 # (bf16) and read there in place of `out` (one tensor read less in each of its passes)
@@ -326,14 +357,18 @@ class Engine:
             # eval: BatchNorm folds into the convolution -- scale into the packed weights, shift as the bias
             scale, shift = ops.bn_eval_params(gamma, beta, rm, rv, BN_EPS)
             wp = ops.pack_weight(self.p[wkey], self.dtype, want_dgrad=False, out_scale=scale)[0]
+            assert not isinstance(residual, ops.BnResidual)
             out = ops.conv2d(x, wp, cout, ks, stride, pad, bias=shift, residual=residual, act=act, dilation=dilation)
             y = mean = invstd = None
         if not self.need_grad:
             return out, None
         has_res = residual is not None
 
-        def bwd(dout, need_dx=True, dx_res=None, next_gate=None, coarse_dx=False, through_up4=None):
-            """through_up4 = (a, b, da, db): this conv's input is bilinear_x4(|a - b|); the gradients land in da, db"""
+        def bwd(dout, need_dx=True, dx_res=None, next_gate=None, coarse_dx=False, through_up4=None, want_dres=True, mask_bits=None):
+            """through_up4 = (a, b, da, db): this conv's input is bilinear_x4(|a - b|); the gradients land in da, db.
+            want_dres=False (layers with a residual): the masked copy of dout is not written, None is returned in its place.
+            mask_bits (layers without ReLU: a shortcut): dout is the gradient of the BLOCK's output and mask_bits the ReLU mask
+            bytes of that output -- this layer's gradient is dout where the bit is set, zero elsewhere"""
             if isinstance(dout, HeadGrad):    # the class head's gradient, recomputed by both passes of this backward
                 dy = ops.head_bn_bwd(dout.dl, dout.w, dout.ncls, y, scale, shift, mean, invstd, gamma,
                                      self.g[bnkey + ".weight"], self.g[bnkey + ".bias"], groups, dw=dout.gw, db=dout.gb)
@@ -347,10 +382,15 @@ class Engine:
                 dy, dres = ops.bn_bwd(dout, None, y, mean, invstd, gamma, self.g[bnkey + ".weight"],
                                       self.g[bnkey + ".bias"], groups, accumulate=True, mask_scale=scale,
                                       mask_shift=shift), None
+            elif mask_bits is not None:
+                assert not relu and not has_res
+                dy, dres = ops.bn_bwd(dout, None, y, mean, invstd, gamma, self.g[bnkey + ".weight"], self.g[bnkey + ".bias"],
+                                      groups, accumulate=True, bits=mask_bits), None
             else:
+                wd = has_res and want_dres
                 r = ops.bn_bwd(dout, out if relu else None, y, mean, invstd, gamma, self.g[bnkey + ".weight"],
-                               self.g[bnkey + ".bias"], groups, accumulate=True, want_dres=has_res, bits=relu_bits)
-                dy, dres = r if has_res else (r, None)
+                               self.g[bnkey + ".bias"], groups, accumulate=True, want_dres=wd, bits=relu_bits)
+                dy, dres = r if wd else (r, None)
             if side_wgrad and self.side is not None:
                 # Deferred to the side stream: nothing until the batched split-K reduce needs this weight gradient.  It is
                 # launched (run_deferred_wgrad) when the main stream reaches the token encoder's backward -- one workgroup per
@@ -374,6 +414,13 @@ class Engine:
         bwd.gate = (out if relu else None, y, mean, invstd, groups) if (self.fused_bn_bwd and cout % 16 == 0) else None
         # what the class head's data gradient needs to gate itself for this layer (ReLU mask recomputed from y)
         bwd.bn = (y, scale, shift, mean, invstd, groups) if (self.training and relu and not has_res) else None
+        # the ReLU mask bytes of this layer's output (BatchNorm + residual + ReLU), for a shortcut's backward (mask_bits)
+        bwd.relu_bits = relu_bits if not self.fused_bn_bwd else None
+        # can this layer's data gradient add a MaskedRes (dx_res)?  3x3 / stride 1 on a plain input, where a kernel applies the bytes
+        bwd.masked_res_ok = lambda: (self.need_grad and not self.block_copies and not self.fused_bn_bwd and not split and ks == 3 and
+                                     stride == 1 and pad == 1 and dilation == 1 and
+                                     ops.conv3x3_res_bits_supported(tuple(x.shape[:3]) + (cout,), x.shape[-1], self.pk[wkey].dgrad,
+                                                                    self.dtype, self.pk[wkey].dgrad_frag is not None))
         return out, bwd
 
     def conv_act(self, x, wkey, bkey, ks, pad, act, cpad_grad=False):
@@ -470,7 +517,8 @@ class Engine:
         h, b1 = self.conv_bn(x, pfx + ".conv1.weight", pfx + ".bn1", 3, stride, 1, groups, True, lazy=True)
         has_ds = (pfx + ".downsample.0.weight") in self.shapes
         if has_ds:
-            idt, bds = self.conv_bn(x, pfx + ".downsample.0.weight", pfx + ".downsample.1", 1, stride, 0, groups, False)
+            idt, bds = self.conv_bn(x, pfx + ".downsample.0.weight", pfx + ".downsample.1", 1, stride, 0, groups, False,
+                                    lazy_res=True)
         else:
             idt, bds = x, None
         out, b2 = self.conv_bn(h, pfx + ".conv2.weight", pfx + ".bn2", 3, 1, 1, groups, True, residual=idt)
@@ -478,14 +526,22 @@ class Engine:
             return out, None
 
         def bwd(dout, next_gate=None):
-            dh, dres = b2(dout, next_gate=b1.gate)
+            # with a downsample the masked copy has one reader, the shortcut's BatchNorm backward: it takes (dout, mask bytes)
+            bits = b2.relu_bits if (has_ds and not self.block_copies and torch.is_tensor(dout)) else None
+            # ... without one its reader is conv1's data gradient, which selects by the mask bytes itself where a kernel does that
+            mres = not has_ds and next_gate is None and torch.is_tensor(dout) and b2.relu_bits is not None and b1.masked_res_ok()
+            dh, dres = b2(dout, next_gate=b1.gate, want_dres=bits is None and not mres)
+            if bits is not None:
+                dres = dout
+            if mres:
+                dres = MaskedRes(dout, b2.relu_bits)
             if has_ds:
                 if stride == 2 and next_gate is None and self.phase_s2_dgrad and x.shape[-1] in (32, 64):
                     # shortcut gradient on the coarse grid; conv1's phase data gradient adds it at the even-even positions
-                    dxds, _ = bds(dres, coarse_dx=True)
+                    dxds, _ = bds(dres, coarse_dx=True, mask_bits=bits)
                     dx, _ = b1(dh, dx_res=CoarseRes(dxds), next_gate=next_gate)
                 else:
-                    dxds, _ = bds(dres)
+                    dxds, _ = bds(dres, mask_bits=bits)
                     dx, _ = b1(dh, dx_res=dxds, next_gate=next_gate)
             else:
                 dx, _ = b1(dh, dx_res=dres, next_gate=next_gate)
@@ -501,7 +557,8 @@ class Engine:
                               dilation=dilation)
         has_ds = (pfx + ".downsample.0.weight") in self.shapes
         if has_ds:
-            idt, bds = self.conv_bn(x, pfx + ".downsample.0.weight", pfx + ".downsample.1", 1, stride, 0, groups, False)
+            idt, bds = self.conv_bn(x, pfx + ".downsample.0.weight", pfx + ".downsample.1", 1, stride, 0, groups, False,
+                                    lazy_res=True)
         else:
             idt, bds = x, None
         out, b3 = self.conv_bn(h2, pfx + ".conv3.weight", pfx + ".bn3", 1, 1, 0, groups, True, residual=idt)
@@ -509,15 +566,18 @@ class Engine:
             return out, None
 
         def bwd(dout, next_gate=None):
-            dh2, dres = b3(dout, next_gate=b2.gate)
+            bits = b3.relu_bits if (has_ds and not self.block_copies and torch.is_tensor(dout)) else None
+            dh2, dres = b3(dout, next_gate=b2.gate, want_dres=bits is None)
+            if bits is not None:
+                dres = dout
             dh1, _ = b2(dh2, next_gate=b1.gate)
             if has_ds and stride == 2 and next_gate is None and self.coarse_shortcut:
                 # the shortcut's gradient on its own coarse grid, added at the even-even positions of conv1's data gradient
-                dxds, _ = bds(dres, coarse_dx=True)
+                dxds, _ = bds(dres, coarse_dx=True, mask_bits=bits)
                 dx, _ = b1(dh1, next_gate=next_gate)
                 ops.add_coarse_(dx, dxds)
             elif has_ds:
-                dxds, _ = bds(dres)
+                dxds, _ = bds(dres, mask_bits=bits)
                 dx, _ = b1(dh1, dx_res=dxds, next_gate=next_gate)
             else:
                 dx, _ = b1(dh1, dx_res=dres, next_gate=next_gate)

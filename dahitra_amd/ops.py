@@ -412,11 +412,48 @@ class BnInput:
         return self.y.dtype
 
 
+def conv3x3_res_bits_supported(xshape, cout, wp, dtype, has_frag):
+    """does a kernel family apply the mask bytes of conv2d(..., residual=r, res_bits=b) for this 3x3 / stride 1 / pad 1 layer
+    (dh_conv3x3_res_bits_supported)?  Where not, callers keep the masked copy of the residual."""
+    N, H, W, Cin = xshape
+    return dtype in _DT and bool(_lib.lib().dh_conv3x3_res_bits_supported(_DT[dtype], N, H, W, Cin, cout, wp.shape[-2], int(bool(has_frag))))
+
+
+def _conv3x3_res_bits(x, wp, cout, residual, res_bits, alg_flops, w_frag):
+    N, H, W, Cin = x.shape
+    v = 8 if x.dtype == torch.bfloat16 else 4
+    assert residual.shape == (N, H, W, cout) and residual.dtype == x.dtype and res_bits.dtype == torch.uint8 and \
+        res_bits.numel() == residual.numel() // v
+    if not conv3x3_res_bits_supported(x.shape, cout, wp, x.dtype, w_frag is not None):
+        raise _lib.HipLibraryError("dahitra_amd: no kernel applies the residual's mask bytes for %s -> %d channels "
+                                   "(ops.conv3x3_res_bits_supported)" % (tuple(x.shape), cout))
+    cpad = wp.shape[-2]
+    y = torch.empty(N, H, W, cout, dtype=x.dtype, device=x.device)
+    nt_ = 64 if cpad % 64 == 0 else (32 if cpad % 32 == 0 else 16)
+    key = "conv_mfma<%s,ks3,s1,nt%d>" % ("bf16" if x.dtype == torch.bfloat16 else "f32", nt_)
+    flops = alg_flops if alg_flops else 2.0 * N * H * W * cout * Cin * 9
+    fixed = (dt(x), P(x), P(wp), P(w_frag), P(residual), P(res_bits), P(y), N, H, W, Cin, cout, cpad)
+    with _Prof(key, flops, _nb(x, y, wp, residual, res_bits)):
+        _call("dh_conv3x3_res_bits_fwd", *fixed, S())
+    if REPLAY is not None and key == REPLAY["key"]:
+        REPLAY["calls"].append((lambda stream, fixed=fixed: _call("dh_conv3x3_res_bits_fwd", *fixed, stream),
+                                (x, wp, w_frag, residual, res_bits, y), flops))
+    return y
+
+
 def conv2d(x, wp, cout, ks=3, stride=1, pad=1, bias=None, residual=None, act=ACT_NONE, want_stats=False,
-           want_preact=False, npix_valid=0, w_image_stride=0, out_hw=None, alg_flops=0, dilation=1, gate=None, w_frag=None):
+           want_preact=False, npix_valid=0, w_image_stride=0, out_hw=None, alg_flops=0, dilation=1, gate=None, w_frag=None,
+           res_bits=None):
     """gate = (out_relu | None, y_pre_bn, mean, invstd, groups): BN-backward gating of a data-gradient launch; the
     call then returns (g, partials) for bn_bwd_from_partials (see include/dahitra_hip.h).
-    x may be a BnInput: BatchNorm-apply + ReLU happen on load."""
+    x may be a BnInput: BatchNorm-apply + ReLU happen on load.
+    res_bits (3x3 / stride 1 / pad 1, nothing but the residual): the residual added is (bit ? residual : 0), the bits in the
+    layout of bn_apply(want_bits=True); raises where no kernel applies them (conv3x3_res_bits_supported)."""
+    if res_bits is not None:
+        assert residual is not None and ks == 3 and stride == 1 and pad == 1 and dilation == 1 and bias is None and \
+            act == ACT_NONE and not want_stats and not want_preact and not npix_valid and not w_image_stride and gate is None and \
+            torch.is_tensor(x) and (out_hw is None or tuple(out_hw) == tuple(x.shape[1:3]))
+        return _conv3x3_res_bits(x, wp, cout, residual, res_bits, alg_flops, w_frag)
     if isinstance(x, Up4Input):
         assert ks == 3 and stride == 1 and pad == 1 and dilation == 1 and residual is None and gate is None and not want_preact
         return _conv3x3_up4(x, wp, cout, bias, act, want_stats)
@@ -876,9 +913,39 @@ def bn_eval_params(gamma, beta, rm, rv, eps=1e-5):
 RELU_BITS = os.environ.get("DAHITRA_NO_RELU_BITS", "0") != "1"      # A/B switch of bn_apply(want_bits=True)
 
 
+BN_APPLY_LAUNCHES = 0       # bn_apply launches issued (or recorded) by this process, and how many of them only wrote the
+BN_SHORTCUT_APPLIES = 0     # BatchNorm output of a shortcut (BnResidual.materialize): what tests count
+BN_DRES_REQUESTS = 0        # bn_bwd calls asked for the masked copy of their gradient (want_dres=True)
+
+
+class BnResidual:
+    """The BatchNorm output of a block's shortcut (no ReLU) that exists only as (conv output y, per-group scale / shift):
+    bn_apply(residual=<BnResidual>) forms T(y * scale + shift) while it loads the residual (dh_bn_apply_res_affine), bit for
+    bit what materialize() -- the bn_apply launch it stands for -- stores.  Any other consumer calls materialize()."""
+    __slots__ = ("y", "scale", "shift", "groups")
+
+    def __init__(self, y, scale, shift, groups):
+        self.y, self.scale, self.shift, self.groups = y, scale, shift, groups
+
+    @property
+    def shape(self):
+        return self.y.shape
+
+    @property
+    def dtype(self):
+        return self.y.dtype
+
+    def materialize(self):
+        global BN_SHORTCUT_APPLIES
+        BN_SHORTCUT_APPLIES += 1
+        return bn_apply(self.y, self.scale, self.shift, self.groups)
+
+
 def bn_apply(x, scale, shift, groups=1, act=ACT_NONE, residual=None, want_bits=False):
     """want_bits (ReLU): also returns the ReLU mask of y as one byte per 16-byte piece (dh_bn_apply_bits) -- what bn_bwd(bits=...)
-    reads in place of the post-activation tensor; None with DAHITRA_NO_RELU_BITS=1"""
+    reads in place of the post-activation tensor; None with DAHITRA_NO_RELU_BITS=1.  residual may be a BnResidual."""
+    global BN_APPLY_LAUNCHES
+    BN_APPLY_LAUNCHES += 1
     C = x.shape[-1]
     npix = x.numel() // C
     y = torch.empty_like(x)
@@ -886,6 +953,13 @@ def bn_apply(x, scale, shift, groups=1, act=ACT_NONE, residual=None, want_bits=F
     v = 8 if x.dtype == torch.bfloat16 else 4
     if want_bits and RELU_BITS and act == ACT_RELU and C % v == 0:
         bits = torch.empty(x.numel() // v, dtype=torch.uint8, device=x.device)
+    if isinstance(residual, BnResidual):
+        r = residual
+        assert r.y.shape == x.shape and r.y.dtype == x.dtype and r.groups == groups
+        with _Prof("bn_apply", 0, _nb(x, r.y, y)):
+            _call("dh_bn_apply_res_affine", dt(x), P(x), P(r.y), P(r.scale), P(r.shift), P(y), P(scale), P(shift), npix, C, groups,
+                  act, P(bits), S())
+        return (y, bits) if want_bits else y
     with _Prof("bn_apply", 0, _nb(x, residual, y)):
         if bits is not None:
             _call("dh_bn_apply_bits", dt(x), P(x), P(residual), P(y), P(scale), P(shift), npix, C, groups, act, P(bits), S())
@@ -952,6 +1026,9 @@ def bn_bwd(dout, out_relu, x, mean, invstd, gamma, dgamma, dbeta, groups=1, accu
     npix = x.numel() // C
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
+    if want_dres:
+        global BN_DRES_REQUESTS
+        BN_DRES_REQUESTS += 1
     L = _lib.lib()
     ws = workspace(L.dh_bn_bwd_workspace_size(npix, C, groups), x.device)
     if BN_BWD_PERSIST and not _PERSIST_BLOCK and \

@@ -76,7 +76,8 @@ int dh_conv2d_fwd_num_tiles(int dtype, int N, int OH, int OW, int Cin, int ks, i
 /* Host only (no launch, no device, no tensor is read): the launch plan of a forward / data-gradient convolution call under the
  * thread's current dh_set_f32_mma_mode and dh_conv_wreg_mode, on a device of `cus` compute units.  entry: 0 dh_conv2d_fwd (every
  * scalar argument as there), 1 dh_conv3x3_head_fwd (dtype, N, H, W, Cin, Cout, in_groups), 2 dh_conv3x3_split_fwd (N, H, W, Cin, Cout),
- * 3 dh_conv3x3_up4_fwd (N, H, W, act), 4 dh_conv3x3_dgrad_up4 (dtype, N, H, W, Cin = K); the other arguments are ignored.  flags: which
+ * 3 dh_conv3x3_up4_fwd (N, H, W, act), 4 dh_conv3x3_dgrad_up4 (dtype, N, H, W, Cin = K), 5 dh_conv3x3_res_bits_fwd (dtype, N, H, W, Cin,
+ * Cout, CoutPad; flag 32); the other arguments are ignored.  flags: which
  * of the tensors the decision depends on are given -- 1 residual, 2 stats_partial, 4 y_preact, 8 the gate_* tensors, 16 in_scale /
  * in_shift, 32 w_frag, 64 x_split_bytes, 128 y_split_bytes.
  * out[30], unused fields 0:
@@ -99,6 +100,17 @@ int dh_conv2d_fwd_describe(int entry, int dtype, int N, int H, int W, int Cin, i
  * (everything through the tap-oriented kernel); 1: wherever it can run.  Returns the previous mode.  Same reference call sites as dh_conv2d_fwd
  * (models/resnet.py:24-73: BasicBlock conv1 / conv2 and their input gradients). */
 int dh_conv_wreg_mode(int mode);
+/* 3x3 / stride-1 / pad-1 convolution + MASKED residual: y = conv(x) + (bit ? residual : 0), the bits taken from res_bits in the
+ * layout of dh_bn_apply_bits's relu_bits for the [N][H][W][Cout] residual (byte i = its 16-byte piece i, bit j = element j).  It is
+ * the data gradient of conv1 of a residual block without a downsample (models/resnet.py:56-71) fed the gradient of the block's
+ * output and the ReLU mask of that output, so that the masked copy `dres` of dh_bn_bwd* need not be written: bit-identical to
+ * dh_conv2d_fwd with that copy as residual.  No bias, activation or statistics; w_frag optional (bf16).  Served by the
+ * weights-resident stream at 64 / 128 / 256 input channels and by the tap kernel; dh_conv3x3_res_bits_supported returns 1
+ * where one of them takes the shape, 0 where the call would be refused (the 32 -> 32 stream form, which has no mask path,
+ * among them): callers keep the masked copy there.  The mask is never silently ignored. */
+int dh_conv3x3_res_bits_supported(int dtype, int N, int H, int W, int Cin, int Cout, int CoutPad, int has_frag);
+int dh_conv3x3_res_bits_fwd(int dtype, const void* x, const void* w_packed, const void* w_frag, const void* residual,
+                            const unsigned char* res_bits, void* y, int N, int H, int W, int Cin, int Cout, int CoutPad, void* stream);
 /* How the matrix products of DH_F32 launches are computed (dh_conv2d_fwd, dh_conv3x3_head_fwd, dh_conv2d_wgrad* and the
  * kernels that call them), per host thread, read when a launch is issued:
  *   0 (default)  exact fp32: v_mfma_f32_16x16x4_f32;
@@ -324,6 +336,13 @@ int dh_bn_bwd_persist(const void* dout, const void* out_relu, const void* x, con
  * (native_batch_norm_backward + threshold_backward). */
 int dh_bn_apply_bits(int dtype, const void* x, const void* residual, void* y, const float* scale, const float* shift, long npix,
                      int C, int groups, int act, unsigned char* relu_bits, void* stream);
+/* dh_bn_apply / dh_bn_apply_bits (relu_bits optional) whose residual is the BatchNorm output of a block's shortcut, given as
+ * that BatchNorm's INPUT `residual` + its res_scale / res_shift [groups][C]: the value added is T(residual * res_scale +
+ * res_shift), rounded through the tensor's dtype exactly as dh_bn_apply(residual, res_scale, res_shift) would have stored it.
+ * Same y and relu_bits bit for bit; the shortcut's normalised tensor is never written or read back. */
+int dh_bn_apply_res_affine(int dtype, const void* x, const void* residual, const float* res_scale, const float* res_shift, void* y,
+                           const float* scale, const float* shift, long npix, int C, int groups, int act,
+                           unsigned char* relu_bits, void* stream);
 int dh_bn_bwd_bits(int dtype, const void* dout, const unsigned char* relu_bits, const void* x, const float* mean, const float* invstd,
                    const float* gamma, long npix, int C, int groups, void* dx, void* dres, float* dgamma, float* dbeta, int accumulate,
                    void* workspace, void* stream);
