@@ -143,6 +143,128 @@ __global__ __launch_bounds__(VC_THREADS) void xbd_val_count_kernel(const float* 
     }
 }
 
+// ---- the threshold sweep: the same pass, binned by a grid of localisation thresholds -------------------------------------------
+// Per pixel: bin = #{k : s0 > thr[k]} (0 .. T; the thresholds ascend, so s0 > thr[k] iff bin > k), arg as above, g0, and over the
+// selected pixels t = min(lbl, 4).  A workgroup counts into ONE u32 LDS histogram: (T + 1) * 8 image cells [bin][arg][g0], then
+// (T + 1) * 20 class cells [bin][arg][t]; one 64-bit integer atomic per non-zero cell and workgroup at the end.
+// Real masks are mostly background: most lanes of a wave hit one cell, and an LDS add of 64 lanes on one address is 64 adds
+// in a row.  So a thread first merges its own 4 pixels that share its first cell, and the wave merges every lane that shares
+// the first active lane's cell into one add by a wave sum; what is left adds for itself.
+constexpr int VS_MAX_T = 64;
+constexpr int VS_ICELL = 8, VS_CCELL = 20;
+constexpr int VS_MAX_CELLS = (VS_MAX_T + 1) * (VS_ICELL + VS_CCELL);
+
+struct SweepThr { float v[VS_MAX_T]; };          // by value in the kernel arguments: a recorded graph owns its thresholds
+
+// c[k]: the cell of pixel k, or -1.  Called by every lane of the wave (the shuffles read all 64).
+__device__ __forceinline__ void sweep_add4(unsigned* __restrict__ h, const int (&c)[4], int lane) {
+    int head = -1;
+#pragma unroll
+    for (int k = 3; k >= 0; --k) head = c[k] >= 0 ? c[k] : head;          // the first valid cell
+    unsigned cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cnt += c[k] == head;
+    const unsigned long long live = __ballot(head >= 0);
+    if (live == 0) return;                                                // wave-uniform
+    const int leader = __ffsll((long long)live) - 1;
+    const int lead = __shfl(head, leader, 64);
+    const bool match = head == lead;
+    const unsigned total = wave_sum_u32(match ? cnt : 0u);
+    if (lane == leader) atomicAdd(&h[lead], total);
+    else if (!match && head >= 0) atomicAdd(&h[head], cnt);
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (c[k] >= 0 && c[k] != head) atomicAdd(&h[c[k]], 1u);
+}
+
+// grid (gx, B) as xbd_val_count_kernel; the loop's trip count is the same for every lane of a workgroup
+__global__ __launch_bounds__(VC_THREADS) void xbd_val_sweep_kernel(const float* __restrict__ logits,
+                                                                   const unsigned char* __restrict__ msk0, long msk0_stride,
+                                                                   const unsigned char* __restrict__ lbl, int W, long HW,
+                                                                   SweepThr thr, int T, int select,
+                                                                   unsigned long long* __restrict__ image_hist,
+                                                                   unsigned long long* __restrict__ class_hist) {
+    __shared__ unsigned hist[VS_MAX_CELLS];
+    const int ni = (T + 1) * VS_ICELL, ncell = (T + 1) * (VS_ICELL + VS_CCELL);
+    for (int i = threadIdx.x; i < ncell; i += VC_THREADS) hist[i] = 0;
+    __syncthreads();
+    const int j = blockIdx.y, lane = threadIdx.x & 63;
+    const float* lg = logits + (long)j * 5 * HW;
+    const unsigned char* m0 = msk0 + (long)j * msk0_stride;
+    const unsigned char* lb = lbl + (long)j * HW;
+    bool vl[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) vl[c] = (reinterpret_cast<uintptr_t>(lg + c * HW) & 15) == 0;
+    const bool vm = (reinterpret_cast<uintptr_t>(m0) & 3) == 0, vb = (reinterpret_cast<uintptr_t>(lb) & 3) == 0;
+
+    const long groups = (HW + 3) >> 2;
+    for (long gb = (long)blockIdx.x * VC_THREADS; gb < groups; gb += (long)gridDim.x * VC_THREADS) {
+        const long g = gb + threadIdx.x;
+        const long p0 = g << 2;
+        const int n = g >= groups ? 0 : (HW - p0 >= 4 ? 4 : (int)(HW - p0));          // 0: a lane past the plane loads nothing
+        const bool full = n == 4;
+        float x[5][4];
+        unsigned gt[4], tg[4];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) load4(lg + c * HW + p0, full && vl[c], n, x[c]);
+        load4(m0 + p0, full && vm, n, gt);
+        load4(lb + p0, full && vb, n, tg);
+        int row = 0, col = 0;
+        if (select == 0) {
+            row = (int)(p0 / W);
+            col = (int)(p0 - (long)row * W);
+        }
+        float s0[4];
+        int ci[4], cc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            ci[k] = cc[k] = -1;
+            s0[k] = 0.f;
+            if (k < n) {
+                s0[k] = sigmoidf_(x[0][k]);
+                float best = sigmoidf_(x[1][k]);
+                unsigned arg = 0;
+#pragma unroll
+                for (int c = 2; c < 5; ++c) {
+                    const float s = sigmoidf_(x[c][k]);
+                    if (s > best) { best = s; arg = c - 1; }
+                }
+                const bool g0 = gt[k] != 0;
+                bool sel;
+                if (select == 0) {
+                    while (col >= W) { col -= W; ++row; }
+                    sel = lb[row] != 0;          // lbl[j][0][row]: H == W, so row < W
+                    ++col;
+                } else {
+                    sel = g0;
+                }
+                const unsigned t = tg[k] < 4u ? tg[k] : 4u;
+                ci[k] = (int)(arg * 2 + g0);                       // + bin * 8 below
+                cc[k] = sel ? ni + (int)(arg * 5 + t) : -1;        // + bin * 20 below
+            }
+        }
+        int bin[4] = {0, 0, 0, 0};
+#pragma unroll 4
+        for (int q = 0; q < T; ++q) {
+            const float th = thr.v[q];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) bin[k] += s0[k] > th;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (ci[k] >= 0) ci[k] += bin[k] * VS_ICELL;
+            if (cc[k] >= 0) cc[k] += bin[k] * VS_CCELL;
+        }
+        sweep_add4(hist, ci, lane);
+        sweep_add4(hist, cc, lane);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < ncell; i += VC_THREADS) {
+        const unsigned s = hist[i];
+        if (s) atomicAdd(i < ni ? image_hist + (long)j * ni + i : class_hist + (i - ni), (unsigned long long)s);
+    }
+}
+
 }  // namespace
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -175,5 +297,44 @@ extern "C" int dh_xbd_val_count(const float* logits, const unsigned char* msk0, 
                        HW, thr, select, reinterpret_cast<unsigned long long*>(image_counts),
                        reinterpret_cast<unsigned long long*>(class_counts));
     DH_CHECK_LAUNCH("xbd_val_count");
+    return 0;
+}
+
+extern "C" int dh_xbd_val_sweep(const float* logits, const unsigned char* msk0, long msk0_image_stride,
+                                const unsigned char* lbl, int B, int H, int W, const float* thr, int T, int select,
+                                long long* image_hist, long long* class_hist, void* stream) {
+    DH_REQUIRE(logits && msk0 && lbl && thr && image_hist && class_hist, "xbd_val_sweep: null pointer");
+    DH_REQUIRE(B >= 1 && B <= 65535, "xbd_val_sweep: B=%d must be in 1..65535", B);
+    DH_REQUIRE(H >= 1 && W >= 1, "xbd_val_sweep: empty image %dx%d", H, W);
+    const long HW = (long)H * W;
+    DH_REQUIRE(HW <= 0x7fffffffL, "xbd_val_sweep: %dx%d: a workgroup's 32-bit partial counts hold 2^31 - 1 pixels", H, W);
+    DH_REQUIRE(T >= 1 && T <= VS_MAX_T, "xbd_val_sweep: T=%d thresholds, must be in 1..%d", T, VS_MAX_T);
+    SweepThr th;
+    for (int k = 0; k < VS_MAX_T; ++k) th.v[k] = 2.f;          // past T: never read
+    for (int k = 0; k < T; ++k) {          // thr is host memory
+        DH_REQUIRE(thr[k] > 0.f && thr[k] < 1.f, "xbd_val_sweep: thr[%d]=%g must lie inside (0, 1)", k, (double)thr[k]);      // (nan too)
+        DH_REQUIRE(k == 0 || thr[k] > thr[k - 1], "xbd_val_sweep: thr[%d]=%g is not above thr[%d]=%g: the grid ascends strictly", k,
+                   (double)thr[k], k - 1, (double)thr[k - 1]);
+        th.v[k] = thr[k];
+    }
+    DH_REQUIRE(select == 0 || select == 1, "xbd_val_sweep: select=%d (0 reference rows, 1 building pixels)", select);
+    DH_REQUIRE(select != 0 || H == W,
+               "xbd_val_sweep: the reference's row selection indexes axis 0 by the first row and needs H == W, got %dx%d", H, W);
+    DH_REQUIRE(msk0_image_stride >= HW, "xbd_val_sweep: msk0_image_stride=%ld is less than one %dx%d plane", msk0_image_stride, H,
+               W);
+    DH_REQUIRE((reinterpret_cast<size_t>(logits) & 3) == 0 && (reinterpret_cast<size_t>(image_hist) & 7) == 0 &&
+                   (reinterpret_cast<size_t>(class_hist) & 7) == 0, "xbd_val_sweep: misaligned pointer");
+    // image_hist is written, not accumulated: cleared by the kernel dh_xbd_val_count clears with, for the same reason
+    const int ni = B * (T + 1) * VS_ICELL;
+    hipLaunchKernelGGL(xbd_val_clear_kernel, dim3(dh_cdiv(ni, VC_THREADS)), dim3(VC_THREADS), 0, ST(stream),
+                       reinterpret_cast<unsigned long long*>(image_hist), ni);
+    DH_CHECK_LAUNCH("xbd_val_sweep clear");
+    int gx = dh_cdiv((HW + 3) / 4, VC_THREADS);
+    const int cap = VC_MAX_WORKGROUPS / B > 0 ? VC_MAX_WORKGROUPS / B : 1;
+    if (gx > cap) gx = cap;
+    hipLaunchKernelGGL(xbd_val_sweep_kernel, dim3(gx, B), dim3(VC_THREADS), 0, ST(stream), logits, msk0, msk0_image_stride, lbl, W,
+                       HW, th, T, select, reinterpret_cast<unsigned long long*>(image_hist),
+                       reinterpret_cast<unsigned long long*>(class_hist));
+    DH_CHECK_LAUNCH("xbd_val_sweep");
     return 0;
 }

@@ -498,6 +498,85 @@ class GraphedXbdEvalStep:
         return self.logits
 
 
+class GraphedXbdSweepStep:
+    """GraphedXbdEvalStep for a whole grid of localisation thresholds: the eval-mode weight re-pack, the forward and
+    dh_xbd_val_sweep on its logits as ONE HIP graph -- the batch's histograms over (threshold bin, damage arg-max, truth), from
+    which models/xbd.sweep_counts gives the counts of every threshold of the grid; no host read.
+
+        step = GraphedXbdSweepStep(net, imgs, msk, lbl_msk, class_hist, thresholds)      # net.eval() is called here
+        logits = step(imgs, msk, lbl_msk)      # class_hist [T + 1, 4, 5] accumulated; step.image_hist [B, T + 1, 4, 2]: the batch's
+
+    thresholds: 1 .. ops.XBD_SWEEP_MAX floats, ascending inside (0, 1); the graph's kernel node holds them by value.  Shapes are
+    static and CHECKED as GraphedXbdEvalStep checks them: another shape raises ValueError, nothing is broadcast.  The parameters
+    are read when the graph replays."""
+
+    def __init__(self, net, imgs, msk, lbl_msk, class_hist, thresholds, select='reference', warmup=2):
+        self.net, self.class_hist, self.select = net, class_hist, select
+        self.thresholds = ops.xbd_sweep_thresholds(thresholds, "GraphedXbdSweepStep")
+        net.eval()
+        self._check(imgs, msk, lbl_msk, tuple(imgs.shape))
+        self.imgs = imgs.clone()
+        self.msk0 = self._plane0(msk).to(torch.uint8).contiguous().clone()
+        self.lbl = lbl_msk.to(torch.uint8).contiguous().clone()
+        self.image_hist = torch.zeros(imgs.shape[0], self.thresholds.size + 1, 4, 2, dtype=torch.int64, device=imgs.device)
+        net._ensure_arena(imgs.device)
+        hist0 = class_hist.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self._body()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        class_hist.copy_(hist0)                              # the warm-up batches are not part of the epoch
+        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
+        ops.rekey_workspace(imgs.device, s, cs)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cs):
+            self.logits = self._body()
+        self._pinned = ops.pin_captured_buffers(net)
+        self._generation = net._arena.generation
+        torch.cuda.synchronize()
+        class_hist.copy_(hist0)
+
+    _plane0 = staticmethod(GraphedXbdEvalStep._plane0)
+
+    @staticmethod
+    def _check(imgs, msk, lbl_msk, want):
+        """`want`: the [B, 6, H, W] the step holds; every tensor must have exactly its shape (see GraphedXbdEvalStep._check)"""
+        B, _, H, W = want
+        if imgs.dim() != 4 or imgs.shape[1] != 6 or tuple(imgs.shape) != tuple(want):
+            raise ValueError("GraphedXbdSweepStep: imgs %s, the step holds [%d, 6, %d, %d]" % (tuple(imgs.shape), B, H, W))
+        if tuple(msk.shape) not in ((B, 5, H, W), (B, H, W)):
+            raise ValueError("GraphedXbdSweepStep: msk %s is neither [%d, 5, %d, %d] nor its channel 0" % (tuple(msk.shape), B, H, W))
+        if tuple(lbl_msk.shape) != (B, H, W):
+            raise ValueError("GraphedXbdSweepStep: lbl_msk %s, the step holds [%d, %d, %d]" % (tuple(lbl_msk.shape), B, H, W))
+
+    def _body(self):
+        with torch.no_grad():
+            logits = self.net(self.imgs)
+        logits = logits.float()
+        ops.xbd_val_sweep(logits, self.msk0, self.lbl, self.image_hist, self.class_hist, self.thresholds, self.select)
+        return logits
+
+    def __call__(self, imgs=None, msk=None, lbl_msk=None):
+        if self.net._arena.generation != self._generation:
+            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this sweep step was captured; "
+                               "build a new GraphedXbdSweepStep")
+        if self.net.training:
+            raise RuntimeError("dahitra_amd: GraphedXbdSweepStep replays the eval-mode forward; call net.eval() (a train-mode "
+                               "forward in between re-packs the weights for training)")
+        if imgs is not None:
+            if msk is None or lbl_msk is None:
+                raise ValueError("GraphedXbdSweepStep: a batch is imgs, msk and lbl_msk")
+            self._check(imgs, msk, lbl_msk, tuple(self.imgs.shape))
+            self.imgs.copy_(imgs, non_blocking=True)
+            self.msk0.copy_(self._plane0(msk), non_blocking=True)
+            self.lbl.copy_(lbl_msk, non_blocking=True)
+        self.graph.replay()
+        return self.logits
+
+
 class GraphedXbdPredictStep:
     """The prediction of one batch of pre / post pairs (xBD_code/predict_test_cls.py:62-94) as ONE HIP graph:
     dh_xbd_tta_pack_u8 (the four flips of the normalised 6-channel image), the eval-mode forward at batch 4N and

@@ -10,6 +10,8 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
     validate(model, data_loader)                      xBD_code/train.py:247-290   (dice of the localisation + harmonic F1)
     evaluate_val(data_val, best_score, model, ...)    xBD_code/train.py:293-307   (the snapshot of the best score)
         the reference reads `optimizer` and the snapshot's folder from globals; here they are arguments
+    validate_sweep / evaluate_val_sweep               no counterpart: validate for a grid of localisation thresholds in one
+        epoch of forwards (the reference's scripts use 0.3, 0.5 and visualize_results.py's 0.38 / 0.13 / 0.14 by turns)
     dice(im1, im2, empty_score=1.0)                   xBD_code/utils.py:124-154   as val_score's per-image term, on counts
     predict_dir(model, test_dir, pred_folder)         xBD_code/predict_test_cls.py:58-97 (the 4-flip TTA loop and its files)
         the reference reads the two folders and its list `models` from globals; here they are arguments
@@ -254,6 +256,177 @@ def evaluate_val(batches, best_score, model, optimizer, path, current_epoch, thr
             'state_dict': model.state_dict(),
             'best_score': d,
             'optimizer': optimizer.state_dict(),
+        }, path)
+        best_score = d
+    print("score: {}\tscore_best: {}".format(d, best_score))
+    return best_score
+
+
+# ---- threshold sweep: validate for a whole grid of localisation thresholds from ONE pass ---------------------------------
+# ops.xbd_val_sweep files every pixel under bin = the number of grid thresholds its localisation sigmoid exceeds.  The thresholds
+# ascend, so "s0 > thresholds[k]" is "bin > k": a localisation rule is a bool table over (bin, arg), and the counts of
+# ops.xbd_val_count under that rule are sums of histogram cells -- int64 sums, exact, on the host, without the device.
+def sweep_loc_table(T, k):
+    """The rule `loc = s0 > thresholds[k]` as a table: bool [T + 1, 4], loc[b, a] = b > k_a.  k: one index into the grid of T
+    thresholds, or four -- one per damage arg-max a.  ValueError for an index outside 0 .. T - 1."""
+    ks = np.asarray(k)
+    if ks.dtype.kind not in "iu" or ks.shape not in ((), (4,)):
+        raise ValueError("sweep_loc_table: k %r is neither one grid index nor four" % (k,))
+    ks = np.broadcast_to(ks, (4,)).astype(np.int64)
+    if T < 1 or ks.min() < 0 or ks.max() >= T:
+        raise ValueError("sweep_loc_table: k %r is outside the grid of %d thresholds" % (k, T))
+    return np.arange(T + 1, dtype=np.int64)[:, None] > ks[None, :]
+
+
+def sweep_rule_table(thresholds, t0, t1, t2):
+    """The three-threshold rule of xBD_code/visualize_results.py:209 as a table over the grid, with dmg = arg + 1:
+        loc = (p > t0) | ((p > t1) & (dmg > 1) & (dmg < 4)) | ((p > t2) & (dmg > 1))
+    so arg 0 is kept above t0, arg 1 and arg 2 above min(t0, t1, t2), arg 3 above min(t0, t2).  Each of t0, t1, t2 must equal
+    a threshold of the grid after conversion to float32: ValueError otherwise (the histogram cannot split a bin)."""
+    thr = ops.xbd_sweep_thresholds(thresholds, "sweep_rule_table")
+    t = [np.float32(v) for v in (t0, t1, t2)]
+    for name, v in zip(("t0", "t1", "t2"), t):
+        if not (thr == v).any():
+            raise ValueError("sweep_rule_table: %s=%r is not a threshold of the grid %s" % (name, float(v), thr.tolist()))
+    per_arg = (t[0], min(t), min(t), min(t[0], t[2]))
+    return sweep_loc_table(thr.size, [int(np.nonzero(thr == v)[0][0]) for v in per_arg])
+
+
+def sweep_counts(image_hist, class_hist, loc):
+    """The counts ops.xbd_val_count would have written under the rule `loc`, from the histograms of ops.xbd_val_sweep.
+    image_hist: integers [n, T + 1, 4, 2] = [image, bin, arg, g0]; class_hist: integers [T + 1, 4, 5] = [bin, arg, t];
+    loc: bool [T + 1, 4] (sweep_loc_table / sweep_rule_table).  Returns (image_counts int64 [n, 3] = |gt0|, |loc|, |gt0 & loc|,
+    class_counts int64 [4, 3] = tp, fn, fp), the layout val_score takes.  pred(bin, arg) = arg where loc, else 0; class c has
+    tp over [pred == c][t == c], fn over [pred != c][t == c], fp over [pred == c][t != c]; t = 4 (a label above 3) is no
+    class's truth.  The histograms are additive: ranks that validate shards sum them before this call."""
+    loc = np.asarray(loc)
+    if loc.dtype != np.bool_ or loc.ndim != 2 or loc.shape[1] != 4:
+        raise ValueError("sweep_counts: loc %s %s is not a bool [T + 1, 4] table" % (loc.shape, loc.dtype))
+    nb = loc.shape[0]
+    ih = np.asarray(image_hist.cpu() if torch.is_tensor(image_hist) else image_hist).astype(np.int64)
+    ch = np.asarray(class_hist.cpu() if torch.is_tensor(class_hist) else class_hist).astype(np.int64)
+    if ih.ndim != 4 or ih.shape[1:] != (nb, 4, 2) or ch.shape != (nb, 4, 5):
+        raise ValueError("sweep_counts: image_hist %s / class_hist %s do not fit a [%d, 4] rule" % (ih.shape, ch.shape, nb))
+    image_counts = np.stack([ih[..., 1].sum(axis=(1, 2)), ih[:, loc].sum(axis=(1, 2)), ih[:, loc, 1].sum(axis=1)], axis=1)
+    pred = np.where(loc, np.arange(4, dtype=np.int64)[None, :], 0)                  # [bin, arg]
+    class_counts = np.zeros((4, 3), dtype=np.int64)
+    for c in range(4):
+        is_c = pred == c
+        class_counts[c] = ch[is_c, c].sum(), ch[~is_c, c].sum(), ch[is_c].sum() - ch[is_c, c].sum()
+    return image_counts, class_counts
+
+
+class XbdSweep:
+    """An epoch's threshold sweep (validate_sweep): `thresholds` float32 [T], `image_hist` int64 [n_images, T + 1, 4, 2],
+    `class_hist` int64 [T + 1, 4, 5] and `scores` float64 [T], scores[k] = the score validate(thr=thresholds[k]) gives."""
+
+    def __init__(self, thresholds, image_hist, class_hist):
+        self.thresholds = ops.xbd_sweep_thresholds(thresholds, "XbdSweep")
+        T = self.thresholds.size
+        self.image_hist = np.asarray(image_hist, dtype=np.int64).reshape(-1, T + 1, 4, 2)
+        self.class_hist = np.asarray(class_hist, dtype=np.int64).reshape(T + 1, 4, 5)
+        self.scores = np.array([val_score(*self.counts(k))[0] for k in range(T)], dtype=np.float64)
+
+    def counts(self, k):
+        """(image_counts [n, 3], class_counts [4, 3]) at thresholds[k]: what validate(thr=thresholds[k], want_counts=True) counts"""
+        return sweep_counts(self.image_hist, self.class_hist, sweep_loc_table(self.thresholds.size, k))
+
+    def parts(self, k):
+        """{'dice', 'f1', 'f1_per_class'} at thresholds[k] (val_score's second result)"""
+        return val_score(*self.counts(k))[1]
+
+    def best(self):
+        """(threshold, score) of the highest score: nan scores are ignored, the lowest threshold wins a tie; (None, nan) if every
+        score is nan"""
+        if np.isnan(self.scores).all():
+            return None, float('nan')
+        k = int(np.nanargmax(self.scores))          # the first maximum
+        return float(self.thresholds[k]), float(self.scores[k])
+
+    def score_rule(self, t0, t1, t2):
+        """(score, parts) under the three-threshold rule of visualize_results.py:209 (sweep_rule_table); t0, t1, t2 from the grid"""
+        return val_score(*sweep_counts(self.image_hist, self.class_hist, sweep_rule_table(self.thresholds, t0, t1, t2)))
+
+
+def _sweep_step(model, batch, class_hist, thresholds, select):
+    """the model's recorded sweep step for this batch shape, grid, selection and device (kept on the model, as _eval_step does)"""
+    from ..graph import GraphedXbdSweepStep
+    steps = model.__dict__.setdefault('_xbd_sweep_steps', {})
+    key = (tuple(batch['img'].shape), thresholds.tobytes(), select, str(batch['img'].device))
+    step = steps.get(key)
+    if step is not None and (step._generation != model._arena.generation or step.class_hist is not class_hist):
+        step = None
+    if step is None:
+        step = steps[key] = GraphedXbdSweepStep(model, batch['img'], batch['msk'], batch['lbl_msk'], class_hist, thresholds, select)
+    return step
+
+
+def validate_sweep(model, batches, thresholds, select='reference', graph=True):
+    """validate for every threshold of a grid from ONE epoch of forwards.  batches, select and graph as validate; thresholds:
+    1 .. ops.XBD_SWEEP_MAX floats inside (0, 1), strictly ascending as float32.  Per batch: the eval-mode forward and ONE
+    histogram kernel (ops.xbd_val_sweep); the batch's image rows go into the epoch's device buffer by an asynchronous device
+    copy, and the host reads ONCE when the epoch is over.  graph=True replays a GraphedXbdSweepStep for every batch of the first
+    batch's shape (recorded once per model, shape, grid, selection and device) and runs other shapes eagerly; the integers
+    are the same either way.  Prints `thr {thr}: ` and the reference's `Val Score: ...` line for every threshold and returns
+    the XbdSweep: .scores[k] is what validate(thr=thresholds[k]) returns, .best() the (threshold, score) to keep."""
+    if select not in ops.XBD_VAL_SELECT:
+        raise ValueError("validate_sweep: select %r is not one of %s" % (select, sorted(ops.XBD_VAL_SELECT)))
+    thr = ops.xbd_sweep_thresholds(thresholds, "validate_sweep")
+    T = thr.size
+    model.eval()
+    hists = model.__dict__.setdefault('_xbd_sweep_class_hist', {})
+    class_hist, rows, n, first, dev = None, None, 0, None, None
+    with torch.no_grad():
+        for batch in batches:
+            imgs, msk, lbl = batch['img'], batch['msk'], batch['lbl_msk']
+            if not imgs.is_cuda:
+                raise _lib.HipLibraryError("dahitra_amd xBD validation runs on MI355X only (no CPU fallback)")
+            B = imgs.shape[0]
+            if rows is None:
+                dev, first = imgs.device, tuple(imgs.shape)
+                class_hist = hists.get((T, str(dev)))          # one buffer per grid size: a recorded step holds its address
+                if class_hist is None:
+                    class_hist = hists[(T, str(dev))] = torch.zeros(T + 1, 4, 5, dtype=torch.int64, device=dev)
+                class_hist.zero_()
+                rows = torch.zeros(max(64, B), T + 1, 4, 2, dtype=torch.int64, device=dev)
+            if n + B > rows.shape[0]:            # an iterator does not say how long it is: the buffer doubles, on the device
+                rows = torch.cat([rows, torch.zeros(max(rows.shape[0], B), T + 1, 4, 2, dtype=torch.int64, device=dev)])
+            if graph and tuple(imgs.shape) == first:
+                step = _sweep_step(model, batch, class_hist, thr, select)
+                step(imgs, msk, lbl)
+                rows[n:n + B].copy_(step.image_hist, non_blocking=True)
+            else:
+                ops.xbd_val_sweep(model(imgs).float(), msk, lbl, rows[n:n + B], class_hist, thr, select)
+            n += B
+    if rows is None:
+        raise ValueError("validate_sweep: no batches")
+    both = torch.cat([rows[:n].reshape(-1), class_hist.reshape(-1)]).cpu().numpy()        # the epoch's one read
+    cut = n * (T + 1) * 8
+    sweep = XbdSweep(thr, both[:cut].reshape(n, T + 1, 4, 2), both[cut:].reshape(T + 1, 4, 5))
+    for k in range(T):
+        sc, parts = sweep.scores[k], sweep.parts(k)
+        f1_sc = parts['f1_per_class']
+        print("thr {}: Val Score: {}, Dice: {}, F1: {}, F1_0: {}, F1_1: {}, F1_2: {}, F1_3: {}".format(
+            str(thr[k]), sc, parts['dice'], parts['f1'], f1_sc[0], f1_sc[1], f1_sc[2], f1_sc[3]))
+    return sweep
+
+
+def evaluate_val_sweep(batches, best_score, model, optimizer, path, current_epoch, thresholds, select='reference', graph=True):
+    """evaluate_val with the grid's best threshold: validate_sweep, and when the best threshold's score beats `best_score` save
+    evaluate_val's snapshot with one more key, 'thr' (that threshold, a Python float), to `path`.  All-nan scores beat nothing.
+    Prints the `score: ... score_best: ...` line and returns the best score."""
+    model = model.eval()
+    thr, d = validate_sweep(model, batches, thresholds, select=select, graph=graph).best()
+    if d > best_score:
+        folder = os.path.dirname(path)
+        if folder:
+            os.makedirs(folder, exist_ok=True)
+        torch.save({
+            'epoch': current_epoch + 1,
+            'state_dict': model.state_dict(),
+            'best_score': d,
+            'optimizer': optimizer.state_dict(),
+            'thr': thr,
         }, path)
         best_score = d
     print("score: {}\tscore_best: {}".format(d, best_score))

@@ -9,6 +9,7 @@ import math
 import os
 import sys
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1927,38 +1928,33 @@ def adamw_xbd_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weig
 XBD_VAL_SELECT = {"reference": 0, "building": 1}
 
 
-def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select="reference"):
-    """The counts of the reference's validate() (xBD_code/train.py:258-279) for one batch, on the device, no host read.
-    logits [B, 5, H, W] fp32; msk: the batch's mask [B, 5, H, W] (channel 0 is read in place) or its localisation plane
-    [B, H, W] / msk[:, 0], uint8 as the device loader gives it; lbl [B, H, W] uint8 (classes 0 .. 3).  A long tensor (the
-    reference's dtype) is converted once.  image_counts int64 [B, 3] = |gt0|, |loc|, |gt0 & loc| is written, class_counts int64
-    [4, 3] = tp, fn, fp of each class is accumulated.  select: 'reference' (train.py:271-274: row r counts iff
-    lbl[j, 0, r] > 0; H == W) or 'building' (pixel p counts iff msk[j, 0, p] > 0).  ValueError for shapes or dtypes that do not
-    fit, before the call."""
+def _xbd_val_args(what, logits, msk, lbl, select):
+    """the tensors of xbd_val_count / xbd_val_sweep: ValueError for shapes or dtypes that do not fit.  Returns the mask plane and
+    the labels as the kernel reads them (uint8), the plane's image stride in bytes, and B, H, W"""
     if select not in XBD_VAL_SELECT:
-        raise ValueError("xbd_val_count: select %r is not one of %s" % (select, sorted(XBD_VAL_SELECT)))
+        raise ValueError("%s: select %r is not one of %s" % (what, select, sorted(XBD_VAL_SELECT)))
     if logits.dim() != 4 or logits.shape[1] != 5:
-        raise ValueError("xbd_val_count: logits %s are not [B, 5, H, W]" % (tuple(logits.shape),))
+        raise ValueError("%s: logits %s are not [B, 5, H, W]" % (what, tuple(logits.shape),))
     if logits.dtype != torch.float32:
-        raise ValueError("xbd_val_count: logits are %s, the sigmoid is taken in float32" % logits.dtype)
+        raise ValueError("%s: logits are %s, the sigmoid is taken in float32" % (what, logits.dtype))
     B, _, H, W = logits.shape
     if B < 1 or H < 1 or W < 1:
-        raise ValueError("xbd_val_count: empty logits %s" % (tuple(logits.shape),))
+        raise ValueError("%s: empty logits %s" % (what, tuple(logits.shape),))
     if msk.dim() == 4:
         if tuple(msk.shape) != (B, 5, H, W):
-            raise ValueError("xbd_val_count: msk %s does not match logits %s" % (tuple(msk.shape), tuple(logits.shape)))
+            raise ValueError("%s: msk %s does not match logits %s" % (what, tuple(msk.shape), tuple(logits.shape)))
         msk = msk[:, 0]
     if tuple(msk.shape) != (B, H, W):
-        raise ValueError("xbd_val_count: msk %s is neither [B, 5, H, W] nor [B, H, W] of logits %s"
-                         % (tuple(msk.shape), tuple(logits.shape)))
+        raise ValueError("%s: msk %s is neither [B, 5, H, W] nor [B, H, W] of logits %s"
+                         % (what, tuple(msk.shape), tuple(logits.shape)))
     if tuple(lbl.shape) != (B, H, W):
-        raise ValueError("xbd_val_count: lbl_msk %s is not [B, H, W] of logits %s" % (tuple(lbl.shape), tuple(logits.shape)))
+        raise ValueError("%s: lbl_msk %s is not [B, H, W] of logits %s" % (what, tuple(lbl.shape), tuple(logits.shape)))
     if select == "reference" and H != W:
-        raise ValueError("xbd_val_count: the reference's selection lbl_msk[j][lbl_msk[j, 0] > 0] indexes rows by the first row "
-                         "and needs H == W, got %dx%d (numpy raises IndexError there)" % (H, W))
+        raise ValueError("%s: the reference's selection lbl_msk[j][lbl_msk[j, 0] > 0] indexes rows by the first row "
+                         "and needs H == W, got %dx%d (numpy raises IndexError there)" % (what, H, W))
     for name, t in (("msk", msk), ("lbl_msk", lbl)):
         if t.dtype not in (torch.uint8, torch.int64, torch.bool):
-            raise ValueError("xbd_val_count: %s is %s, expected uint8 (or the reference's long)" % (name, t.dtype))
+            raise ValueError("%s: %s is %s, expected uint8 (or the reference's long)" % (what, name, t.dtype))
     if msk.dtype != torch.uint8:
         msk = (msk != 0).to(torch.uint8)
     if lbl.dtype != torch.uint8:
@@ -1967,6 +1963,18 @@ def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select=
     if not (msk.stride(2) == 1 and msk.stride(1) == W and (B == 1 or msk.stride(0) >= H * W)):
         msk = msk.contiguous()
     stride = msk.stride(0) if B > 1 else H * W
+    return msk, lbl, stride, B, H, W
+
+
+def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select="reference"):
+    """The counts of the reference's validate() (xBD_code/train.py:258-279) for one batch, on the device, no host read.
+    logits [B, 5, H, W] fp32; msk: the batch's mask [B, 5, H, W] (channel 0 is read in place) or its localisation plane
+    [B, H, W] / msk[:, 0], uint8 as the device loader gives it; lbl [B, H, W] uint8 (classes 0 .. 3).  A long tensor (the
+    reference's dtype) is converted once.  image_counts int64 [B, 3] = |gt0|, |loc|, |gt0 & loc| is written, class_counts int64
+    [4, 3] = tp, fn, fp of each class is accumulated.  select: 'reference' (train.py:271-274: row r counts iff
+    lbl[j, 0, r] > 0; H == W) or 'building' (pixel p counts iff msk[j, 0, p] > 0).  ValueError for shapes or dtypes that do not
+    fit, before the call."""
+    msk, lbl, stride, B, H, W = _xbd_val_args("xbd_val_count", logits, msk, lbl, select)
     if tuple(image_counts.shape) != (B, 3) or image_counts.dtype != torch.int64:
         raise ValueError("xbd_val_count: image_counts %s %s is not int64 [%d, 3]" % (tuple(image_counts.shape), image_counts.dtype, B))
     if tuple(class_counts.shape) != (4, 3) or class_counts.dtype != torch.int64:
@@ -1978,6 +1986,50 @@ def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select=
             raise _lib.HipLibraryError("xbd_val_count runs on MI355X only (no CPU fallback)")
     _call("dh_xbd_val_count", P(logits.contiguous()), _vp(msk.data_ptr()), stride, P(lbl.contiguous()), B, H, W, float(thr),
           XBD_VAL_SELECT[select], P(image_counts), P(class_counts), S())
+
+
+XBD_SWEEP_MAX = 64          # thresholds per call: they travel by value in the kernel's arguments
+
+
+def xbd_sweep_thresholds(thresholds, what="xbd_val_sweep"):
+    """a threshold grid as the kernel takes it: a contiguous float32 array of 1 .. XBD_SWEEP_MAX values inside (0, 1), strictly
+    ascending AFTER the conversion to float32 (two float64 neighbours may round to one float32).  ValueError otherwise."""
+    try:
+        thr = np.asarray(thresholds.detach().cpu().numpy() if torch.is_tensor(thresholds) else thresholds, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("%s: thresholds %r are not a sequence of numbers" % (what, thresholds))
+    if thr.ndim != 1 or not 1 <= thr.size <= XBD_SWEEP_MAX:
+        raise ValueError("%s: thresholds of shape %s, expected a 1-D sequence of 1 .. %d values" % (what, thr.shape, XBD_SWEEP_MAX))
+    thr = np.ascontiguousarray(thr)
+    if not bool(np.all((thr > 0) & (thr < 1))):          # (a nan fails too)
+        raise ValueError("%s: every threshold must lie inside (0, 1), got %s" % (what, thr.tolist()))
+    if not bool(np.all(thr[1:] > thr[:-1])):
+        raise ValueError("%s: the thresholds must ascend strictly as float32, got %s" % (what, thr.tolist()))
+    return thr
+
+
+def xbd_val_sweep(logits, msk, lbl, image_hist, class_hist, thresholds, select="reference"):
+    """xbd_val_count for a whole grid of localisation thresholds in the same single pass over the logits: instead of counting
+    against one threshold, every pixel is filed under bin = the number of thresholds its localisation sigmoid exceeds (strict,
+    float32), 0 .. T, so `bin > k` is xbd_val_count's `loc` at thresholds[k].  logits, msk, lbl and select as xbd_val_count.
+    image_hist int64 [B, T + 1, 4, 2], indexed [j, bin, arg, g0] over every pixel of image j (arg: the first maximum of the
+    damage sigmoids, g0: msk[j, 0] != 0), is written; class_hist int64 [T + 1, 4, 5], indexed [bin, arg, t] over the selected
+    pixels with t = min(lbl, 4), is accumulated.  models/xbd.sweep_counts reduces the two to xbd_val_count's counts for any
+    threshold of the grid or any per-class rule.  thresholds: 1 .. XBD_SWEEP_MAX floats, inside (0, 1) and strictly ascending as
+    float32.  ValueError for whatever does not fit, before the call."""
+    msk, lbl, stride, B, H, W = _xbd_val_args("xbd_val_sweep", logits, msk, lbl, select)
+    thr = xbd_sweep_thresholds(thresholds)
+    T = int(thr.size)
+    if tuple(image_hist.shape) != (B, T + 1, 4, 2) or image_hist.dtype != torch.int64:
+        raise ValueError("xbd_val_sweep: image_hist %s %s is not int64 [%d, %d, 4, 2]"
+                         % (tuple(image_hist.shape), image_hist.dtype, B, T + 1))
+    if tuple(class_hist.shape) != (T + 1, 4, 5) or class_hist.dtype != torch.int64:
+        raise ValueError("xbd_val_sweep: class_hist %s %s is not int64 [%d, 4, 5]" % (tuple(class_hist.shape), class_hist.dtype, T + 1))
+    for t in (logits, msk, lbl, image_hist, class_hist):
+        if not t.is_cuda:
+            raise _lib.HipLibraryError("xbd_val_sweep runs on MI355X only (no CPU fallback)")
+    _call("dh_xbd_val_sweep", P(logits.contiguous()), _vp(msk.data_ptr()), stride, P(lbl.contiguous()), B, H, W, _vp(thr.ctypes.data),
+          T, XBD_VAL_SELECT[select], P(image_hist), P(class_hist), S())
 
 
 # ---- xBD prediction: 4-flip test-time augmentation (csrc/xbd_predict.hip) ---------------------------------

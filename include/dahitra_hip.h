@@ -748,6 +748,19 @@ int dh_adamw_xbd_step_graph(float* param, const float* grad, float* exp_avg, flo
  * Refused (nothing is written): a null pointer, B < 1, thr outside (0, 1), select 0 with H != W, H * W >= 2^31. */
 int dh_xbd_val_count(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl, int B,
                      int H, int W, float thr, int select, long long* image_counts, long long* class_counts, void* stream);
+/* The same pass for a whole grid of localisation thresholds: thr is a HOST pointer to T float32 values, 1 <= T <= 64, each
+ * inside (0, 1), strictly ascending; they are read during the call and travel by value in the kernel's arguments (a recorded
+ * graph owns its copy; there is no device table).  Per pixel: bin = the number of k with s0 > thr[k] (strict, float32), 0 .. T;
+ * arg = the first maximum of the fp32 sigmoids of channels 1 .. 4, 0 .. 3; g0 = msk0 != 0; t = min(lbl, 4) (a label above 3 is
+ * "other": never a tp or fn, an fp of the predicted class, as dh_xbd_val_count's comparisons have it).  Same sigmoid, loads
+ * and selection code as dh_xbd_val_count, so loc = (bin > k) is that call's s0 > thr[k] bit for bit.
+ * image_hist [B][T + 1][4][2], indexed [j][bin][arg][g0] over every pixel of image j, is WRITTEN (cleared by a kernel, no memset
+ * node); class_hist [T + 1][4][5], indexed [bin][arg][t] over the selected pixels, is ACCUMULATED.  All integer, exact.
+ * Refused (nothing is launched or written): whatever dh_xbd_val_count refuses, thr NULL, T outside 1..64, a threshold outside
+ * (0, 1) or NaN, thresholds that do not ascend strictly. */
+int dh_xbd_val_sweep(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl, int B,
+                     int H, int W, const float* thr, int T, int select, long long* image_hist, long long* class_hist,
+                     void* stream);
 
 /* ---- xBD prediction: the 4-flip test-time augmentation (xBD_code/predict_test_cls.py:60-94; csrc/xbd_predict.hip) ----------
  * flip_0 = identity, flip_1 reverses the rows, flip_2 the columns, flip_3 both (each its own inverse).
