@@ -43,6 +43,9 @@ struct Lds {
     float *x, *xn, *qkv, *p, *o, *x1, *x1n, *z, *h, *xh1, *xh2, *st, *red;
 };
 // red: [8][n][32] scratch of the split reductions
+// Every buffer starts at a multiple of 4 floats: l.o (behind the heads*n*n probabilities), the backward's d_o / dx1 / dS and the
+// buffers behind l.z / l.h (n*mlp each) are read with 16-byte LDS loads.  n*32 and n*inner (inner % 16 == 0) are multiples of 4
+// for any n; the two other terms are only when (heads*n*n) % 4 == 0 && (n*mlp) % 4 == 0 -- dh_encoder_supported refuses the rest.
 __device__ __forceinline__ Lds carve(float* sm, int n, int inner, int heads, int mlp) {
     Lds l;
     l.x = sm; sm += n * D;
@@ -62,7 +65,8 @@ __device__ __forceinline__ Lds carve(float* sm, int n, int inner, int heads, int
 }
 // floats of one saved (layer, image) record: the forward's LDS image up to (not including) the reduction scratch --
 // layer input, both LayerNorm outputs / normalised values / statistics, qkv, probabilities, attention output,
-// MLP pre-activations and activations
+// MLP pre-activations and activations.  A multiple of 4 (the record is copied as float4s, and record after record stays
+// 16-byte aligned) under the condition stated at carve(): (heads*n*n) % 4 == 0 && (n*mlp) % 4 == 0.
 __host__ __device__ static inline size_t saved_img_floats(int n, int inner, int heads, int mlp) {
     return (size_t)n * D * 6 + (size_t)n * 3 * inner + (size_t)heads * n * n + (size_t)n * inner + 2 * (size_t)n * mlp + 4 * n;
 }
@@ -705,6 +709,7 @@ extern "C" int dh_encoder_batch_abort() { g_eb.on = false; g_eb.nf = g_eb.nb = 0
 // largest inner width whose backward working set (forward buffers + gradient scratch) fits the 160 KB LDS
 extern "C" int dh_encoder_supported(int n, int heads, int dim_head, int mlp) {
     if (n < 1 || n > MAXN || mlp > 64 || mlp < 1 || heads < 1 || dim_head % 16) return 0;      // (16-byte LDS reads of a quarter head)
+    if ((heads * n * n) % 4 || (n * mlp) % 4) return 0;      // carve(): 16-byte alignment of every LDS buffer and saved record
     const int inner = heads * dim_head;
     const size_t bwd = (fwd_lds_floats(n, inner, heads, mlp) + (size_t)n * D * 4 + (size_t)n * mlp + (size_t)n * inner +
                         (size_t)n * 3 * inner + (size_t)heads * n * n) * 4;

@@ -560,7 +560,8 @@ int dh_self_attn_bwd(int dtype, const void* qkv, const float* attn, const void* 
  * image pair, fp32: one workgroup per image and direction + one launch for all parameter gradients.  x, y, dy, dx:
  * [B][n][32]; parameters are the first layer's pointers in torch layouts (to_qkv [3*inner][32], to_out [32][inner],
  * net.0 [mlp][32], net.3 [32][mlp]), consecutive layers param_stride floats apart; gradients are accumulated.
- * dh_encoder_supported: 1 when the shape fits the kernels (n <= 8, mlp <= 64, working set within the 160 KB LDS). */
+ * dh_encoder_supported: 1 when the shape fits the kernels (n <= 8, mlp <= 64, dim_head % 16 == 0, heads*n*n and n*mlp multiples
+ * of 4 -- every LDS buffer and saved record 16-byte aligned --, working set within the 160 KB LDS). */
 int dh_encoder_supported(int n, int heads, int dim_head, int mlp);
 int dh_encoder_fwd(const float* x, float* y, float* saved_inputs, int B, int n, int depth, int heads, int dim_head,
                    int mlp, float scale, float eps, long param_stride, const float* ln1_g, const float* ln1_b,
