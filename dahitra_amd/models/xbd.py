@@ -18,8 +18,10 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
     visualize_dir(model, test_dir, mask_dir, out_dir) xBD_code/visualize_results.py:171-223 (pre | post | truth | prediction PNGs)
         damage_map / visual_grid are its lines 206-211 / 213-220 on device tensors; the folders are arguments here too, and
         the localisation probability is channel 0 of the same prediction (the script's separate localisation net is not built)
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_visual.hip +
-the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
+    buildings / building_damage / building_confusion / building_f1   no counterpart: connected components of a class map, one
+        damage class per building by vote, and the building-level confusion and F1 against the ground truth
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_visual.hip,
+csrc/xbd_buildings.hip + the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
 import numpy as np
@@ -615,3 +617,105 @@ def visualize_dir(model, test_dir, mask_dir, out_dir, model_str='TUNet', crop=51
         Image.fromarray(grid).save(os.path.join(out_dir, visual_name(f, model_str)), format='PNG', compress_level=9)
         written.append(f)
     return written
+
+
+# ---- buildings: components, votes and the building-level score (no counterpart in the reference; csrc/xbd_buildings.hip) -----
+def _device_u8(what, *tensors):
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise _lib.HipLibraryError("dahitra_amd xBD %s runs on MI355X only (no CPU fallback)" % what)
+
+
+def buildings(key_u8, connectivity=8, keyed=False):
+    """Connected components of a class map on the device: key_u8 [N, H, W] uint8 -> (labels [N, H, W] int32, count [N] int32).
+    Neighbouring pixels (connectivity 4 or 8) form one building when both are nonzero, with keyed=True when they are nonzero and
+    equal (touching ground-truth buildings of different classes stay apart).  0 is the background; the buildings of each image
+    are numbered 1 .. count[n] in raster order of their first pixel, scipy.ndimage.label's numbering (ops.xbd_cc_label)."""
+    _device_u8("buildings", key_u8)
+    return ops.xbd_cc_label(key_u8, connectivity, keyed)
+
+
+class XbdBuildings:
+    """What building_damage returns, all on the device: labels [N, H, W] int32, count [N] int32, table [N, max_buildings, 10]
+    int32 (ops.xbd_cc_stats' rows: area, h0 .. h4, y0, x0, y1, x1), cls [N, max_buildings] uint8 and map [N, H, W] uint8, the
+    map with one class per building.  rows(n) copies image n's buildings to the host."""
+
+    def __init__(self, labels, count, table, cls, map, counts_host):
+        self.labels, self.count, self.table, self.cls, self.map = labels, count, table, cls, map
+        self._counts = counts_host
+
+    def rows(self, n):
+        """(table rows [count[n], 10] int32, classes [count[n]] uint8) of image n as numpy arrays"""
+        k = int(self._counts[n])
+        return self.table[n, :k].cpu().numpy(), self.cls[n, :k].cpu().numpy()
+
+
+def _check_count(what, count, max_buildings):
+    """the one read of `count`: ValueError when an image has more components than the table has rows"""
+    counts = count.cpu().numpy()
+    if counts.size and int(counts.max()) > max_buildings:
+        raise ValueError("%s: an image has %d components, more than max_buildings=%d" % (what, int(counts.max()), max_buildings))
+    return counts
+
+
+def building_damage(msk_u8, loc=ops.XBD_LOC_THR, footprint=None, connectivity=8, min_area=0, max_buildings=4096):
+    """One damage class per building from a prediction msk_u8 [N, H, W, 5] uint8 (predict_tta's tensor), on the device.
+    The footprint is damage_map(msk_u8, loc) != 0, or the given [N, H, W] uint8 map (nonzero = building); its components
+    (connectivity 4 or 8) are the buildings.  Every footprint pixel votes with damage_map(msk_u8, None), and a building's class
+    is the first maximum of its votes for 1 .. 4; buildings of fewer than min_area pixels get class 0.  Returns an XbdBuildings.
+    loc=None without a footprint is a ValueError (the whole tile would be one building), and so is an image with more than
+    max_buildings components (count is read once, after the labelling)."""
+    what = "building_damage"
+    _device_u8("building damage", msk_u8, *(() if footprint is None else (footprint,)))
+    if footprint is None and loc is None:
+        raise ValueError("%s: loc=None without a footprint makes the whole tile one building" % what)
+    ops._cc_cap(what, max_buildings)
+    vote = ops.xbd_damage_map(msk_u8, None)
+    if footprint is None:
+        footprint = ops.xbd_damage_map(msk_u8, loc)
+    elif not (footprint.dtype == torch.uint8 and tuple(footprint.shape) == tuple(vote.shape)):
+        raise ValueError("%s: footprint %s %s is not uint8 %s like msk_u8" % (what, tuple(footprint.shape), footprint.dtype,
+                                                                            list(vote.shape)))
+    labels, count = ops.xbd_cc_label(footprint, connectivity, False)
+    table = ops.xbd_cc_stats(labels, vote, max_buildings)
+    cls = ops.xbd_cc_vote(table, min_area, "damage")
+    painted = ops.xbd_cc_paint(labels, cls)
+    counts = _check_count(what, count, max_buildings)
+    return XbdBuildings(labels, count, table, cls, painted, counts)
+
+
+def building_confusion(pred_map_u8, gt_u8, connectivity=8, max_buildings=4096):
+    """The building-level confusion of a predicted class map against the ground truth, np.int64 [4, 5]: the ground-truth
+    buildings are the keyed components of gt_u8 [N, H, W] uint8 (classes 0 .. 4; a label above 4 raises KeyError, as visual_grid
+    does), each predicted as the first maximum of pred_map_u8's classes 0 .. 4 over its pixels (0: missed); [g - 1, p] counts the
+    buildings of class g predicted p.  Confusions of batches add.  ValueError for an image with more than max_buildings
+    ground-truth buildings."""
+    what = "building_confusion"
+    _device_u8("building confusion", pred_map_u8, gt_u8)
+    ops._cc_cap(what, max_buildings)
+    _check_labels(gt_u8)
+    labels, count = ops.xbd_cc_label(gt_u8, connectivity, True)
+    pred = ops.xbd_cc_vote(ops.xbd_cc_stats(labels, pred_map_u8, max_buildings), 0, "all")
+    truth = ops.xbd_cc_vote(ops.xbd_cc_stats(labels, gt_u8, max_buildings), 0, "all")     # a keyed component has one class
+    counts = _check_count(what, count, max_buildings)
+    pred, truth = pred.cpu().numpy(), truth.cpu().numpy()
+    conf = np.zeros((4, 5), dtype=np.int64)
+    for n, k in enumerate(counts):
+        np.add.at(conf, (truth[n, :k].astype(np.int64) - 1, pred[n, :k].astype(np.int64)), 1)
+    return conf
+
+
+def building_f1(confusion):
+    """(the four per-class F1 values, their harmonic mean) of a building_confusion [4, 5], as val_score forms them: for class c,
+    tp = [c - 1, c], fn = the rest of the row, fp = the rest of column c; f1_sc = 2 tp / (2 tp + fp + fn), nan for 0 / 0;
+    f1 = 4 / sum(1 / (f1_sc + 1e-6))."""
+    conf = np.asarray(confusion).astype(np.float64).reshape(4, 5)
+    f1_sc = np.zeros((4,))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for c in range(1, 5):
+            tp = conf[c - 1, c]
+            fn = conf[c - 1].sum() - tp
+            fp = conf[:, c].sum() - tp
+            f1_sc[c - 1] = 2 * tp / (2 * tp + fp + fn)
+        f1 = 4 / np.sum(1.0 / (f1_sc + 1e-6))
+    return f1_sc, f1

@@ -2185,6 +2185,138 @@ def xbd_vis_grid(pre_u8, post_u8, gt_u8, msk_u8, loc=None, out=None):
     return out
 
 
+# ---- xBD buildings: components, statistics, vote, paint (csrc/xbd_buildings.hip) --------------------------
+XBD_CC_TILE = (32, 64)           # (TH, TW) of the tile-local pass: dh_xbd_cc_tile_h / dh_xbd_cc_tile_w
+XBD_CC_COLS = 10                 # area, h0 .. h4, y0, x0, y1, x1
+XBD_CC_MODES = {"damage": 0, "all": 1}
+
+
+def _cc_tensors(what, named, device=None):
+    """named: (name, tensor, dtype, shape or None, text).  Rank, dtype and shape of every argument first, then device and
+    storage: ValueError, before any launch."""
+    for name, t, dtype, shape, text in named:
+        if not torch.is_tensor(t) or t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
+            raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
+                                                            str(dtype).replace("torch.", ""), text))
+    device = named[0][1].device if device is None else device
+    for name, t, _, _, _ in named:
+        if not t.is_cuda or t.device != device:
+            raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device" % (what, name, t.device))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
+
+
+def _cc_image(what, name, t, dtype):
+    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 3 or t.numel() == 0:
+        raise ValueError("%s: %s %s %s is not a non-empty %s [N, H, W]" % (what, name, tuple(getattr(t, "shape", ())),
+                                                                          getattr(t, "dtype", type(t)), str(dtype).replace("torch.", "")))
+    return tuple(t.shape)
+
+
+def _cc_cap(what, cap):
+    if isinstance(cap, bool) or not isinstance(cap, int) or cap < 1:
+        raise ValueError("%s: cap %r is not an integer >= 1" % (what, cap))
+
+
+def xbd_cc_ws_bytes(N, H, W):
+    """bytes of the workspace xbd_cc_label needs for [N, H, W]: parents int32 [N, H W] + block counts [N, ceil(H W / 1024)]"""
+    n = ctypes.c_long(0)
+    if _lib.lib().dh_xbd_cc_ws_bytes(N, H, W, ctypes.byref(n)) != 0:
+        raise ValueError(_lib.lib().dh_last_error().decode())
+    return int(n.value)
+
+
+def xbd_cc_label(key_u8, connectivity=8, keyed=False, out=None, ws=None):
+    """Connected components on the device.  key_u8 [N, H, W] uint8 -> (labels [N, H, W] int32, count [N] int32).  Neighbours
+    (connectivity 4, or 8 with the diagonals) belong together when both keys are nonzero, with keyed=True when they are nonzero
+    and equal.  labels is 0 where the key is 0 and 1 .. count[n] elsewhere, numbered per image in raster order of each
+    component's first pixel -- scipy.ndimage.label's numbering.  Six launches whatever the data, nothing read back, bit-exact.
+    out: (labels, count) buffers to write into.  ws: a uint8 device buffer of xbd_cc_ws_bytes(N, H, W) bytes or more (default:
+    a fresh one).  ValueError, before any launch, for a wrong rank, dtype or device, non-contiguous storage, a connectivity
+    other than 4 or 8 or an `out` / `ws` that does not fit."""
+    what = "xbd_cc_label"
+    if connectivity not in (4, 8):
+        raise ValueError("%s: connectivity %r is neither 4 nor 8" % (what, connectivity))
+    N, H, W = _cc_image(what, "key_u8", key_u8, torch.uint8)
+    named = [("key_u8", key_u8, torch.uint8, None, "[N, H, W]")]
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 2):
+            raise ValueError("%s: out is a pair (labels, count)" % what)
+        named += [("out[0]", out[0], torch.int32, (N, H, W), "labels %s" % [N, H, W]), ("out[1]", out[1], torch.int32, (N,), "count %s" % [N])]
+    if ws is not None:
+        named.append(("ws", ws, torch.uint8, None, "workspace"))
+    _cc_tensors(what, named)
+    need = xbd_cc_ws_bytes(N, H, W)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=key_u8.device)
+    elif ws.numel() < need or ws.data_ptr() % 4:
+        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
+    labels, count = out if out is not None else (torch.empty(N, H, W, dtype=torch.int32, device=key_u8.device),
+                                                 torch.empty(N, dtype=torch.int32, device=key_u8.device))
+    _call("dh_xbd_cc_label", _vp(key_u8.data_ptr()), N, H, W, connectivity, int(bool(keyed)), _vp(labels.data_ptr()),
+          _vp(count.data_ptr()), _vp(ws.data_ptr()), ws.numel(), S())
+    return labels, count
+
+
+def xbd_cc_stats(labels, vote_u8, cap, out=None):
+    """Per-component statistics: labels [N, H, W] int32 (xbd_cc_label's), vote_u8 [N, H, W] uint8, cap >= 1 -> table
+    [N, cap, 10] int32; row i describes label i + 1: area, h0 .. h4 (pixels whose vote is 0 .. 4; a larger byte counts in the area
+    only), y0, x0, y1, x1 (inclusive box).  Rows of labels that do not exist: area 0, h 0, y0 = H, x0 = W, y1 = x1 = -1.  Labels
+    above cap are ignored.  Every int of the table is written.  out: a [N, cap, 10] int32 buffer to write into."""
+    what = "xbd_cc_stats"
+    _cc_cap(what, cap)
+    N, H, W = _cc_image(what, "labels", labels, torch.int32)
+    named = [("labels", labels, torch.int32, None, "[N, H, W]"), ("vote_u8", vote_u8, torch.uint8, (N, H, W), "%s like labels" % [N, H, W])]
+    if out is not None:
+        named.append(("out", out, torch.int32, (N, cap, XBD_CC_COLS), str([N, cap, XBD_CC_COLS])))
+    _cc_tensors(what, named)
+    if out is None:
+        out = torch.empty(N, cap, XBD_CC_COLS, dtype=torch.int32, device=labels.device)
+    _call("dh_xbd_cc_stats", _vp(labels.data_ptr()), _vp(vote_u8.data_ptr()), N, H, W, cap, _vp(out.data_ptr()), S())
+    return out
+
+
+def xbd_cc_vote(table, min_area=0, mode="damage", out=None):
+    """The class of every table row: table [N, cap, 10] int32 -> cls [N, cap] uint8.  mode 'damage': 1 + the first maximum of
+    h1 .. h4, 0 when all four are zero; mode 'all': the first maximum of h0 .. h4; a tie goes to the lowest class.  Rows with
+    area 0 or area < min_area get 0.  out: a [N, cap] uint8 buffer to write into."""
+    what = "xbd_cc_vote"
+    if mode not in XBD_CC_MODES:
+        raise ValueError("%s: mode %r is neither 'damage' nor 'all'" % (what, mode))
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 0:
+        raise ValueError("%s: min_area %r is not an integer >= 0" % (what, min_area))
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 3 or table.shape[2] != XBD_CC_COLS or table.numel() == 0:
+        raise ValueError("%s: table %s %s is not a non-empty int32 [N, cap, %d]" % (what, tuple(getattr(table, "shape", ())),
+                                                                                   getattr(table, "dtype", type(table)), XBD_CC_COLS))
+    N, cap = table.shape[:2]
+    named = [("table", table, torch.int32, None, "")]
+    if out is not None:
+        named.append(("out", out, torch.uint8, (N, cap), str([N, cap])))
+    _cc_tensors(what, named)
+    if out is None:
+        out = torch.empty(N, cap, dtype=torch.uint8, device=table.device)
+    _call("dh_xbd_cc_vote", _vp(table.data_ptr()), N, cap, min_area, XBD_CC_MODES[mode], _vp(out.data_ptr()), S())
+    return out
+
+
+def xbd_cc_paint(labels, cls_u8, out=None):
+    """The one-class-per-component map: labels [N, H, W] int32, cls_u8 [N, cap] uint8 -> [N, H, W] uint8, cls_u8[n, l - 1] for a
+    pixel with label l, 0 for l = 0 or l > cap.  Every byte is written.  out: a [N, H, W] uint8 buffer to write into."""
+    what = "xbd_cc_paint"
+    N, H, W = _cc_image(what, "labels", labels, torch.int32)
+    if not torch.is_tensor(cls_u8) or cls_u8.dtype != torch.uint8 or cls_u8.dim() != 2 or cls_u8.shape[0] != N or cls_u8.shape[1] < 1:
+        raise ValueError("%s: cls_u8 %s %s is not uint8 [%d, cap >= 1]" % (what, tuple(getattr(cls_u8, "shape", ())),
+                                                                          getattr(cls_u8, "dtype", type(cls_u8)), N))
+    named = [("labels", labels, torch.int32, None, ""), ("cls_u8", cls_u8, torch.uint8, None, "")]
+    if out is not None:
+        named.append(("out", out, torch.uint8, (N, H, W), str([N, H, W])))
+    _cc_tensors(what, named)
+    if out is None:
+        out = torch.empty(N, H, W, dtype=torch.uint8, device=labels.device)
+    _call("dh_xbd_cc_paint", _vp(labels.data_ptr()), _vp(cls_u8.data_ptr()), N, H, W, cls_u8.shape[1], _vp(out.data_ptr()), S())
+    return out
+
+
 # ---- the change-detection evaluator's picture (csrc/cd_visual.hip) -----------------------------------------
 def cd_vis_shape(N, H, W):
     """the shape of the evaluator's picture of N images H x W: make_grid's min(8, N) tiles per row, padding 0, four bands"""

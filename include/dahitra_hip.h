@@ -800,6 +800,44 @@ int dh_xbd_damage_map_u8(const unsigned char* msk, int N, int H, int W, int use_
 int dh_xbd_vis_grid_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* gt, const unsigned char* msk,
                        int N, int H, int W, int use_loc, int b0, int b1, int b2, unsigned char* grid, void* stream);
 
+/* ---- xBD buildings: connected components, statistics, vote and the painted map (csrc/xbd_buildings.hip) ----------------------
+ * Beyond the reference (which stops at pixels).  All integer, bit-exact, independent of launch order and scheduling.
+ * dh_xbd_cc_label: key [N][H][W] uint8 -> labels [N][H][W] int32, count [N] int32.  Two pixels that are neighbours (conn 4:
+ *   left / right / up / down; conn 8: and the diagonals) belong together when both keys are nonzero (keyed == 0), or nonzero and
+ *   equal (keyed == 1).  labels is 0 where key == 0, elsewhere 1 .. K_n per image, the components numbered in raster order of
+ *   their first pixel (minimum linear index): scipy.ndimage.label's numbering; count[n] = K_n.  Images are independent.
+ *   Union-find with union-by-minimum-index in six launches, their number and grids fixed by the shape: a tile pass in LDS
+ *   (dh_xbd_cc_tile_h() x dh_xbd_cc_tile_w() pixels per workgroup), a pass that unites across tile borders with agent-scope
+ *   atomicMin (parents read with agent-scope relaxed atomic loads), a flatten pass that also counts the roots per block of 1024
+ *   pixels, a one-workgroup-per-image scan of those counts, root ids, and the write of every label.  No workgroup waits for
+ *   another and nothing is read back to the host: the sequence can be captured in a graph.
+ *   ws: the caller's workspace of at least 4 N (H W + ceil(H W / 1024)) bytes (dh_xbd_cc_ws_bytes writes that number to
+ *   *bytes, a host pointer), 4-byte aligned
+ *   (parents [N][H W] int32, then block counts); its content before and after the call is meaningless, nothing needs clearing.
+ * dh_xbd_cc_stats: labels, vote [N][H][W] uint8, cap >= 1 -> table [N][cap][10] int32; row i describes label i + 1:
+ *   area, h0 .. h4 (pixels with vote == 0 .. 4; a vote byte above 4 counts in area only), y0, x0, y1, x1 (inclusive box).
+ *   A row whose label does not exist is area = 0, h = 0, y0 = H, x0 = W, y1 = x1 = -1.  Labels above cap (or below 1) are
+ *   ignored.  Two launches: one writes every int of the table, one accumulates with integer atomics (add, min, max), reduced
+ *   per wave and label with ballots and per workgroup (one tile of the local pass) in LDS before the table is touched.
+ * dh_xbd_cc_vote: table, min_area >= 0, mode -> cls [N][cap] uint8.  mode 0 (damage): 1 + the first maximum of h1 .. h4, 0 when
+ *   all four are zero; mode 1 (all): the first maximum of h0 .. h4.  A tie goes to the lowest class.  A row with area == 0 or
+ *   area < min_area gets 0.  One launch.
+ * dh_xbd_cc_paint: out [N][H][W] uint8 = cls[n][l - 1] for a pixel with label l, 0 when l < 1 or l > cap.  One launch, every byte
+ *   written.
+ * key, vote, cls and out may start at any byte; labels, count, table and ws are 4-byte aligned.
+ * Refused (nothing is written, non-zero, dh_last_error begins with xbd_cc_label / xbd_cc_stats / xbd_cc_vote / xbd_cc_paint):
+ * a null pointer, N < 1, N > 65535, H < 1, W < 1, H * W >= 2^31, conn outside {4, 8}, keyed or mode outside {0, 1}, cap < 1,
+ * cap > 2^24, N * cap > 2^28, min_area < 0, ws_bytes below the query, a misaligned int32 pointer.  dh_xbd_cc_ws_bytes refuses
+ * the same shapes (its message begins with xbd_cc_ws_bytes). */
+int dh_xbd_cc_tile_h(void);
+int dh_xbd_cc_tile_w(void);
+int dh_xbd_cc_ws_bytes(int N, int H, int W, long* bytes);
+int dh_xbd_cc_label(const unsigned char* key, int N, int H, int W, int conn, int keyed, int* labels, int* count, void* ws,
+                    long ws_bytes, void* stream);
+int dh_xbd_cc_stats(const int* labels, const unsigned char* vote, int N, int H, int W, int cap, int* table, void* stream);
+int dh_xbd_cc_vote(const int* table, int N, int cap, int min_area, int mode, unsigned char* cls, void* stream);
+int dh_xbd_cc_paint(const int* labels, const unsigned char* cls, int N, int H, int W, int cap, unsigned char* out, void* stream);
+
 /* ---- the change-detection evaluator's picture (models/evaluator.py:118-131; csrc/cd_visual.hip) ------------------------------
  * dh_cd_eval_vis_u8: A, B [N][3][H][W] fp32 (as the net receives them), logits [N][C][H][W] fp32, label [N][H][W] int64 ->
  * out [4 * rows * H][cols * W][3] uint8 RGB, cols = min(8, N), rows = ceil(N / cols) (make_grid, padding 0): four bands of
