@@ -1,7 +1,7 @@
 // Buildings from an xBD class map: connected components, per-component statistics, the vote and the painted map.  All integer.
 //   key [N][H][W] uint8 -> labels [N][H][W] int32 (0 background, 1 .. K_n in raster order of each component's first pixel: the
 //   numbering of scipy.ndimage.label) and count [N] = K_n; then table [N][cap][10], cls [N][cap], out [N][H][W] (contracts:
-//   include/dahitra_hip.h).
+//   include/dahitra_hip.h).  Further down: two label maps matched by IoU, match_a [N][cap_a][5] and match_b [N][cap_b].
 //
 // Labelling is union-find with union-by-minimum-index in SIX launches whose number and grids depend on the shape alone:
 //   1 cc_tile_kernel     one workgroup per CC_TH x CC_TW tile, in LDS.  A wave holds one tile row: the horizontal runs come from
@@ -398,9 +398,196 @@ __global__ __launch_bounds__(CC_THREADS) void cc_paint_kernel(const int* __restr
     }
 }
 
+// ---- matching two label maps -----------------------------------------------------------------------------------------------
+// A [N][H][W] (labels 1 .. cap_a) against B (1 .. cap_b): for every label a the label of B that covers more than half of it, and
+// whether the two match above an IoU of num / den.  No table of pairs: with NB = bit_length(cap_b), a row of NB + 1 counters per
+// label a (its area, and for every bit k the pixels of a whose B label has bit k set) names the ONLY label that can cover more
+// than half of a -- each of its set bits is counted more than area / 2 times, each of its clear bits fewer -- and a second pass
+// counts the pixels of a that carry that candidate, which is what decides.  Five launches, grids fixed by the shapes:
+//   1 match_init_kernel    zeroes the workspace and match_b
+//   2 match_count_kernel   the pixels, once: rows [area, ones_0 .. ones_NB-1] of A and the areas of B
+//   3 match_cand_kernel    cand(a) = OR_k (2 ones_k > area) << k
+//   4 match_verify_kernel  the pixels again: inter(a) = pixels with A == a, B == cand(a)
+//   5 match_decide_kernel  the five columns of match_a, and match_b[match - 1] = a (one writer: the match is one-to-one)
+// The two pixel passes have the tile and wave shape of cc_stats_kernel, and its LDS slots.
+// Workspace, int32: rows [N][cap_a][NB + 1], area_b [N][cap_b], cand [N][cap_a], inter [N][cap_a].
+constexpr int MATCH_COLS = 5;
+constexpr int MATCH_MAX_BITS = 25;            // bit_length(CC_MAX_CAP)
+constexpr int MATCH_ROW = MATCH_MAX_BITS + 1;
+static_assert(MATCH_ROW <= 32, "the count pass flushes a slot with 32 lanes");
+
+__host__ __device__ inline int match_bits(int cap_b) {
+    int nb = 0;
+    while (nb < 31 && (cap_b >> nb)) ++nb;
+    return nb;
+}
+__host__ __device__ inline long match_ws_words(long N, long cap_a, long cap_b) {
+    return N * (cap_a * (match_bits((int)cap_b) + 3) + cap_b);
+}
+
+__global__ __launch_bounds__(CC_THREADS) void match_init_kernel(int* __restrict__ ws, long ws_words, int* __restrict__ match_b,
+                                                                long b_words) {
+    const long i = (long)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i < ws_words) ws[i] = 0;
+    else if (i - ws_words < b_words) match_b[i - ws_words] = 0;
+}
+
+// grid (tiles of an image, N).  A wave holds 64 consecutive pixels of one image row.  Once per row, lane k + 1 takes the ballot of
+// bit k of the 64 B labels and lane 0 all ones.  Then one turn per distinct label of A among the pixels: the ballot of the
+// label's lanes, ANDed with what a lane holds and counted, is the area in lane 0 and ones_k in lane k + 1, so a turn costs one
+// popcount whatever NB is, and the NB + 1 counters of the partial row go to the LDS slot (or, when the slot is another label's,
+// straight to the table) in ONE atomic instruction of NB + 1 lanes.  Then one turn per distinct label of B for its area,
+// through a second slot array.
+__global__ __launch_bounds__(CC_THREADS) void match_count_kernel(const int* __restrict__ la, const int* __restrict__ lb, int H, int W,
+                                                                 int tiles_x, int cap_a, int cap_b, int nb, int* rows, int* area_b) {
+    __shared__ int tag_a[CC_SLOTS], tag_b[CC_SLOTS];
+    __shared__ int acc_a[CC_SLOTS][MATCH_ROW];
+    __shared__ int acc_b[CC_SLOTS];
+    const long hw = (long)H * W;
+    const int* A = la + (long)blockIdx.y * hw;
+    const int* B = lb + (long)blockIdx.y * hw;
+    const int rw = nb + 1;
+    int* R = rows + (long)blockIdx.y * cap_a * rw;
+    int* AB = area_b + (long)blockIdx.y * cap_b;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int y0 = ty * CC_TH, x0 = tx * CC_TW;
+    const int lane = threadIdx.x & 63;
+    for (int s = threadIdx.x; s < CC_SLOTS; s += CC_THREADS) tag_a[s] = tag_b[s] = acc_b[s] = 0;
+    for (int j = threadIdx.x; j < CC_SLOTS * MATCH_ROW; j += CC_THREADS) (&acc_a[0][0])[j] = 0;
+    __syncthreads();
+#pragma unroll 1
+    for (int i = threadIdx.x; i < CC_TH * CC_TW; i += CC_THREADS) {
+        const int y = y0 + i / CC_TW, x = x0 + lane;            // i % CC_TW == lane
+        const bool in = y < H && x < W;
+        int a = in ? A[(long)y * W + x] : 0;
+        int b = in ? B[(long)y * W + x] : 0;
+        if (a < 0 || a > cap_a) a = 0;
+        if (b < 0 || b > cap_b) b = 0;
+        unsigned long long rest = __ballot(a > 0);
+        unsigned long long bits = lane == 0 ? ~0ull : 0ull;     // lane k + 1: the lanes whose B label has bit k set
+        if (rest) {
+#pragma unroll 1
+            for (int k = 0; k < nb; ++k) {
+                const unsigned long long bk = __ballot((b >> k) & 1);
+                if (lane == k + 1) bits = bk;
+            }
+        }
+        while (rest) {                                          // one turn per distinct label of A; `rest` is the same in every lane
+            const int leader = __ffsll((long long)rest) - 1;
+            const int lead = __shfl(a, leader, 64);
+            const unsigned long long mm = __ballot(a == lead);
+            const int val = __popcll(bits & mm);
+            const int slot = lead & (CC_SLOTS - 1);
+            int old = 0;
+            if (lane == leader) old = atomicCAS(&tag_a[slot], 0, lead);
+            old = __shfl(old, leader, 64);
+            if (lane < rw && val) {
+                if (old == 0 || old == lead) atomicAdd(&acc_a[slot][lane], val);
+                else __hip_atomic_fetch_add(R + (long)(lead - 1) * rw + lane, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            rest &= ~mm;
+        }
+        rest = __ballot(b > 0);
+        while (rest) {                                          // and per distinct label of B
+            const int leader = __ffsll((long long)rest) - 1;
+            const int lead = __shfl(b, leader, 64);
+            const unsigned long long mm = __ballot(b == lead);
+            if (lane == leader) {
+                const int slot = lead & (CC_SLOTS - 1);
+                const int old = atomicCAS(&tag_b[slot], 0, lead);
+                if (old == 0 || old == lead) atomicAdd(&acc_b[slot], __popcll(mm));
+                else __hip_atomic_fetch_add(AB + (lead - 1), __popcll(mm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            rest &= ~mm;
+        }
+    }
+    __syncthreads();
+    for (int sl = threadIdx.x >> 5; sl < CC_SLOTS; sl += CC_THREADS >> 5) {         // 32 lanes per slot: MATCH_ROW <= 32
+        const int c = threadIdx.x & 31;
+        const int lab = tag_a[sl], v = c < rw ? acc_a[sl][c] : 0;
+        if (lab && v) __hip_atomic_fetch_add(R + (long)(lab - 1) * rw + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int sl = threadIdx.x; sl < CC_SLOTS; sl += CC_THREADS)
+        if (tag_b[sl]) __hip_atomic_fetch_add(AB + (tag_b[sl] - 1), acc_b[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// one thread per row of A, all images
+__global__ __launch_bounds__(CC_THREADS) void match_cand_kernel(const int* __restrict__ rows, long nrows, int nb, int* __restrict__ cand) {
+    const long i = (long)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= nrows) return;
+    const int* r = rows + i * (nb + 1);
+    const long area = r[0];
+    int c = 0;
+    for (int k = 0; k < nb; ++k) c |= (2L * r[1 + k] > area) << k;
+    cand[i] = c;                                                // may exceed cap_b, or name a label that merely touches: verified next
+}
+
+// grid (tiles of an image, N): inter[a - 1] += the pixels with A == a and B == cand(a), B a label of 1 .. cap_b
+__global__ __launch_bounds__(CC_THREADS) void match_verify_kernel(const int* __restrict__ la, const int* __restrict__ lb, int H, int W,
+                                                                  int tiles_x, int cap_a, int cap_b, const int* __restrict__ cand,
+                                                                  int* inter) {
+    __shared__ int tag[CC_SLOTS], acc[CC_SLOTS];
+    const long hw = (long)H * W;
+    const int* A = la + (long)blockIdx.y * hw;
+    const int* B = lb + (long)blockIdx.y * hw;
+    const int* C = cand + (long)blockIdx.y * cap_a;
+    int* I = inter + (long)blockIdx.y * cap_a;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int y0 = ty * CC_TH, x0 = tx * CC_TW;
+    const int lane = threadIdx.x & 63;
+    for (int s = threadIdx.x; s < CC_SLOTS; s += CC_THREADS) tag[s] = acc[s] = 0;
+    __syncthreads();
+#pragma unroll 1
+    for (int i = threadIdx.x; i < CC_TH * CC_TW; i += CC_THREADS) {
+        const int y = y0 + i / CC_TW, x = x0 + lane;
+        const bool in = y < H && x < W;
+        int a = in ? A[(long)y * W + x] : 0;
+        const int b = in ? B[(long)y * W + x] : 0;
+        if (a < 0 || a > cap_a) a = 0;
+        const bool hit = a > 0 && b >= 1 && b <= cap_b && b == C[a - 1];
+        unsigned long long rest = __ballot(hit);
+        while (rest) {
+            const int leader = __ffsll((long long)rest) - 1;
+            const int lead = __shfl(a, leader, 64);
+            const unsigned long long mm = __ballot(hit && a == lead);
+            if (lane == leader) {
+                const int slot = lead & (CC_SLOTS - 1);
+                const int old = atomicCAS(&tag[slot], 0, lead);
+                if (old == 0 || old == lead) atomicAdd(&acc[slot], __popcll(mm));
+                else __hip_atomic_fetch_add(I + (lead - 1), __popcll(mm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            rest &= ~mm;
+        }
+    }
+    __syncthreads();
+    for (int sl = threadIdx.x; sl < CC_SLOTS; sl += CC_THREADS)
+        if (tag[sl]) __hip_atomic_fetch_add(I + (tag[sl] - 1), acc[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid (ceil(cap_a / 256), N): one thread per row of A
+__global__ __launch_bounds__(CC_THREADS) void match_decide_kernel(const int* __restrict__ rows, const int* __restrict__ area_b,
+                                                                  const int* __restrict__ cand, const int* __restrict__ inter,
+                                                                  int cap_a, int cap_b, int nb, int num, int den,
+                                                                  int* __restrict__ match_a, int* __restrict__ match_b) {
+    const int i = blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= cap_a) return;
+    const long row = (long)blockIdx.y * cap_a + i;
+    const int area = rows[row * (nb + 1)];
+    int it = inter[row];
+    int maj = 2L * it > area ? cand[row] : 0;                   // a verified candidate is a label of 1 .. cap_b
+    int maj_area = 0;
+    if (maj) maj_area = area_b[(long)blockIdx.y * cap_b + maj - 1];
+    else it = 0;
+    const int match = (long)it * den > (long)num * ((long)area + maj_area - it) ? maj : 0;
+    int* o = match_a + row * MATCH_COLS;
+    o[0] = area; o[1] = maj; o[2] = it; o[3] = maj_area; o[4] = match;
+    if (match) match_b[(long)blockIdx.y * cap_b + match - 1] = i + 1;
+}
+
 bool aligned4(const void* p) { return (reinterpret_cast<size_t>(p) & 3) == 0; }
 long blocks_of(int H, int W) { return ((long)H * W + CC_BLOCK - 1) / CC_BLOCK; }
 constexpr int CC_MAX_CAP = 1 << 24;
+static_assert(MATCH_MAX_BITS == 25 && (CC_MAX_CAP >> 24) == 1 && (CC_MAX_CAP >> 25) == 0, "a row of the count pass holds every bit of a label");
 
 }  // namespace
 
@@ -488,5 +675,56 @@ extern "C" int dh_xbd_cc_paint(const int* labels, const unsigned char* cls, int 
     DH_REQUIRE(aligned4(labels), "xbd_cc_paint: labels hold int32");
     hipLaunchKernelGGL(cc_paint_kernel, dim3((int)blocks_of(H, W), N), dim3(CC_THREADS), 0, ST(stream), labels, cls, H, W, cap, out);
     DH_CHECK_LAUNCH("xbd_cc_paint");
+    return 0;
+}
+
+extern "C" int dh_xbd_cc_match_ws_bytes(int N, int cap_a, int cap_b, long* bytes) {
+    DH_REQUIRE(bytes, "xbd_cc_match_ws_bytes: null pointer");
+    DH_REQUIRE(N >= 1 && N <= 65535, "xbd_cc_match_ws_bytes: N=%d: 1 .. 65535 images", N);
+    {
+        const int cap = cap_a;
+        CC_REQUIRE_CAP("xbd_cc_match_ws_bytes");
+    }
+    {
+        const int cap = cap_b;
+        CC_REQUIRE_CAP("xbd_cc_match_ws_bytes");
+    }
+    *bytes = 4L * match_ws_words(N, cap_a, cap_b);
+    return 0;
+}
+
+extern "C" int dh_xbd_cc_match(const int* labels_a, const int* labels_b, int N, int H, int W, int cap_a, int cap_b, int iou_num,
+                               int iou_den, int* match_a, int* match_b, void* ws, long ws_bytes, void* stream) {
+    DH_REQUIRE(labels_a && labels_b && match_a && match_b && ws, "xbd_cc_match: null pointer");
+    CC_REQUIRE_SHAPE("xbd_cc_match");
+    {
+        const int cap = cap_a;
+        CC_REQUIRE_CAP("xbd_cc_match");
+    }
+    {
+        const int cap = cap_b;
+        CC_REQUIRE_CAP("xbd_cc_match");
+    }
+    DH_REQUIRE(iou_num >= 1 && iou_num <= iou_den && iou_den <= 32768 && 2L * iou_num >= iou_den,
+               "xbd_cc_match: iou %d / %d: 1 <= num <= den <= 32768 and num / den >= 1 / 2", iou_num, iou_den);
+    DH_REQUIRE(aligned4(labels_a) && aligned4(labels_b) && aligned4(match_a) && aligned4(match_b) && aligned4(ws),
+               "xbd_cc_match: both label maps, match_a, match_b and the workspace hold int32");
+    const long words = match_ws_words(N, cap_a, cap_b);
+    DH_REQUIRE(ws_bytes >= 4 * words, "xbd_cc_match: a workspace of %ld bytes, %ld are needed", ws_bytes, 4 * words);
+    const int nb = match_bits(cap_b);
+    const long nrows = (long)N * cap_a, b_words = (long)N * cap_b;
+    int* rows = reinterpret_cast<int*>(ws);
+    int* area_b = rows + nrows * (nb + 1);
+    int* cand = area_b + b_words;
+    int* inter = cand + nrows;
+    const int tiles_x = dh_cdiv(W, CC_TW), tiles_y = dh_cdiv(H, CC_TH);
+    const dim3 tiles(tiles_x * tiles_y, N), thr(CC_THREADS);
+    hipLaunchKernelGGL(match_init_kernel, dim3(dh_cdiv(words + b_words, CC_THREADS)), thr, 0, ST(stream), rows, words, match_b, b_words);
+    hipLaunchKernelGGL(match_count_kernel, tiles, thr, 0, ST(stream), labels_a, labels_b, H, W, tiles_x, cap_a, cap_b, nb, rows, area_b);
+    hipLaunchKernelGGL(match_cand_kernel, dim3(dh_cdiv(nrows, CC_THREADS)), thr, 0, ST(stream), rows, nrows, nb, cand);
+    hipLaunchKernelGGL(match_verify_kernel, tiles, thr, 0, ST(stream), labels_a, labels_b, H, W, tiles_x, cap_a, cap_b, cand, inter);
+    hipLaunchKernelGGL(match_decide_kernel, dim3(dh_cdiv(cap_a, CC_THREADS), N), thr, 0, ST(stream), rows, area_b, cand, inter, cap_a,
+                       cap_b, nb, iou_num, iou_den, match_a, match_b);
+    DH_CHECK_LAUNCH("xbd_cc_match");
     return 0;
 }

@@ -719,3 +719,72 @@ def building_f1(confusion):
             f1_sc[c - 1] = 2 * tp / (2 * tp + fp + fn)
         f1 = 4 / np.sum(1.0 / (f1_sc + 1e-6))
     return f1_sc, f1
+
+
+class XbdMatch:
+    """What building_match returns.  On the device: pred_labels / gt_labels [N, H, W] int32 and pred_count / gt_count [N] int32
+    (the predicted and the true buildings), match_pred [N, max_buildings, 5] int32 and match_gt [N, max_buildings] int32
+    (ops.xbd_cc_match's match_a and match_b), pred_cls and gt_cls [N, max_buildings] uint8.  On the host, np.int64 and additive
+    over batches: loc [3] = tp, fp, fn buildings; confusion [4, 5], [g - 1, p] the true buildings of class g whose matched
+    predicted building has class p (0: unmatched, or a partner of class 0); spurious [5], the unmatched predicted buildings by
+    class."""
+
+    def __init__(self, pred_labels, pred_count, gt_labels, gt_count, match_pred, match_gt, pred_cls, gt_cls, loc, confusion, spurious):
+        self.pred_labels, self.pred_count, self.gt_labels, self.gt_count = pred_labels, pred_count, gt_labels, gt_count
+        self.match_pred, self.match_gt, self.pred_cls, self.gt_cls = match_pred, match_gt, pred_cls, gt_cls
+        self.loc, self.confusion, self.spurious = loc, confusion, spurious
+
+
+def building_match(pred_map_u8, gt_u8, iou=(1, 2), connectivity=8, max_buildings=4096):
+    """Predicted buildings matched one-to-one to the true ones at an intersection over union above iou = (num, den), on the
+    device.  The predicted buildings are the components of pred_map_u8 != 0 ([N, H, W] uint8; building_damage(...).map drops the
+    buildings under min_area first), each with the class its pixels vote for (first maximum of 1 .. 4); the true buildings are
+    the keyed components of gt_u8 with their class, as in building_confusion.  A pair matches when inter * den > num * union
+    (ops.xbd_cc_match: exact, strict, num / den >= 1 / 2, so no building has two partners).  Returns an XbdMatch.  The two counts
+    are read once and the small tables copied once; no label map leaves the device.  A label above 4 raises KeyError, more than
+    max_buildings components on either side ValueError."""
+    what = "building_match"
+    _device_u8("building match", pred_map_u8, gt_u8)
+    ops._cc_cap(what, max_buildings)
+    ops._cc_iou(what, iou)
+    _check_labels(gt_u8)
+    cap = max_buildings
+    pred_labels, pred_count = ops.xbd_cc_label(pred_map_u8, connectivity, False)
+    gt_labels, gt_count = ops.xbd_cc_label(gt_u8, connectivity, True)
+    pred_cls = ops.xbd_cc_vote(ops.xbd_cc_stats(pred_labels, pred_map_u8, cap), 0, "damage")
+    gt_cls = ops.xbd_cc_vote(ops.xbd_cc_stats(gt_labels, gt_u8, cap), 0, "all")               # a keyed component has one class
+    match_pred, match_gt = ops.xbd_cc_match(pred_labels, gt_labels, cap, cap, iou)
+    counts = _check_count(what, torch.stack((pred_count, gt_count)), cap)
+    m_pred, m_gt = match_pred[:, :, 4].cpu().numpy(), match_gt.cpu().numpy()
+    c_pred, c_gt = pred_cls.cpu().numpy().astype(np.int64), gt_cls.cpu().numpy().astype(np.int64)
+    loc, conf, spur = np.zeros(3, dtype=np.int64), np.zeros((4, 5), dtype=np.int64), np.zeros(5, dtype=np.int64)
+    for n in range(m_gt.shape[0]):
+        ka, kb = int(counts[0, n]), int(counts[1, n])
+        partner = m_gt[n, :kb]
+        p = np.where(partner > 0, c_pred[n][np.maximum(partner, 1) - 1], 0)
+        np.add.at(conf, (c_gt[n, :kb] - 1, p), 1)
+        free = m_pred[n, :ka] == 0
+        spur += np.bincount(c_pred[n, :ka][free], minlength=5)[:5]
+        tp = int((partner > 0).sum())
+        loc += (tp, int(free.sum()), kb - tp)
+    return XbdMatch(pred_labels, pred_count, gt_labels, gt_count, match_pred, match_gt, pred_cls, gt_cls, loc, conf, spur)
+
+
+def building_match_f1(loc, confusion, spurious):
+    """(loc_f1, the four per-class F1 values, their harmonic mean) of building_match's three tables (summed over batches):
+    loc_f1 = 2 tp / (2 tp + fp + fn) of the buildings; for class c, tp = confusion[c - 1, c], fn = the rest of the row,
+    fp = the rest of column c + spurious[c]; f1_sc = 2 tp / (2 tp + fp + fn), nan for 0 / 0; f1 = 4 / sum(1 / (f1_sc + 1e-6)),
+    as building_f1 and val_score form them."""
+    tp, fp, fn = (float(v) for v in np.asarray(loc).reshape(3))
+    conf = np.asarray(confusion).astype(np.float64).reshape(4, 5)
+    spur = np.asarray(spurious).astype(np.float64).reshape(5)
+    f1_sc = np.zeros((4,))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        loc_f1 = np.float64(2 * tp) / np.float64(2 * tp + fp + fn)
+        for c in range(1, 5):
+            tp = conf[c - 1, c]
+            fn = conf[c - 1].sum() - tp
+            fp = conf[:, c].sum() - tp + spur[c]
+            f1_sc[c - 1] = 2 * tp / (2 * tp + fp + fn)
+        f1 = 4 / np.sum(1.0 / (f1_sc + 1e-6))
+    return loc_f1, f1_sc, f1

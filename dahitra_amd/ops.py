@@ -2317,6 +2317,67 @@ def xbd_cc_paint(labels, cls_u8, out=None):
     return out
 
 
+XBD_CC_MATCH_COLS = 5            # area, maj, inter, maj_area, match
+XBD_CC_MATCH_MAX_DEN = 32768
+
+
+def _cc_iou(what, iou):
+    """(num, den) of an IoU threshold given as a pair of ints, 1 <= num <= den <= 32768 and num / den >= 1 / 2.  A float is
+    refused: 0.5 and 2 / 3 have to be exact."""
+    ok = isinstance(iou, (tuple, list)) and len(iou) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in iou)
+    if not ok or not (1 <= iou[0] <= iou[1] <= XBD_CC_MATCH_MAX_DEN and 2 * iou[0] >= iou[1]):
+        raise ValueError("%s: iou %r is not a pair of ints (num, den) with 1 <= num <= den <= %d and 2 num >= den"
+                         % (what, iou, XBD_CC_MATCH_MAX_DEN))
+    return int(iou[0]), int(iou[1])
+
+
+def xbd_cc_match_ws_bytes(N, cap_a, cap_b):
+    """bytes of the workspace xbd_cc_match needs: int32 rows [N, cap_a, NB + 1] with NB = cap_b.bit_length(), the areas of B
+    [N, cap_b], candidates and intersections [N, cap_a] each"""
+    n = ctypes.c_long(0)
+    if _lib.lib().dh_xbd_cc_match_ws_bytes(N, cap_a, cap_b, ctypes.byref(n)) != 0:
+        raise ValueError(_lib.lib().dh_last_error().decode())
+    return int(n.value)
+
+
+def xbd_cc_match(labels_a, labels_b, cap_a, cap_b, iou=(1, 2), out=None, ws=None):
+    """Two label maps matched by intersection over union, on the device.  labels_a (predicted buildings, 1 .. cap_a) and
+    labels_b (true buildings, 1 .. cap_b), both [N, H, W] int32 as xbd_cc_label writes them; labels outside 1 .. cap are
+    background.  Returns (match_a [N, cap_a, 5] int32, match_b [N, cap_b] int32).  Row i of match_a describes label i + 1 of A:
+    area, maj (the label of B that covers more than half of it, or 0), inter and maj_area (its intersection with maj and maj's
+    area, 0 without one) and match = maj if inter * den > num * (area + maj_area - inter), else 0, with iou = (num, den) ints,
+    1 <= num <= den <= 32768, 2 num >= den (strict, exact; one-to-one).  match_b[n, j] is the label of A matched to label j + 1 of
+    B, or 0.  Rows of labels that do not exist are 0; every int is written.  Five launches whatever the data, nothing read back,
+    bit-exact.  out: (match_a, match_b) buffers to write into.  ws: a uint8 device buffer of xbd_cc_match_ws_bytes(N, cap_a,
+    cap_b) bytes or more (default: a fresh one).  ValueError, before any launch, for a wrong rank, dtype, device or shape,
+    non-contiguous storage, a bad cap or iou (a float among them) or an `out` / `ws` that does not fit."""
+    what = "xbd_cc_match"
+    _cc_cap(what, cap_a)
+    _cc_cap(what, cap_b)
+    num, den = _cc_iou(what, iou)
+    N, H, W = _cc_image(what, "labels_a", labels_a, torch.int32)
+    named = [("labels_a", labels_a, torch.int32, None, "[N, H, W]"),
+             ("labels_b", labels_b, torch.int32, (N, H, W), "%s like labels_a" % [N, H, W])]
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 2):
+            raise ValueError("%s: out is a pair (match_a, match_b)" % what)
+        named += [("out[0]", out[0], torch.int32, (N, cap_a, XBD_CC_MATCH_COLS), "match_a %s" % [N, cap_a, XBD_CC_MATCH_COLS]),
+                  ("out[1]", out[1], torch.int32, (N, cap_b), "match_b %s" % [N, cap_b])]
+    if ws is not None:
+        named.append(("ws", ws, torch.uint8, None, "workspace"))
+    _cc_tensors(what, named)
+    need = xbd_cc_match_ws_bytes(N, cap_a, cap_b)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=labels_a.device)
+    elif ws.numel() < need or ws.data_ptr() % 4:
+        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
+    match_a, match_b = out if out is not None else (torch.empty(N, cap_a, XBD_CC_MATCH_COLS, dtype=torch.int32, device=labels_a.device),
+                                                    torch.empty(N, cap_b, dtype=torch.int32, device=labels_a.device))
+    _call("dh_xbd_cc_match", _vp(labels_a.data_ptr()), _vp(labels_b.data_ptr()), N, H, W, cap_a, cap_b, num, den,
+          _vp(match_a.data_ptr()), _vp(match_b.data_ptr()), _vp(ws.data_ptr()), ws.numel(), S())
+    return match_a, match_b
+
+
 # ---- the change-detection evaluator's picture (csrc/cd_visual.hip) -----------------------------------------
 def cd_vis_shape(N, H, W):
     """the shape of the evaluator's picture of N images H x W: make_grid's min(8, N) tiles per row, padding 0, four bands"""

@@ -838,6 +838,35 @@ int dh_xbd_cc_stats(const int* labels, const unsigned char* vote, int N, int H, 
 int dh_xbd_cc_vote(const int* table, int N, int cap, int min_area, int mode, unsigned char* cls, void* stream);
 int dh_xbd_cc_paint(const int* labels, const unsigned char* cls, int N, int H, int W, int cap, unsigned char* out, void* stream);
 
+/* ---- xBD buildings: two label maps matched by IoU (csrc/xbd_buildings.hip) ---------------------------------------------------
+ * dh_xbd_cc_match: labels_a (the predicted buildings, labels 1 .. cap_a) and labels_b (the true ones, 1 .. cap_b), both
+ *   [N][H][W] int32 as dh_xbd_cc_label writes them; a label below 1 or above its cap is background on that side.  Images are
+ *   independent.  For a label a: area(a) = pixels with A == a; inter(a, b) = pixels with A == a and B == b;
+ *     maj(a)   = the b >= 1 with 2 inter(a, b) > area(a), 0 when there is none;
+ *     inter    = inter(a, maj), maj_area = area_B(maj), both 0 when maj == 0;
+ *     match(a) = maj if inter * iou_den > iou_num * (area + maj_area - inter) (strict, in 64-bit integers), else 0.
+ *   1 <= iou_num <= iou_den <= 32768 and 2 iou_num >= iou_den: above one half a match is one-to-one with no tie rule (the
+ *   shared pixels are more than half of a and more than half of b).
+ *   -> match_a [N][cap_a][5] int32, row i describes label i + 1 of A: area, maj, inter, maj_area, match;
+ *      match_b [N][cap_b] int32: the label of A matched to label j + 1 of B, or 0.
+ *   Rows of labels that do not exist are all 0.  Every int of both outputs is written by every call.
+ *   No table of pairs and no hash: with NB = bit_length(cap_b) <= 25, a first pass over the pixels counts per label a its area
+ *   and, for every bit k < NB, its pixels whose B label has bit k set (and the areas of B); cand(a) = OR_k (2 ones_k > area) << k
+ *   is maj(a) whenever maj(a) != 0 (each set bit of maj is counted more than area / 2 times, each clear bit fewer) and anything
+ *   otherwise, so a second pass over the pixels counts inter(a, cand(a)) and the candidate stands only if that is more than half
+ *   of the area.  Five launches whose number and grids depend on the shapes alone (zero, count, candidate, verify, decide); the
+ *   pixel passes reduce per wave and label with ballots and per workgroup in LDS, as dh_xbd_cc_stats does, and sum across
+ *   workgroups with agent-scope integer atomics.  No workgroup waits for another; the same bits on every run.
+ *   ws: the caller's workspace of at least 4 N (cap_a (NB + 3) + cap_b) bytes (dh_xbd_cc_match_ws_bytes writes that number to
+ *   *bytes, a host pointer), 4-byte aligned; every word that is read is written first by the same call, so nothing needs clearing
+ *   and the sequence replays from a captured graph.  All five device pointers are 4-byte aligned.
+ * Refused (nothing is written, non-zero, dh_last_error begins with xbd_cc_match): a null pointer, N < 1, N > 65535, H < 1, W < 1,
+ * H * W >= 2^31, a cap < 1 or > 2^24, N * cap > 2^28 (either cap), iou_num < 1, iou_num > iou_den, iou_den > 32768,
+ * 2 iou_num < iou_den, a misaligned pointer, ws_bytes below the query.  dh_xbd_cc_match_ws_bytes refuses the same N and caps. */
+int dh_xbd_cc_match_ws_bytes(int N, int cap_a, int cap_b, long* bytes);
+int dh_xbd_cc_match(const int* labels_a, const int* labels_b, int N, int H, int W, int cap_a, int cap_b, int iou_num, int iou_den,
+                    int* match_a, int* match_b, void* ws, long ws_bytes, void* stream);
+
 /* ---- the change-detection evaluator's picture (models/evaluator.py:118-131; csrc/cd_visual.hip) ------------------------------
  * dh_cd_eval_vis_u8: A, B [N][3][H][W] fp32 (as the net receives them), logits [N][C][H][W] fp32, label [N][H][W] int64 ->
  * out [4 * rows * H][cols * W][3] uint8 RGB, cols = min(8, N), rows = ceil(N / cols) (make_grid, padding 0): four bands of

@@ -14,7 +14,14 @@ No host work is inside a timed window: the four calls are recorded `chain` times
 checked at record time), and `replays` replays of it are timed between two device events, several rounds, the inputs
 alternating.  `label_us` is the labelling alone (six launches), `all_us` label + stats + vote + paint (ten launches), per
 sequence in such a chain.  If scipy can be imported, `host_ms` is what the step costs without these kernels: the map copied to
-the host, scipy.ndimage.label, np.bincount votes per building and class, the painted map copied back.  Prints one JSON line."""
+the host, scipy.ndimage.label, np.bincount votes per building and class, the painted map copied back.
+
+The `match` record times the matching of two label maps (ops.xbd_cc_match, five launches) for three pairs of predicted / true
+buildings: `match_us` the same way, in a chain of its own with both label maps already on the device, `building_match_ms` the
+whole models/xbd.building_match (both labellings, statistics, votes, the match, the two counts read and the small tables
+copied; a host clock around the call, which ends in those copies, median of `rounds`), and `host_ms` the route without the
+kernel, timed once: both label maps copied to the host, np.unique over the pairs a * (cap + 1) + b, the definition on arrays.
+Prints one JSON line."""
 import argparse
 import json
 import os
@@ -51,6 +58,82 @@ def host_path(key_dev, vote_dev, conn8=True):
     cls = np.where(hist[:, 1:].max(1) > 0, 1 + hist[:, 1:].argmax(1), 0).astype(np.uint8)
     cls[0] = 0
     return torch.from_numpy(cls[labels][None]).to(key_dev.device), k
+
+
+def host_match(la_dev, lb_dev, cap, num=1, den=2):
+    """ops.xbd_cc_match's two outputs without the kernel: both label maps copied back, np.unique over the pairs"""
+    a, b = la_dev.cpu().numpy()[0].astype(np.int64).ravel(), lb_dev.cpu().numpy()[0].astype(np.int64).ravel()
+    a, b = np.where((a >= 1) & (a <= cap), a, 0), np.where((b >= 1) & (b <= cap), b, 0)
+    area_a, area_b = np.bincount(a, minlength=cap + 1), np.bincount(b, minlength=cap + 1)
+    pairs, cnt = np.unique(a * (cap + 1) + b, return_counts=True)
+    pa, pb = pairs // (cap + 1), pairs % (cap + 1)
+    sel = (pa >= 1) & (pb >= 1) & (2 * cnt > area_a[pa])
+    m = np.zeros((cap, 5), dtype=np.int64)
+    m[:, 0] = area_a[1:]
+    m[pa[sel] - 1, 1], m[pa[sel] - 1, 2], m[pa[sel] - 1, 3] = pb[sel], cnt[sel], area_b[pb[sel]]
+    ok = (m[:, 1] > 0) & (m[:, 2] * den > num * (m[:, 0] + m[:, 3] - m[:, 2]))
+    m[:, 4] = np.where(ok, m[:, 1], 0)
+    mb = np.zeros(cap, dtype=np.int32)
+    mb[m[ok, 4] - 1] = np.flatnonzero(ok) + 1
+    return m.astype(np.int32)[None], mb[None]
+
+
+def shifted(t):
+    """one column to the right, column 0 cleared"""
+    out = torch.zeros_like(t)
+    out[:, :, 1:] = t[:, :, :-1]
+    return out
+
+
+def match_record(args, keys, vote, timed):
+    from dahitra_amd.models import xbd
+    S, cap, dev = args.size, args.cap, vote.device
+    pairs = {"squares_shifted": (keys["squares"], shifted(keys["squares"])), "noise_squares": (keys["noise"], keys["squares"]),
+             "serpentine_squares": (keys["serpentine"], keys["squares"])}
+    match_a = torch.empty(1, cap, ops.XBD_CC_MATCH_COLS, dtype=torch.int32, device=dev)
+    match_b = torch.empty(1, cap, dtype=torch.int32, device=dev)
+    ws = torch.empty(ops.xbd_cc_match_ws_bytes(1, cap, cap), dtype=torch.uint8, device=dev)
+    labels, graphs, matched, host_ms, agree, whole_ms = {}, {}, {}, {}, {}, {}
+    for k, (pred, gt) in pairs.items():
+        la, lb = ops.xbd_cc_label(pred, 8, False)[0], ops.xbd_cc_label(gt, 8, False)[0]
+        labels[k] = (la, lb)
+        for _ in range(3):
+            ops.xbd_cc_match(la, lb, cap, cap, (1, 2), out=(match_a, match_b), ws=ws)
+        torch.cuda.synchronize()
+        matched[k] = int((match_b != 0).sum())
+        t0 = time.perf_counter()
+        want = host_match(la, lb, cap)
+        host_ms[k] = round((time.perf_counter() - t0) * 1e3, 2)
+        agree[k] = bool(np.array_equal(match_a.cpu().numpy(), want[0]) and np.array_equal(match_b.cpu().numpy(), want[1]))
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(args.chain):
+                ops.xbd_cc_match(la, lb, cap, cap, (1, 2), out=(match_a, match_b), ws=ws)
+        g.replay()
+        graphs[k] = g
+    torch.cuda.synchronize()
+    t = {k: [] for k in graphs}
+    for _ in range(args.rounds):
+        for k in graphs:
+            t[k].append(timed(graphs[k]))
+    yy, xx = torch.meshgrid(torch.arange(S, device=dev), torch.arange(S, device=dev), indexing="ij")
+    blocks = (1 + (yy // 48 + xx // 48) % 4).to(torch.uint8)[None]        # classes 1 .. 4 in 48 x 48 blocks: no square is cut
+    for k, (pred, gt) in pairs.items():                       # the whole building_match: class maps on both sides
+        pm, gm = pred * vote, gt * blocks
+        ts = []
+        for i in range(args.rounds + 2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = xbd.building_match(pm, gm, (1, 2), 8, cap)
+            torch.cuda.synchronize()
+            if i >= 2:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        whole_ms[k] = {"median": round(statistics.median(ts), 2), "min": round(min(ts), 2), "max": round(max(ts), 2),
+                       "loc": r.loc.tolist()}
+    row = lambda k: {"median": round(statistics.median(t[k]), 1), "min": round(min(t[k]), 1), "max": round(max(t[k]), 1)}
+    return {"what": "match_us: us per xbd_cc_match in a recorded chain; building_match_ms: host clock around the whole call",
+            "matched": matched, "match_us": {k: row(k) for k in pairs}, "building_match_ms": whole_ms, "host_ms": host_ms,
+            "host_agrees": agree}
 
 
 def main():
@@ -136,6 +219,7 @@ def main():
            "host_ms": host_ms, "host_agrees": agree}
     med = [res["all_us"][k]["median"] for k in keys]
     res["spread_all"] = round(max(med) / min(med), 2)
+    res["match"] = match_record(args, keys, vote, timed)
     print(json.dumps(res))
 
 
