@@ -22,6 +22,9 @@ Differences from the reference, all deliberate:
     draws them from torch's global generator, in its worker processes); without one the flag `draw_train_params` reports is
     dropped, as before.  The draws are torchvision's (>= 0.8: one randperm(4), then the three factors) and the arithmetic is
     Pillow's (`jitter_reference_u8` states it).
+  * `dilate=k` (off by default) replaces `msk` of a training batch by the dilated, prioritised channels that
+    xBD_code/train_unettransformer.py:262-273 builds with dilation(., square(5)) -- lines that train.py, which this loader
+    follows, has commented out -- in one more launch (dh_xbd_msk_dilate_u8).  That script's other augmentations are not built.
 """
 import ctypes
 import functools
@@ -271,7 +274,7 @@ class GpuXbdPipeline:
     def __len__(self):
         return self.pre.shape[0]
 
-    def make_batch(self, indices, crop, params=None, train=True, jitter=None):
+    def make_batch(self, indices, crop, params=None, train=True, jitter=None, dilate=0):
         """indices: source samples of the batch; params: one row per sample in PARAM_FIELDS order (draw_train_params), or None
         for the crop at the origin without augmentation.  train=False builds ValData's masks (msk[0] from the pre mask,
         lbl_msk = label - 1 on the buildings); the reference validates whole images, i.e. crop == H == W and params=None.
@@ -281,10 +284,25 @@ class GpuXbdPipeline:
         jitter: one entry per sample, None or the pair (pre, post) of draw_jitter_params results applied to the sample's two
         images (ColorJitter, train.py:139; training batches only).  None, or every entry None, is dh_xbd_augment_u8 exactly
         as without the argument; otherwise one call of dh_xbd_augment_jitter_u8.
+        dilate: 0 (default) is the batch as above, with the same launches and the same bytes.  An odd k of 3 .. 31 (training
+        batches only; 5 is the script's value) gives the targets xBD_code/train_unettransformer.py trains on: after the augment
+        launch ONE more launch (ops.xbd_msk_dilate) replaces `msk` by the four damage channels dilated with square(k) and put
+        through the priority rule of its lines 262-273 (class 2 over 3 over 4, any of them over 1; channel 0 = any).  The
+        dilation acts on the augmented crop, as in the script, which dilates after its crop and flips: a building just outside
+        the crop window contributes nothing.  `img`, `lbl_msk` (still all zeros: channel 0 is set wherever another is) and `fn`
+        are untouched.  What this is NOT: that script's rot90, its reflect-101 shift, its cv2.warpAffine rotate / scale and its
+        rare colour operations are not built (cv2's arithmetic, which no test here has an oracle for), so the switch gives
+        train.py's geometry with train_unettransformer.py's targets.  The script's ValData does not dilate: train=False is
+        refused.
         ValueError for a crop larger than the image, a window outside it, a resize box that leaves the crop, jitter in a
         validation batch, jitter rows that do not match the samples, an order that is no permutation, a factor that is not
-        finite."""
+        finite, a `dilate` that is not 0 or an odd integer of 3 .. 31, or `dilate` in a validation batch."""
         n = len(indices)
+        if isinstance(dilate, bool) or not isinstance(dilate, int) or (dilate != 0 and not (3 <= dilate <= ops.XBD_MORPH_MAX_K
+                                                                                             and dilate % 2 == 1)):
+            raise ValueError("dilate: %r is neither 0 nor an odd window of 3 .. %d" % (dilate, ops.XBD_MORPH_MAX_K))
+        if dilate and not train:
+            raise ValueError("dilate: the dilated masks are training targets; the reference's ValData does not dilate (train=False)")
         table = None
         if jitter is not None:
             if not train:
@@ -326,9 +344,11 @@ class GpuXbdPipeline:
             ops._call("dh_xbd_augment_jitter_u8", ops.P(self.pre), ops.P(self.post), ops.P(None), ops.P(self.post_label),
                       ops.P(idx), ops.P(p), ops.P(coef), ctypes.c_void_p(table.ctypes.data), n, H, W, crop, 0, ops.P(img),
                       ops.P(msk), ops.P(None), ops.P(ws), ws.numel(), ops.S())
+        if dilate:
+            msk = ops.xbd_msk_dilate(msk, dilate)
         return {'img': img, 'msk': msk, 'lbl_msk': lbl, 'fn': [self.files[int(i)] for i in indices]}
 
-    def batches(self, batch_size, crop, train=True, rng=None, jitter_gen=None):
+    def batches(self, batch_size, crop, train=True, rng=None, jitter_gen=None, dilate=0):
         """one epoch.  train: `rng` (a random.Random) shuffles the samples, then every sample draws its parameters with
         draw_train_params, in batch order (the reference's DataLoader shuffles with torch's generator and draws in its worker
         processes: the order of the samples is this loader's own, a sample's draws are the reference's).  Otherwise the
@@ -336,8 +356,11 @@ class GpuXbdPipeline:
         size -- ValueError otherwise; a validation crop is make_batch(..., params, train=False).
         jitter_gen: a torch.Generator; every training sample whose draw_train_params flag is set then draws its ColorJitter
         parameters from it (draw_jitter_params, pre then post, in sample order) and gets them applied.  None: no ColorJitter
-        and no draw from any torch generator."""
+        and no draw from any torch generator.
+        dilate: make_batch's, for every batch of a training epoch (0: off; ValueError with train=False).  It draws nothing."""
         _, H, W, _ = self.pre.shape
+        if dilate and not train:
+            raise ValueError("dilate: the dilated masks are training targets; the reference's ValData does not dilate (train=False)")
         if not train and not crop == H == W:
             raise ValueError("a validation epoch takes whole images: crop %d is not the %dx%d image" % (crop, H, W))
         order = list(range(len(self)))
@@ -356,4 +379,4 @@ class GpuXbdPipeline:
                 params.append(row)
                 jitter.append((draw_jitter_params(jitter_gen), draw_jitter_params(jitter_gen))
                               if flag and jitter_gen is not None else None)
-            yield self.make_batch(ind, crop, params, train, jitter if jitter_gen is not None else None)
+            yield self.make_batch(ind, crop, params, train, jitter if jitter_gen is not None else None, dilate)

@@ -20,8 +20,10 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
         the localisation probability is channel 0 of the same prediction (the script's separate localisation net is not built)
     buildings / building_damage / building_confusion / building_f1   no counterpart: connected components of a class map, one
         damage class per building by vote, and the building-level confusion and F1 against the ground truth
+    dilate / erode / opening / closing / fill_holes / clean_footprint   no counterpart: square-window morphology and hole
+        filling of a footprint before its buildings are counted (scipy.ndimage's binary_* functions are the oracle)
 Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_visual.hip,
-csrc/xbd_buildings.hip + the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
+csrc/xbd_buildings.hip, csrc/xbd_morph.hip + the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
 import numpy as np
@@ -682,6 +684,80 @@ def building_damage(msk_u8, loc=ops.XBD_LOC_THR, footprint=None, connectivity=8,
     painted = ops.xbd_cc_paint(labels, cls)
     counts = _check_count(what, count, max_buildings)
     return XbdBuildings(labels, count, table, cls, painted, counts)
+
+
+# ---- cleaning the footprint: morphology and hole filling (no counterpart in the reference; csrc/xbd_morph.hip) --------------
+def dilate(map_u8, k):
+    """map_u8 [N, H, W] uint8 (nonzero = set) dilated by a k x k square (k odd, 1 .. 31), everything outside the image clear:
+    [N, H, W] uint8, 0 / 1, on the device.  scipy.ndimage.binary_dilation(a, structure=ones((k, k))); one launch."""
+    _device_u8("dilate", map_u8)
+    return ops.xbd_morph(map_u8, "dilate", k)
+
+
+def erode(map_u8, k):
+    """map_u8 eroded by a k x k square, everything outside the image set (skimage's convention):
+    scipy.ndimage.binary_erosion(a, structure=ones((k, k)), border_value=1); one launch."""
+    _device_u8("erode", map_u8)
+    return ops.xbd_morph(map_u8, "erode", k)
+
+
+def opening(map_u8, k):
+    """erode, then dilate, with the same k x k square: removes what the square does not fit into (specks, one-pixel bridges).
+    Two launches."""
+    _device_u8("opening", map_u8)
+    return ops.xbd_morph(ops.xbd_morph(map_u8, "erode", k), "dilate", k)
+
+
+def closing(map_u8, k):
+    """dilate, then erode, with the same k x k square: closes gaps and pin-holes narrower than the square.  Two launches."""
+    _device_u8("closing", map_u8)
+    return ops.xbd_morph(ops.xbd_morph(map_u8, "dilate", k), "erode", k)
+
+
+def fill_holes(map_u8, background=4):
+    """map_u8 with its holes filled: the set pixels plus every component of the clear ones (connectivity `background`, 4 or 8)
+    that does not touch the image border.  scipy.ndimage.binary_fill_holes with generate_binary_structure(2, 1) for 4 (its
+    default) or (2, 2) for 8.  Nine launches whatever the data, no cap on the number of holes (ops.xbd_fill_holes)."""
+    _device_u8("fill holes", map_u8)
+    return ops.xbd_fill_holes(map_u8, background)
+
+
+def clean_footprint(map_u8, open=0, close=0, fill=False, background=4, out=None, ws=None):
+    """A footprint cleaned before its buildings are counted, on the device: map_u8 [N, H, W] uint8 (nonzero = building, e.g.
+    damage_map(msk_u8, loc)) -> [N, H, W] uint8, 0 / 1.  The order is fixed:
+        1. opening with square(open) if open > 0     specks and one-pixel bridges between neighbouring houses go
+        2. closing with square(close) if close > 0   gaps narrower than the square close
+        3. fill_holes(background) if fill            pin-holes inside roofs fill
+    open, close: 0 or an odd window of 1 .. 31.  With open == close == 0 and not fill the result is (map_u8 != 0).  The result goes
+    into building_damage(msk_u8, footprint=...), and through its .map into building_match.
+    out: a [N, H, W] uint8 buffer for the result; ws: a uint8 device buffer of ops.xbd_fill_holes_ws_bytes(N, H, W) + 2 N H W
+    bytes or more (the hole fill's workspace, then two maps for the intermediate results).  With both given nothing is
+    allocated, so the call can be recorded in a graph."""
+    what = "clean_footprint"
+    _device_u8("footprint cleaning", map_u8)
+    for name, k in (("open", open), ("close", close)):
+        if isinstance(k, bool) or not isinstance(k, int) or k != 0:
+            ops._morph_k("%s: %s" % (what, name), k)
+    if isinstance(background, bool) or not isinstance(background, int) or background not in (4, 8):
+        raise ValueError("%s: background connectivity %r is neither 4 nor 8" % (what, background))
+    N, H, W = ops._cc_image(what, "map_u8", map_u8, torch.uint8)
+    steps = [(op, k) for k, pair in ((open, ("erode", "dilate")), (close, ("dilate", "erode"))) if k for op in pair]
+    fill_ws, tmp = None, [None, None]
+    if ws is not None:
+        need = ops.xbd_fill_holes_ws_bytes(N, H, W)
+        if not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.dim() != 1 or ws.numel() < need + 2 * N * H * W:
+            raise ValueError("%s: ws is not a uint8 buffer of %d bytes or more" % (what, need + 2 * N * H * W))
+        fill_ws = ws[:need]
+        tmp = [ws[need + i * N * H * W:need + (i + 1) * N * H * W].view(N, H, W) for i in range(2)]
+    if not steps and not fill:
+        return ops.xbd_morph(map_u8, "dilate", 1, out=out)           # (map_u8 != 0) as 0 / 1
+    cur = map_u8
+    for i, (op, k) in enumerate(steps):
+        last = i == len(steps) - 1 and not fill
+        cur = ops.xbd_morph(cur, op, k, out=out if last else tmp[i % 2])
+    if fill:
+        cur = ops.xbd_fill_holes(cur, background, out=out, ws=fill_ws)
+    return cur
 
 
 def building_confusion(pred_map_u8, gt_u8, connectivity=8, max_buildings=4096):

@@ -2378,6 +2378,113 @@ def xbd_cc_match(labels_a, labels_b, cap_a, cap_b, iou=(1, 2), out=None, ws=None
     return match_a, match_b
 
 
+# ---- xBD masks: morphology, the dilated training masks, hole filling (csrc/xbd_morph.hip) -------------------
+XBD_MORPH_TILE = (32, 64)        # (TH, TW) of the window kernel's output tile: dh_xbd_morph_tile_h / dh_xbd_morph_tile_w
+XBD_MORPH_MAX_K = 31
+XBD_MORPH_OPS = {"dilate": 0, "erode": 1}
+
+
+def _morph_k(what, k, lo=1):
+    if isinstance(k, bool) or not isinstance(k, int) or k < lo or k > XBD_MORPH_MAX_K or k % 2 == 0:
+        raise ValueError("%s: k %r is not an odd integer of %d .. %d" % (what, k, lo, XBD_MORPH_MAX_K))
+
+
+def _morph_apart(what, name, src, out):
+    """an output that shares bytes with its input: a window reads its neighbours"""
+    if out is not None and src.numel() and out.numel():
+        a, b = src.data_ptr(), out.data_ptr()
+        if a < b + out.numel() * out.element_size() and b < a + src.numel() * src.element_size():
+            raise ValueError("%s: out overlaps %s" % (what, name))
+
+
+def xbd_morph(map_u8, op, k, out=None):
+    """Binary morphology with a k x k square on the device.  map_u8 [N, H, W] uint8 (nonzero = set) -> [N, H, W] uint8, 0 / 1.
+    op 'dilate': set where any pixel of the window centred on it is set, everything outside the image clear --
+    scipy.ndimage.binary_dilation(a, structure=ones((k, k))), skimage's dilation(a, square(k)).  op 'erode': set where every pixel
+    of the window is set, everything outside the image set -- binary_erosion(a, structure=ones((k, k)), border_value=1), skimage's
+    erosion.  k: odd, 1 .. 31 (1 is `map_u8 != 0`).  One launch, bit-exact.  out: a [N, H, W] uint8 buffer to write into, not the
+    input.  ValueError, before any launch, for a wrong rank, dtype or device, non-contiguous storage, an even k, a k outside
+    1 .. 31 or a bool or float, an unknown op, or an `out` that is the input or does not fit."""
+    what = "xbd_morph"
+    if not isinstance(op, str) or op not in XBD_MORPH_OPS:
+        raise ValueError("%s: op %r is neither 'dilate' nor 'erode'" % (what, op))
+    _morph_k(what, k)
+    N, H, W = _cc_image(what, "map_u8", map_u8, torch.uint8)
+    named = [("map_u8", map_u8, torch.uint8, None, "[N, H, W]")]
+    if out is not None:
+        named.append(("out", out, torch.uint8, (N, H, W), str([N, H, W])))
+    _cc_tensors(what, named)
+    _morph_apart(what, "map_u8", map_u8, out)
+    if out is None:
+        out = torch.empty(N, H, W, dtype=torch.uint8, device=map_u8.device)
+    _call("dh_xbd_morph_u8", _vp(map_u8.data_ptr()), N, H, W, k, XBD_MORPH_OPS[op], _vp(out.data_ptr()), S())
+    return out
+
+
+def xbd_msk_dilate(msk_u8, k=5, out=None):
+    """The dilated, prioritised training masks of xBD_code/train_unettransformer.py:262-273 on the device.  msk_u8 [N, 5, H, W]
+    uint8 mask channels (what the loader's augment launch writes; nonzero = set) -> [N, 5, H, W] uint8, 0 / 1: with
+    d_c = dilation(msk[c], square(k)) for c = 1 .. 4 (channel 0 is not read),
+        out[2] = d2, out[3] = d3 & ~d2, out[4] = d4 & ~d2 & ~d3, out[1] = d1 & ~(d2 | d3 | d4), out[0] = out[1] | .. | out[4].
+    k: odd, 1 .. 31; 5 is the script's square(5).  One launch, bit-exact.  out: a [N, 5, H, W] uint8 buffer, not the input.
+    ValueError, before any launch, as xbd_morph."""
+    what = "xbd_msk_dilate"
+    _morph_k(what, k)
+    if not torch.is_tensor(msk_u8) or msk_u8.dtype != torch.uint8 or msk_u8.dim() != 4 or msk_u8.shape[1] != 5 or msk_u8.numel() == 0:
+        raise ValueError("%s: msk_u8 %s %s is not a non-empty uint8 [N, 5, H, W]" % (what, tuple(getattr(msk_u8, "shape", ())),
+                                                                                    getattr(msk_u8, "dtype", type(msk_u8))))
+    N, _, H, W = msk_u8.shape
+    named = [("msk_u8", msk_u8, torch.uint8, None, "[N, 5, H, W]")]
+    if out is not None:
+        named.append(("out", out, torch.uint8, (N, 5, H, W), str([N, 5, H, W])))
+    _cc_tensors(what, named)
+    _morph_apart(what, "msk_u8", msk_u8, out)
+    if out is None:
+        out = torch.empty(N, 5, H, W, dtype=torch.uint8, device=msk_u8.device)
+    _call("dh_xbd_msk_dilate_u8", _vp(msk_u8.data_ptr()), N, H, W, k, _vp(out.data_ptr()), S())
+    return out
+
+
+def xbd_fill_holes_ws_bytes(N, H, W):
+    """bytes of the workspace xbd_fill_holes needs for [N, H, W]: labels int32 [N, H W] and count [N], xbd_cc_label's own
+    workspace, the key uint8 [N, H W] and the marks uint8 [N, H W + 1] (each padded to four bytes)"""
+    n = ctypes.c_long(0)
+    if _lib.lib().dh_xbd_fill_holes_ws_bytes(N, H, W, ctypes.byref(n)) != 0:
+        raise ValueError(_lib.lib().dh_last_error().decode())
+    return int(n.value)
+
+
+def xbd_fill_holes(map_u8, background=4, out=None, ws=None):
+    """Hole filling on the device.  map_u8 [N, H, W] uint8 (nonzero = set) -> [N, H, W] uint8, 0 / 1: the set pixels, plus every
+    component of the clear ones (connectivity `background`, 4 or 8) that has no pixel on the image border --
+    scipy.ndimage.binary_fill_holes(a, structure=generate_binary_structure(2, 1)) for 4 (scipy's default), (2, 2) for 8.  Nine
+    launches whatever the data (xbd_cc_label's six among them), nothing read back, no cap on the number of holes, bit-exact.
+    out: a [N, H, W] uint8 buffer to write into, not the input.  ws: a uint8 device buffer of xbd_fill_holes_ws_bytes(N, H, W)
+    bytes or more (default: a fresh one).  ValueError, before any launch, for a wrong rank, dtype or device, non-contiguous
+    storage, a background other than 4 or 8, an `out` that is the input or does not fit, or a short or misaligned `ws`."""
+    what = "xbd_fill_holes"
+    if isinstance(background, bool) or not isinstance(background, int) or background not in (4, 8):
+        raise ValueError("%s: background connectivity %r is neither 4 nor 8" % (what, background))
+    N, H, W = _cc_image(what, "map_u8", map_u8, torch.uint8)
+    named = [("map_u8", map_u8, torch.uint8, None, "[N, H, W]")]
+    if out is not None:
+        named.append(("out", out, torch.uint8, (N, H, W), str([N, H, W])))
+    if ws is not None:
+        named.append(("ws", ws, torch.uint8, None, "workspace"))
+    _cc_tensors(what, named)
+    _morph_apart(what, "map_u8", map_u8, out)
+    need = xbd_fill_holes_ws_bytes(N, H, W)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=map_u8.device)
+    elif ws.numel() < need or ws.data_ptr() % 4:
+        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
+    if out is None:
+        out = torch.empty(N, H, W, dtype=torch.uint8, device=map_u8.device)
+    _call("dh_xbd_fill_holes_u8", _vp(map_u8.data_ptr()), N, H, W, int(background), _vp(out.data_ptr()), _vp(ws.data_ptr()),
+          ws.numel(), S())
+    return out
+
+
 # ---- the change-detection evaluator's picture (csrc/cd_visual.hip) -----------------------------------------
 def cd_vis_shape(N, H, W):
     """the shape of the evaluator's picture of N images H x W: make_grid's min(8, N) tiles per row, padding 0, four bands"""

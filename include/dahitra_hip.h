@@ -867,6 +867,43 @@ int dh_xbd_cc_match_ws_bytes(int N, int cap_a, int cap_b, long* bytes);
 int dh_xbd_cc_match(const int* labels_a, const int* labels_b, int N, int H, int W, int cap_a, int cap_b, int iou_num, int iou_den,
                     int* match_a, int* match_b, void* ws, long ws_bytes, void* stream);
 
+/* ---- xBD masks: square-window morphology, the dilated training masks, hole filling (csrc/xbd_morph.hip) -----------------------
+ * All integer, bit-exact.  k is the side of the square window: odd, 1 .. 31; r = k / 2.
+ * dh_xbd_morph_u8: src [N][H][W] uint8 (nonzero = set) -> dst [N][H][W] uint8, 0 / 1.
+ *   op 0 (dilate): dst = 1 where any pixel of the k x k window centred on it is set, everything outside the image clear:
+ *     scipy.ndimage.binary_dilation(a, structure=ones((k, k))), skimage.morphology.dilation(a, square(k)).
+ *   op 1 (erode): dst = 1 where every pixel of the window is set, everything outside the image SET:
+ *     binary_erosion(a, structure=ones((k, k)), border_value=1), skimage's erosion.
+ *   One launch.  A workgroup owns a dh_xbd_morph_tile_h() x dh_xbd_morph_tile_w() tile of dst and stages it with its halo in LDS,
+ *   four pixels to a dword; the window is separable (rows, then columns) and each pass doubles (widths 1, 2, 4, .. then the two
+ *   overlapping windows that make k), so the cost grows with log k.  Erosion is the dilation of the complement (De Morgan).
+ * dh_xbd_msk_dilate_u8: msk [N][5][H][W] uint8 mask channels (dh_xbd_augment_u8's out_msk; nonzero = set) -> out [N][5][H][W],
+ *   0 / 1: with d_c = dilate(msk[c], k) for c = 1 .. 4 (channel 0 is not read), the priority rule of
+ *   xBD_code/train_unettransformer.py:262-273,
+ *     out[2] = d2, out[3] = d3 & ~d2, out[4] = d4 & ~d2 & ~d3, out[1] = d1 & ~(d2 | d3 | d4), out[0] = out[1] | .. | out[4].
+ *   One launch of the same kernel: the four channels are four bit planes of the staged byte.
+ * dh_xbd_fill_holes_u8: src [N][H][W] uint8 (nonzero = set) -> dst [N][H][W] uint8, 0 / 1: src != 0, plus every component of
+ *   src == 0 (background connectivity 4 or 8) that has no pixel on the image border:
+ *   scipy.ndimage.binary_fill_holes(a, structure=generate_binary_structure(2, 1 for 4, 2 for 8)).
+ *   Nine launches whatever the data, nothing read back: the key src == 0 and the cleared marks, dh_xbd_cc_label's six, one thread
+ *   per border pixel that stores mark[label] = 1 (plain byte stores of one value: no atomic, no order), the write of dst.  The
+ *   marks are bytes [N][H W + 1] indexed by the label, so there is no cap on the number of holes.
+ *   ws: the caller's workspace of at least dh_xbd_fill_holes_ws_bytes bytes (written to *bytes, a host pointer), 4-byte aligned:
+ *   labels and count, the labelling's workspace, the key and the marks.  Nothing needs clearing; the sequence replays from a
+ *   captured graph.
+ * Any H, W >= 1; W % 4 == 0 with 4-byte aligned pointers takes dword loads and stores, anything else goes byte by byte with the
+ * same result.  Every output byte is written and nothing outside the source is read.
+ * Refused (nothing is written, non-zero, dh_last_error begins with xbd_morph / xbd_msk_dilate / xbd_fill_holes): a null pointer,
+ * N < 1, N > 65535, H < 1, W < 1, H * W >= 2^31, an even k or one outside 1 .. 31, op outside {0, 1}, background outside {4, 8},
+ * an output that overlaps its input, a misaligned or short workspace. */
+int dh_xbd_morph_tile_h(void);
+int dh_xbd_morph_tile_w(void);
+int dh_xbd_morph_u8(const unsigned char* src, int N, int H, int W, int k, int op, unsigned char* dst, void* stream);
+int dh_xbd_msk_dilate_u8(const unsigned char* msk, int N, int H, int W, int k, unsigned char* out, void* stream);
+int dh_xbd_fill_holes_ws_bytes(int N, int H, int W, long* bytes);
+int dh_xbd_fill_holes_u8(const unsigned char* src, int N, int H, int W, int background, unsigned char* dst, void* ws,
+                         long ws_bytes, void* stream);
+
 /* ---- the change-detection evaluator's picture (models/evaluator.py:118-131; csrc/cd_visual.hip) ------------------------------
  * dh_cd_eval_vis_u8: A, B [N][3][H][W] fp32 (as the net receives them), logits [N][C][H][W] fp32, label [N][H][W] int64 ->
  * out [4 * rows * H][cols * W][3] uint8 RGB, cols = min(8, N), rows = ceil(N / cols) (make_grid, padding 0): four bands of
