@@ -645,6 +645,85 @@ class GraphedXbdPredictStep:
     __call__ = step
 
 
+class GraphedXbdEnsembleStep:
+    """GraphedXbdPredictStep for a list of snapshots and 4 or 8 views (xBD_code/predict_test_cls.py:38-55, 81-91) as ONE HIP
+    graph: dh_xbd_tta_pack_views_u8 once, the eval-mode forward of every net at batch views * N on that one static input, and
+    dh_xbd_tta_merge_multi_u8 (sigmoid, un-view, the float32 mean over models and views in the script's order, uint8).
+
+        step = GraphedXbdEnsembleStep([net_a, net_b], pre_u8, post_u8, views=8)      # net.eval() is called on each
+        msk = step(pre_u8, post_u8)                             # the static [N, H, W, 5] uint8 tensor, valid until the next replay
+
+    All nets are on the device of pre_u8; the same net may appear twice (the script's behaviour for a repeated snapshot).  The
+    shapes are static and CHECKED: a pair of another shape raises ValueError, nothing is broadcast.  The parameters are read
+    when the graph replays."""
+
+    def __init__(self, nets, pre_u8, post_u8, order='bgr', views=4, warmup=2):
+        if not isinstance(nets, (list, tuple)) or not 1 <= len(nets) <= ops.XBD_TTA_MAX_MODELS:
+            raise ValueError("GraphedXbdEnsembleStep: nets is not a list of 1 .. %d models" % ops.XBD_TTA_MAX_MODELS)
+        self.nets, self.order, self.views = list(nets), order, views
+        self.inp = ops.xbd_tta_pack_views(pre_u8, post_u8, order, views)      # validates the pair; the static input of the forwards
+        for net in self.nets:
+            if next(net.parameters()).device != pre_u8.device:
+                raise ValueError("GraphedXbdEnsembleStep: a net is on %s, the pair on %s" % (next(net.parameters()).device, pre_u8.device))
+            net.eval()
+        self.pre, self.post = pre_u8.clone(), post_u8.clone()
+        N, H, W, _ = pre_u8.shape
+        self.out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=pre_u8.device)
+        for net in self.nets:
+            net._ensure_arena(pre_u8.device)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self._body()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
+        ops.rekey_workspace(pre_u8.device, s, cs)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cs):
+            self.logits = self._body()
+        self._pinned = [ops.pin_captured_buffers(net) for net in self.nets]
+        self._generations = [net._arena.generation for net in self.nets]
+        torch.cuda.synchronize()
+
+    def _check(self, pre_u8, post_u8):
+        want = tuple(self.pre.shape)
+        for name, t in (("pre_u8", pre_u8), ("post_u8", post_u8)):
+            if not torch.is_tensor(t) or tuple(t.shape) != want or t.dtype != torch.uint8 or t.device != self.pre.device:
+                raise ValueError("GraphedXbdEnsembleStep: %s %s %s, the step holds uint8 %s on %s"
+                                 % (name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)), list(want), self.pre.device))
+
+    def _body(self):
+        ops.xbd_tta_pack_views(self.pre, self.post, self.order, self.views, out=self.inp)
+        logits = []
+        with torch.no_grad():
+            for net in self.nets:
+                logits.append(net(self.inp).float().contiguous())
+        ops.xbd_tta_merge_multi(logits, self.views, out=self.out)
+        return logits
+
+    def stale(self):
+        """whether a net's parameter arena was rebuilt after the capture"""
+        return any(net._arena.generation != g for net, g in zip(self.nets, self._generations))
+
+    def step(self, pre_u8=None, post_u8=None):
+        if self.stale():
+            raise RuntimeError("dahitra_amd: a net's parameter arena was rebuilt after this ensemble step was captured; "
+                               "build a new GraphedXbdEnsembleStep")
+        if any(net.training for net in self.nets):
+            raise RuntimeError("dahitra_amd: GraphedXbdEnsembleStep replays the eval-mode forward; call net.eval() on every net (a "
+                               "train-mode forward in between re-packs the weights for training)")
+        if pre_u8 is not None or post_u8 is not None:
+            self._check(pre_u8, post_u8)
+            self.pre.copy_(pre_u8, non_blocking=True)
+            self.post.copy_(post_u8, non_blocking=True)
+        self.graph.replay()
+        return self.out
+
+    __call__ = step
+
+
 class GraphedXbdStep(GraphedTrainStep):
     """The xBD step (xBD_code/train.py:331-374) as one HIP graph: forward of the 6-channel model, the five weighted
     ComboLoss terms, backward, clip_grad_norm_(0.999) and the hand-rolled AdamW.

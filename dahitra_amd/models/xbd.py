@@ -15,6 +15,10 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
     dice(im1, im2, empty_score=1.0)                   xBD_code/utils.py:124-154   as val_score's per-image term, on counts
     predict_dir(model, test_dir, pred_folder)         xBD_code/predict_test_cls.py:58-97 (the 4-flip TTA loop and its files)
         the reference reads the two folders and its list `models` from globals; here they are arguments
+    load_snapshot(model, path)                        xBD_code/predict_test_cls.py:43-53 (the size-matched copy of a snapshot)
+    predict_ensemble(models, pre_u8, post_u8)         xBD_code/predict_test_cls.py:81-94 for a list of several snapshots: every
+        model's un-flipped sigmoids in one stack, numpy's float32 mean over it; views=8 adds the transposed views
+    predict_dir_ensemble(models, test_dir, pred_folder)   predict_dir's loop and files on predict_ensemble
     visualize_dir(model, test_dir, mask_dir, out_dir) xBD_code/visualize_results.py:171-223 (pre | post | truth | prediction PNGs)
         damage_map / visual_grid are its lines 206-211 / 213-220 on device tensors; the folders are arguments here too, and
         the localisation probability is channel 0 of the same prediction (the script's separate localisation net is not built)
@@ -22,7 +26,7 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
         damage class per building by vote, and the building-level confusion and F1 against the ground truth
     dilate / erode / opening / closing / fill_holes / clean_footprint   no counterpart: square-window morphology and hole
         filling of a footprint before its buildings are counted (scipy.ndimage's binary_* functions are the oracle)
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_visual.hip,
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_ensemble.hip, csrc/xbd_visual.hip,
 csrc/xbd_buildings.hip, csrc/xbd_morph.hip + the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
@@ -534,6 +538,122 @@ def predict_dir(model, test_dir, pred_folder, order='bgr', graph=True):
                                                                         compress_level=9)
         written.append(f)
     return written
+
+
+# ---- prediction with several snapshots and 4 or 8 views (predict_test_cls.py:38-55, 81-91) -----------------------------------
+def _ensemble(what, models):
+    if not isinstance(models, (list, tuple)) or not 1 <= len(models) <= ops.XBD_TTA_MAX_MODELS:
+        raise ValueError("%s: models is not a list of 1 .. %d nets (%s)" % (
+            what, ops.XBD_TTA_MAX_MODELS, len(models) if isinstance(models, (list, tuple)) else type(models)))
+    return list(models)
+
+
+def _ensemble_step(models, pre_u8, post_u8, order, views):
+    """the recorded step of this list of models, shape, order, views and device, kept on the first model (as _predict_step
+    keeps one per model); rebuilt when any net's arena generation moved.  A kept step holds its nets, so their ids stay theirs."""
+    from ..graph import GraphedXbdEnsembleStep
+    steps = models[0].__dict__.setdefault('_xbd_ensemble_steps', {})
+    key = (tuple(id(m) for m in models), tuple(pre_u8.shape), order, views, str(pre_u8.device))
+    step = steps.get(key)
+    if step is not None and step.stale():
+        step = None
+    if step is None:
+        step = steps[key] = GraphedXbdEnsembleStep(models, pre_u8, post_u8, order, views)
+    return step
+
+
+def predict_ensemble(models, pre_u8, post_u8, order='bgr', views=4, graph=True):
+    """predict_tta for the script's list `models` with more than one snapshot in it, and for 4 or 8 views.  models: a list or
+    tuple of 1 .. 8 nets on one device (the same net may appear twice); pre_u8, post_u8 [N, H, W, 3] uint8 as in predict_tta.
+    The views of the normalised 6-channel image (ops.xbd_tta_pack_views: views=4 are the script's four flips, views=8 adds
+    their transposes -- all eight symmetries of the square, what train_unettransformer.py:135-144 trains with -- and needs
+    H == W) go through every eval-mode model as one batch of views * N; every model's sigmoids are brought back, and all
+    M * views maps are averaged in float32 in the order `for model in models: pred.append(...)` stacks them and numpy's
+    mean(axis=0) adds them, then written as uint8(mean * 255).  Returns the device tensor [N, H, W, 5] uint8, channels last.
+    With one model and views=4 the bytes are predict_tta's.  (Averaging several predict_tta results is something else: each is
+    already a byte.)
+    graph=True replays one GraphedXbdEnsembleStep, kept on the first model and recorded once per list of models, shape, order,
+    views and device; the returned tensor is that step's static output, valid until the next call with the same key.
+    graph=False runs the stages eagerly into a new tensor.  Both give the same bytes.  ValueError for an empty or too long list,
+    an unknown order, views outside {4, 8} or views=8 with H != W; CPU tensors raise HipLibraryError."""
+    models = _ensemble("predict_ensemble", models)
+    if order not in ops.XBD_TTA_ORDER:
+        raise ValueError("predict_ensemble: order %r is not one of %s" % (order, sorted(ops.XBD_TTA_ORDER)))
+    if isinstance(views, bool) or views not in ops.XBD_TTA_VIEWS:
+        raise ValueError("predict_ensemble: views=%r is not one of %s" % (views, list(ops.XBD_TTA_VIEWS)))
+    for t in (pre_u8, post_u8):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback)")
+    if pre_u8.dim() != 4 or pre_u8.shape != post_u8.shape:
+        raise ValueError("predict_ensemble: pre_u8 %s and post_u8 %s are not two [N, H, W, 3] tensors of one shape"
+                         % (tuple(pre_u8.shape), tuple(post_u8.shape)))
+    if views == 8 and pre_u8.shape[1] != pre_u8.shape[2]:
+        raise ValueError("predict_ensemble: views=8 adds the transposes, which need a square image; got %dx%d"
+                         % (pre_u8.shape[1], pre_u8.shape[2]))
+    for m in models:
+        m.eval()
+    if graph:
+        for m in models:
+            m._ensure_arena(pre_u8.device)          # a rebuilt arena shows here, before a stale step could be chosen
+        return _ensemble_step(models, pre_u8, post_u8, order, views).step(pre_u8, post_u8)
+    inp = ops.xbd_tta_pack_views(pre_u8, post_u8, order, views)
+    with torch.no_grad():
+        logits = [m(inp).float().contiguous() for m in models]
+    return ops.xbd_tta_merge_multi(logits, views)
+
+
+def predict_dir_ensemble(models, test_dir, pred_folder, order='bgr', views=4, graph=True):
+    """predict_dir with predict_ensemble in place of predict_tta: the same loop over sorted(listdir(test_dir)), the same skip of a
+    pair whose two shapes differ, the same three files per pair under predict_names(f), written the same way.  With views=8 a
+    pair whose image is not square cannot be transposed: it is skipped, and a line says so.  Returns the list of the pre names
+    whose files were written."""
+    from PIL import Image
+    models = _ensemble("predict_dir_ensemble", models)
+    device = next(models[0].parameters()).device
+    if device.type != 'cuda':
+        raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback): move the models to the GPU")
+    os.makedirs(pred_folder, exist_ok=True)
+    written = []
+    for f in sorted(os.listdir(test_dir)):
+        if '_pre_' not in f:
+            continue
+        fn = os.path.join(test_dir, f)
+        img = np.array(Image.open(fn).convert('RGB'))
+        img2 = np.array(Image.open(fn.replace('_pre_', '_post_')).convert('RGB'))
+        if img.shape != img2.shape:
+            continue
+        if views == 8 and img.shape[0] != img.shape[1]:
+            print("skipping {}: views=8 needs a square image, got {}x{}".format(f, img.shape[0], img.shape[1]))
+            continue
+        pre, post = (torch.from_numpy(a).to(device).unsqueeze(0) for a in (img, img2))
+        msk = predict_ensemble(models, pre, post, order=order, views=views, graph=graph)[0].cpu().numpy()
+        full, part1, part2 = predict_names(f)
+        np.save(os.path.join(pred_folder, full), msk)
+        for name, part in ((part1, msk[..., :3]), (part2, msk[..., 2:])):
+            Image.fromarray(np.ascontiguousarray(part[..., ::-1])).save(os.path.join(pred_folder, name), format='PNG',
+                                                                        compress_level=9)
+        written.append(f)
+    return written
+
+
+def load_snapshot(model, path):
+    """Lines 43-53 of predict_test_cls.py for one snapshot: torch.load(path, map_location='cpu'), take ['state_dict'], copy every
+    key the model has with the same size and leave the model's other tensors as they are, print the script's two lines.  The
+    script loads into nn.DataParallel(model), whose keys carry a 'module.' prefix; here a snapshot's keys are accepted with or
+    without it, so the snapshots evaluate_val and evaluate_val_sweep write load as well as the script's.  The caller moves the
+    model to the device and calls eval(), as the script does next.  Returns (epoch, best_score)."""
+    print("=> loading checkpoint '{}'".format(path))
+    checkpoint = torch.load(path, map_location='cpu', weights_only=False)      # 'best_score' is a numpy scalar, 'optimizer' a dict
+    loaded_dict = checkpoint['state_dict']
+    sd = model.state_dict()
+    for k in model.state_dict():
+        for name in (k, 'module.' + k):
+            if name in loaded_dict and sd[k].size() == loaded_dict[name].size():
+                sd[k] = loaded_dict[name]
+                break
+    model.load_state_dict(sd)
+    print("loaded checkpoint '{}' (epoch {}, best_score {})".format(path, checkpoint['epoch'], checkpoint['best_score']))
+    return checkpoint['epoch'], checkpoint['best_score']
 
 
 # ---- damage map and visual grid (xBD_code/visualize_results.py:171-223) ----------------------------------------------

@@ -2091,6 +2091,76 @@ def xbd_tta_merge(logits, out=None):
     return out
 
 
+# ---- xBD prediction for several snapshots and 4 or 8 views (csrc/xbd_ensemble.hip) -------------------------
+XBD_TTA_VIEWS = (4, 8)
+XBD_TTA_MAX_MODELS = 8
+
+
+def _tta_views(what, views, H, W):
+    if isinstance(views, bool) or views not in XBD_TTA_VIEWS:
+        raise ValueError("%s: views=%r is not one of %s" % (what, views, list(XBD_TTA_VIEWS)))
+    if views == 8 and H != W:
+        raise ValueError("%s: views=8 adds the transposes, which need a square image; got %dx%d" % (what, H, W))
+    return int(views)
+
+
+def xbd_tta_pack_views(pre_u8, post_u8, order="bgr", views=4, out=None):
+    """xbd_tta_pack for 4 or 8 views.  pre_u8, post_u8 [N, H, W, 3] uint8 -> [views * N, 6, H, W] float32: image views * n + v is
+    view_v of concat(pre_n, post_n), every byte as float32(b) / 127 - 1.  view_v = flip_v for v < 4 (xbd_tta_pack's flips: with
+    views=4 the same bytes as that call); view_{4+k} is the transpose of flip_k, so the eight views are the symmetries of the
+    square: identity, the two flips, rot180, transpose, anti-transpose and both rot90.  views=8 needs H == W.  order and out as
+    in xbd_tta_pack.  ValueError, before any launch, for a wrong rank, dtype or device, non-contiguous storage, an unknown
+    order, views outside {4, 8} or views=8 on an image that is not square."""
+    what = "xbd_tta_pack_views"
+    if order not in XBD_TTA_ORDER:
+        raise ValueError("%s: order %r is not one of %s" % (what, order, sorted(XBD_TTA_ORDER)))
+    _tta_tensor(what, "pre_u8", pre_u8, torch.uint8, "[N, H, W, 3]", lambda t: t.dim() == 4 and t.shape[3] == 3)
+    N, H, W, _ = pre_u8.shape
+    V = _tta_views(what, views, H, W)
+    _tta_tensor(what, "post_u8", post_u8, torch.uint8, "[%d, %d, %d, 3] like pre_u8" % (N, H, W),
+                lambda t: t.shape == pre_u8.shape, pre_u8.device)
+    if out is None:
+        out = torch.empty(V * N, 6, H, W, dtype=torch.float32, device=pre_u8.device)
+    else:
+        _tta_tensor(what, "out", out, torch.float32, "[%d, 6, %d, %d]" % (V * N, H, W),
+                    lambda t: tuple(t.shape) == (V * N, 6, H, W), pre_u8.device)
+    _call("dh_xbd_tta_pack_views_u8", _vp(pre_u8.data_ptr()), _vp(post_u8.data_ptr()), N, H, W, XBD_TTA_ORDER[order], V,
+          _vp(out.data_ptr()), S())
+    return out
+
+
+def xbd_tta_merge_multi(logits_list, views=4, out=None):
+    """xbd_tta_merge for a list of models and 4 or 8 views.  logits_list: 1 .. 8 tensors [views * N, 5, H, W] float32 of one
+    shape on one device, entry m the answers of model m to xbd_tta_pack_views' batch -> [N, H, W, 5] uint8, channels last.
+    Per pixel and channel in float32: every sigmoid with its view undone, added one after the other, model-major and
+    view-minor (the order in which the script appends to its stack, which numpy's mean(axis=0) then adds in), divided by
+    float32(M * views), uint8(trunc(mean * 255)).  A NaN gives 0.  With one model and views=4 the same bytes as xbd_tta_merge.
+    ValueError, before any launch, for an empty or too long list, a wrong rank, dtype or device, non-contiguous storage,
+    tensors of different shapes, views outside {4, 8}, a batch that is no multiple of views or views=8 with H != W."""
+    what = "xbd_tta_merge_multi"
+    if not isinstance(logits_list, (list, tuple)) or not 1 <= len(logits_list) <= XBD_TTA_MAX_MODELS:
+        raise ValueError("%s: logits_list is not a list of 1 .. %d tensors (%s)" % (
+            what, XBD_TTA_MAX_MODELS, len(logits_list) if isinstance(logits_list, (list, tuple)) else type(logits_list)))
+    first = logits_list[0]
+    _tta_tensor(what, "logits_list[0]", first, torch.float32, "[views N, 5, H, W]", lambda t: t.dim() == 4 and t.shape[1] == 5)
+    B, _, H, W = first.shape
+    V = _tta_views(what, views, H, W)
+    if B % V:
+        raise ValueError("%s: a batch of %d logits is not %d views per image" % (what, B, V))
+    N = B // V
+    for m, t in enumerate(logits_list[1:], 1):
+        _tta_tensor(what, "logits_list[%d]" % m, t, torch.float32, "%s like logits_list[0]" % list(first.shape),
+                    lambda t: t.shape == first.shape, first.device)
+    if out is None:
+        out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=first.device)
+    else:
+        _tta_tensor(what, "out", out, torch.uint8, "[%d, %d, %d, 5]" % (N, H, W),
+                    lambda t: tuple(t.shape) == (N, H, W, 5), first.device)
+    table = (ctypes.c_void_p * len(logits_list))(*[t.data_ptr() for t in logits_list])      # read by the entry, not the kernel
+    _call("dh_xbd_tta_merge_multi_u8", ctypes.cast(table, ctypes.c_void_p), len(logits_list), V, N, H, W, _vp(out.data_ptr()), S())
+    return out
+
+
 # ---- xBD damage map and visual grid (csrc/xbd_visual.hip) --------------------------------------------------
 XBD_LOC_THR = (0.38, 0.13, 0.14)          # _thr of xBD_code/visualize_results.py
 

@@ -779,6 +779,27 @@ int dh_xbd_tta_pack_u8(const unsigned char* pre, const unsigned char* post, int 
                        void* stream);
 int dh_xbd_tta_merge_u8(const float* logits, int N, int H, int W, unsigned char* out, void* stream);
 
+/* ---- xBD prediction for M snapshots and V = 4 or 8 views (predict_test_cls.py:38-55, 81-91; csrc/xbd_ensemble.hip) ---------
+ * view_v = flip_v for v < 4; view_{4+k}(x)[c][i][j] = flip_k(x)[c][j][i], the transpose of flip_k: with V = 8 the eight
+ * symmetries of the square, each once.  Undoing view 4 + k on an output s is flip_k(transpose(s)).  V = 8 needs H == W.
+ * dh_xbd_tta_pack_views_u8: pre, post [N][H][W][3] uint8 -> inp [V N][6][H][W] fp32, inp[V n + v] = view_v(concat(pre_n, post_n)),
+ *   bytes normalised and `bgr` as in dh_xbd_tta_pack_u8; with V = 4 the same bytes as that call.
+ * dh_xbd_tta_merge_multi_u8: logits_host_table is a HOST array of M device pointers, each to one model's contiguous
+ *   [V N][5][H][W] fp32 logits; the entry reads and checks the table and hands the pointers to the kernel by value.
+ *   u_{m,v} = un-view_v(sigmoid(logits_m[V n + v])) in fp32; t = (((u_{0,0} + u_{0,1}) + ...) + u_{M-1,V-1}), model-major and
+ *   view-minor, one fp32 add after the other (numpy's float32 mean over the script's stack); mean = t / (float)(M V), a true
+ *   division; out [N][H][W][5] uint8 = uint8(trunc(float32(mean * 255))), channels last; a NaN gives 0.  With M = 1 and V = 4
+ *   the same bytes as dh_xbd_tta_merge_u8.
+ * Both work on 32 x 32 pixel tiles staged in LDS (row pitch 33 floats), so the transposed views are read and written as row
+ * segments too; both launch one kernel and nothing else and write every byte of their output.  pre / post / out may start at any
+ * byte; pointers not aligned to their vector, or a W that is no multiple of 4, take a scalar path with the same result.
+ * Refused (nothing is written): a null pointer or table entry, V not 4 or 8, N < 1, V N > 65535, H < 1, W < 1, H * W >= 2^31,
+ * V = 8 with H != W, M outside 1..8, a float pointer that is not 4-byte aligned. */
+int dh_xbd_tta_pack_views_u8(const unsigned char* pre, const unsigned char* post, int N, int H, int W, int bgr, int V, float* inp,
+                             void* stream);
+int dh_xbd_tta_merge_multi_u8(const float* const* logits_host_table, int M, int V, int N, int H, int W, unsigned char* out,
+                              void* stream);
+
 /* ---- xBD damage map and the 4-panel visual grid (xBD_code/visualize_results.py:204-220; csrc/xbd_visual.hip) ---------------
  * msk [N][H][W][5] uint8, channels last: what dh_xbd_tta_merge_u8 writes.  All integer.
  *   class: dmg = 1 + index of the first maximum of msk[1..4] (a tie goes to the lowest channel): 1 .. 4.
