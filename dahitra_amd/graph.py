@@ -228,7 +228,68 @@ class GraphedTrainStep:
         return self.loss
 
 
-class GraphedEvalStep:
+class _RecordedEval:
+    """What the recorded evaluation steps below share: how an eval-mode body becomes one HIP graph (`_record`) and what a replay
+    refuses (`_guard`).  A subclass holds its static buffers, its `_body`, its input copy and its shape check."""
+    _word = "evaluation"                                  # "... after this <word> step was captured"
+    _whose, _eval_call = "the net's", "net.eval()"
+
+    def _record(self, nets, device, body, accumulators=(), warmup=2):
+        """net.eval() on every net, `warmup` eager bodies on a side stream, then `body()` captured into self.graph; returns what
+        the captured body returned (its static output).  accumulators: the tensors the body adds to (None entries are skipped);
+        they are as they were before, since neither the warm-up nor the capture is part of any count."""
+        self._nets = list(nets)
+        for net in self._nets:
+            net.eval()
+            net._ensure_arena(device)
+        accumulators = [t for t in accumulators if t is not None]
+        saved = [t.clone() for t in accumulators]
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                body()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        for t, t0 in zip(accumulators, saved):
+            t.copy_(t0)
+        # The capture stream inherits the warm-up stream's scratch workspace and is KEPT for the life of the step: released,
+        # PyTorch's stream pool could hand its handle to a later torch.cuda.Stream(), whose eager launches would then look up -- and
+        # scribble over -- the workspace the recorded graph reads and writes.  The captured buffers are pinned for the same
+        # reason (the full account stands at GraphedTrainStep's capture).
+        cs = self._capture_stream = torch.cuda.Stream()
+        ops.rekey_workspace(device, s, cs)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cs):
+            out = body()
+        self._pinned = [ops.pin_captured_buffers(net) for net in self._nets]
+        self._generations = [net._arena.generation for net in self._nets]
+        torch.cuda.synchronize()
+        for t, t0 in zip(accumulators, saved):
+            t.copy_(t0)
+        return out
+
+    @property
+    def _generation(self):
+        """the arena generation of the (first) net at the capture"""
+        return self._generations[0]
+
+    def stale(self):
+        """whether a net's parameter arena was rebuilt after the capture"""
+        return any(net._arena.generation != g for net, g in zip(self._nets, self._generations))
+
+    def _guard(self):
+        """what every replay refuses: a rebuilt arena (the graph holds the old one's addresses) and a net in train mode"""
+        name = type(self).__name__
+        if self.stale():
+            raise RuntimeError("dahitra_amd: %s parameter arena was rebuilt after this %s step was captured; build a new %s"
+                               % (self._whose, self._word, name))
+        if any(net.training for net in self._nets):
+            raise RuntimeError("dahitra_amd: %s replays the eval-mode forward; call %s (a train-mode forward in between re-packs "
+                               "the weights for training)" % (name, self._eval_call))
+
+
+class GraphedEvalStep(_RecordedEval):
     """The evaluation forward (models/evaluator.py:156-164: net.eval(), no gradient state) as ONE HIP graph: the eval-mode weight
     re-pack (every BatchNorm folded into its convolution), the forward and -- with `confusion` -- the arg-max + confusion-matrix
     count against the labels (one kernel, no host read).  ~130 (BiT) / ~200 (DAHiTra) launches per batch become one
@@ -241,30 +302,11 @@ class GraphedEvalStep:
 
     def __init__(self, net, a, b, lab=None, confusion=None, warmup=2):
         self.net, self.confusion = net, confusion
-        net.eval()
         self.a, self.b = a.clone(), b.clone()
         self.lab = lab.clone() if lab is not None else None
         if confusion is not None and lab is None:
             raise ValueError("GraphedEvalStep: a confusion matrix needs the labels")
-        net._ensure_arena(a.device)
-        conf0 = confusion.clone() if confusion is not None else None
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        if confusion is not None:
-            confusion.copy_(conf0)
-        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
-        ops.rekey_workspace(a.device, s, cs)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=cs):
-            self.logits = self._body()
-        self._pinned = ops.pin_captured_buffers(net)
-        self._generation = net._arena.generation
-        torch.cuda.synchronize()
+        self.logits = self._record([net], a.device, self._body, (confusion,), warmup)
 
     def _body(self):
         with torch.no_grad():
@@ -275,12 +317,7 @@ class GraphedEvalStep:
         return logits
 
     def __call__(self, a=None, b=None, lab=None):
-        if self.net._arena.generation != self._generation:
-            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this evaluation step was captured; "
-                               "build a new GraphedEvalStep")
-        if self.net.training:
-            raise RuntimeError("dahitra_amd: GraphedEvalStep replays the eval-mode forward; call net.eval() (a train-mode forward "
-                               "in between re-packs the weights for training)")
+        self._guard()
         if a is not None:
             self.a.copy_(a, non_blocking=True)
             self.b.copy_(b, non_blocking=True)
@@ -362,7 +399,7 @@ class TileBuffers:
         return self.mask, self.logits
 
 
-class GraphedTileStep:
+class GraphedTileStep(_RecordedEval):
     """The change map of one whole tile as ONE HIP graph: dh_augment_pairs_u8 cuts the P views of `plan` (tiles.TilePlan) from
     the pair a static device index names, the eval-mode forward runs over them in chunks of `chunk` views (back to back, into
     one [P, C, h, w] buffer), and dh_cd_tile_stitch blends the answers into the [H, W] class map and [C, H, W] logits -- or, for
@@ -375,41 +412,15 @@ class GraphedTileStep:
     confusion: int64 [C, C] (stitchable plan: the stitched map against the tile's own label plane, accumulated) or [P, C, C]
     (eval_cd plan, required).  chunk: views per forward, a divisor of P (default: the largest up to 16).  Another tile is another
     value of the device index, not another recording.  The parameters are read when the graph replays."""
+    _word = "tile"
 
     def __init__(self, net, pipe, plan, confusion=None, chunk=None, warmup=2):
-        net.eval()
         self.net = net
         self.buf = TileBuffers(net, pipe, plan, confusion, chunk)
-        dev = pipe.a.device
-        net._ensure_arena(dev)
-        conf0 = confusion.clone() if confusion is not None else None
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.buf.run()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        if confusion is not None:
-            confusion.copy_(conf0)                            # the warm-up passes are not part of any count
-        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
-        ops.rekey_workspace(dev, s, cs)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=cs):
-            self.buf.run()
-        self._pinned = ops.pin_captured_buffers(net)
-        self._generation = net._arena.generation
-        torch.cuda.synchronize()
-        if confusion is not None:
-            confusion.copy_(conf0)
+        self._record([net], pipe.a.device, self.buf.run, (confusion,), warmup)
 
     def step(self, index):
-        if self.net._arena.generation != self._generation:
-            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this tile step was captured; "
-                               "build a new GraphedTileStep")
-        if self.net.training:
-            raise RuntimeError("dahitra_amd: GraphedTileStep replays the eval-mode forward; call net.eval() (a train-mode "
-                               "forward in between re-packs the weights for training)")
+        self._guard()
         self.buf.aim(index)
         self.graph.replay()
         return self.buf.mask, self.buf.logits
@@ -417,7 +428,45 @@ class GraphedTileStep:
     __call__ = step
 
 
-class GraphedXbdEvalStep:
+class _RecordedXbdBatch(_RecordedEval):
+    """The static batch of the two validation steps: imgs, channel 0 of msk and lbl_msk, checked and copied by every call"""
+
+    def _hold(self, imgs, msk, lbl_msk):
+        self._check(imgs, msk, lbl_msk, tuple(imgs.shape))
+        self.imgs = imgs.clone()
+        self.msk0 = self._plane0(msk).to(torch.uint8).contiguous().clone()
+        self.lbl = lbl_msk.to(torch.uint8).contiguous().clone()
+
+    @staticmethod
+    def _plane0(msk):
+        return msk[:, 0] if msk.dim() == 4 else msk
+
+    def _check(self, imgs, msk, lbl_msk, want):
+        """`want`: the [B, 6, H, W] the step holds.  Every tensor must have exactly its shape: copy_ would broadcast a [1, ...]
+        batch over the static buffer and score one image B times."""
+        name = type(self).__name__
+        B, _, H, W = want
+        if imgs.dim() != 4 or imgs.shape[1] != 6 or tuple(imgs.shape) != tuple(want):
+            raise ValueError("%s: imgs %s, the step holds [%d, 6, %d, %d]" % (name, tuple(imgs.shape), B, H, W))
+        if tuple(msk.shape) not in ((B, 5, H, W), (B, H, W)):
+            raise ValueError("%s: msk %s is neither [%d, 5, %d, %d] nor its channel 0" % (name, tuple(msk.shape), B, H, W))
+        if tuple(lbl_msk.shape) != (B, H, W):
+            raise ValueError("%s: lbl_msk %s, the step holds [%d, %d, %d]" % (name, tuple(lbl_msk.shape), B, H, W))
+
+    def __call__(self, imgs=None, msk=None, lbl_msk=None):
+        self._guard()
+        if imgs is not None:
+            if msk is None or lbl_msk is None:
+                raise ValueError("%s: a batch is imgs, msk and lbl_msk" % type(self).__name__)
+            self._check(imgs, msk, lbl_msk, tuple(self.imgs.shape))
+            self.imgs.copy_(imgs, non_blocking=True)
+            self.msk0.copy_(self._plane0(msk), non_blocking=True)
+            self.lbl.copy_(lbl_msk, non_blocking=True)
+        self.graph.replay()
+        return self.logits
+
+
+class GraphedXbdEvalStep(_RecordedXbdBatch):
     """One validation batch of the xBD loop (xBD_code/train.py:259-279) as ONE HIP graph: the eval-mode weight re-pack, the
     forward of the 6-channel model and dh_xbd_val_count on its logits -- sigmoid, threshold, arg-max and the tp / fn / fp and
     dice counts, no host read.
@@ -431,47 +480,9 @@ class GraphedXbdEvalStep:
 
     def __init__(self, net, imgs, msk, lbl_msk, class_counts, thr=0.3, select='reference', warmup=2):
         self.net, self.class_counts, self.thr, self.select = net, class_counts, float(thr), select
-        net.eval()
-        self._check(imgs, msk, lbl_msk, tuple(imgs.shape))
-        self.imgs = imgs.clone()
-        self.msk0 = self._plane0(msk).to(torch.uint8).contiguous().clone()
-        self.lbl = lbl_msk.to(torch.uint8).contiguous().clone()
+        self._hold(imgs, msk, lbl_msk)
         self.image_counts = torch.zeros(imgs.shape[0], 3, dtype=torch.int64, device=imgs.device)
-        net._ensure_arena(imgs.device)
-        counts0 = class_counts.clone()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        class_counts.copy_(counts0)                          # the warm-up batches are not part of the epoch
-        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
-        ops.rekey_workspace(imgs.device, s, cs)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=cs):
-            self.logits = self._body()
-        self._pinned = ops.pin_captured_buffers(net)
-        self._generation = net._arena.generation
-        torch.cuda.synchronize()
-        class_counts.copy_(counts0)
-
-    @staticmethod
-    def _plane0(msk):
-        return msk[:, 0] if msk.dim() == 4 else msk
-
-    @staticmethod
-    def _check(imgs, msk, lbl_msk, want):
-        """`want`: the [B, 6, H, W] the step holds.  Every tensor must have exactly its shape: copy_ would broadcast a [1, ...]
-        batch over the static buffer and score one image B times."""
-        B, _, H, W = want
-        if imgs.dim() != 4 or imgs.shape[1] != 6 or tuple(imgs.shape) != tuple(want):
-            raise ValueError("GraphedXbdEvalStep: imgs %s, the step holds [%d, 6, %d, %d]" % (tuple(imgs.shape), B, H, W))
-        if tuple(msk.shape) not in ((B, 5, H, W), (B, H, W)):
-            raise ValueError("GraphedXbdEvalStep: msk %s is neither [%d, 5, %d, %d] nor its channel 0" % (tuple(msk.shape), B, H, W))
-        if tuple(lbl_msk.shape) != (B, H, W):
-            raise ValueError("GraphedXbdEvalStep: lbl_msk %s, the step holds [%d, %d, %d]" % (tuple(lbl_msk.shape), B, H, W))
+        self.logits = self._record([net], imgs.device, self._body, (class_counts,), warmup)
 
     def _body(self):
         with torch.no_grad():
@@ -480,25 +491,8 @@ class GraphedXbdEvalStep:
         ops.xbd_val_count(logits, self.msk0, self.lbl, self.image_counts, self.class_counts, self.thr, self.select)
         return logits
 
-    def __call__(self, imgs=None, msk=None, lbl_msk=None):
-        if self.net._arena.generation != self._generation:
-            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this evaluation step was captured; "
-                               "build a new GraphedXbdEvalStep")
-        if self.net.training:
-            raise RuntimeError("dahitra_amd: GraphedXbdEvalStep replays the eval-mode forward; call net.eval() (a train-mode "
-                               "forward in between re-packs the weights for training)")
-        if imgs is not None:
-            if msk is None or lbl_msk is None:
-                raise ValueError("GraphedXbdEvalStep: a batch is imgs, msk and lbl_msk")
-            self._check(imgs, msk, lbl_msk, tuple(self.imgs.shape))
-            self.imgs.copy_(imgs, non_blocking=True)
-            self.msk0.copy_(self._plane0(msk), non_blocking=True)
-            self.lbl.copy_(lbl_msk, non_blocking=True)
-        self.graph.replay()
-        return self.logits
 
-
-class GraphedXbdSweepStep:
+class GraphedXbdSweepStep(_RecordedXbdBatch):
     """GraphedXbdEvalStep for a whole grid of localisation thresholds: the eval-mode weight re-pack, the forward and
     dh_xbd_val_sweep on its logits as ONE HIP graph -- the batch's histograms over (threshold bin, damage arg-max, truth), from
     which models/xbd.sweep_counts gives the counts of every threshold of the grid; no host read.
@@ -509,48 +503,14 @@ class GraphedXbdSweepStep:
     thresholds: 1 .. ops.XBD_SWEEP_MAX floats, ascending inside (0, 1); the graph's kernel node holds them by value.  Shapes are
     static and CHECKED as GraphedXbdEvalStep checks them: another shape raises ValueError, nothing is broadcast.  The parameters
     are read when the graph replays."""
+    _word = "sweep"
 
     def __init__(self, net, imgs, msk, lbl_msk, class_hist, thresholds, select='reference', warmup=2):
         self.net, self.class_hist, self.select = net, class_hist, select
         self.thresholds = ops.xbd_sweep_thresholds(thresholds, "GraphedXbdSweepStep")
-        net.eval()
-        self._check(imgs, msk, lbl_msk, tuple(imgs.shape))
-        self.imgs = imgs.clone()
-        self.msk0 = self._plane0(msk).to(torch.uint8).contiguous().clone()
-        self.lbl = lbl_msk.to(torch.uint8).contiguous().clone()
+        self._hold(imgs, msk, lbl_msk)
         self.image_hist = torch.zeros(imgs.shape[0], self.thresholds.size + 1, 4, 2, dtype=torch.int64, device=imgs.device)
-        net._ensure_arena(imgs.device)
-        hist0 = class_hist.clone()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        class_hist.copy_(hist0)                              # the warm-up batches are not part of the epoch
-        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
-        ops.rekey_workspace(imgs.device, s, cs)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=cs):
-            self.logits = self._body()
-        self._pinned = ops.pin_captured_buffers(net)
-        self._generation = net._arena.generation
-        torch.cuda.synchronize()
-        class_hist.copy_(hist0)
-
-    _plane0 = staticmethod(GraphedXbdEvalStep._plane0)
-
-    @staticmethod
-    def _check(imgs, msk, lbl_msk, want):
-        """`want`: the [B, 6, H, W] the step holds; every tensor must have exactly its shape (see GraphedXbdEvalStep._check)"""
-        B, _, H, W = want
-        if imgs.dim() != 4 or imgs.shape[1] != 6 or tuple(imgs.shape) != tuple(want):
-            raise ValueError("GraphedXbdSweepStep: imgs %s, the step holds [%d, 6, %d, %d]" % (tuple(imgs.shape), B, H, W))
-        if tuple(msk.shape) not in ((B, 5, H, W), (B, H, W)):
-            raise ValueError("GraphedXbdSweepStep: msk %s is neither [%d, 5, %d, %d] nor its channel 0" % (tuple(msk.shape), B, H, W))
-        if tuple(lbl_msk.shape) != (B, H, W):
-            raise ValueError("GraphedXbdSweepStep: lbl_msk %s, the step holds [%d, %d, %d]" % (tuple(lbl_msk.shape), B, H, W))
+        self.logits = self._record([net], imgs.device, self._body, (class_hist,), warmup)
 
     def _body(self):
         with torch.no_grad():
@@ -559,25 +519,35 @@ class GraphedXbdSweepStep:
         ops.xbd_val_sweep(logits, self.msk0, self.lbl, self.image_hist, self.class_hist, self.thresholds, self.select)
         return logits
 
-    def __call__(self, imgs=None, msk=None, lbl_msk=None):
-        if self.net._arena.generation != self._generation:
-            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this sweep step was captured; "
-                               "build a new GraphedXbdSweepStep")
-        if self.net.training:
-            raise RuntimeError("dahitra_amd: GraphedXbdSweepStep replays the eval-mode forward; call net.eval() (a train-mode "
-                               "forward in between re-packs the weights for training)")
-        if imgs is not None:
-            if msk is None or lbl_msk is None:
-                raise ValueError("GraphedXbdSweepStep: a batch is imgs, msk and lbl_msk")
-            self._check(imgs, msk, lbl_msk, tuple(self.imgs.shape))
-            self.imgs.copy_(imgs, non_blocking=True)
-            self.msk0.copy_(self._plane0(msk), non_blocking=True)
-            self.lbl.copy_(lbl_msk, non_blocking=True)
+
+class _RecordedXbdPair(_RecordedEval):
+    """The static pre / post pair of the two prediction steps and their [N, H, W, 5] answer: checked and copied by every call"""
+
+    def _hold(self, pre_u8, post_u8):
+        self.pre, self.post = pre_u8.clone(), post_u8.clone()
+        N, H, W, _ = pre_u8.shape
+        self.out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=pre_u8.device)
+
+    def _check(self, pre_u8, post_u8):
+        want = tuple(self.pre.shape)
+        for name, t in (("pre_u8", pre_u8), ("post_u8", post_u8)):
+            if not torch.is_tensor(t) or tuple(t.shape) != want or t.dtype != torch.uint8 or t.device != self.pre.device:
+                raise ValueError("%s: %s %s %s, the step holds uint8 %s on %s" % (
+                    type(self).__name__, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)), list(want), self.pre.device))
+
+    def step(self, pre_u8=None, post_u8=None):
+        self._guard()
+        if pre_u8 is not None or post_u8 is not None:
+            self._check(pre_u8, post_u8)
+            self.pre.copy_(pre_u8, non_blocking=True)
+            self.post.copy_(post_u8, non_blocking=True)
         self.graph.replay()
-        return self.logits
+        return self.out
+
+    __call__ = step
 
 
-class GraphedXbdPredictStep:
+class GraphedXbdPredictStep(_RecordedXbdPair):
     """The prediction of one batch of pre / post pairs (xBD_code/predict_test_cls.py:62-94) as ONE HIP graph:
     dh_xbd_tta_pack_u8 (the four flips of the normalised 6-channel image), the eval-mode forward at batch 4N and
     dh_xbd_tta_merge_u8 (sigmoid, un-flip, float32 mean, uint8), no host read.
@@ -588,37 +558,13 @@ class GraphedXbdPredictStep:
     pre_u8, post_u8 [N, H, W, 3] uint8 on the device.  order: 'bgr' (default, the script as executed) or 'rgb', see
     ops.xbd_tta_pack.  The shapes are static and CHECKED: a pair of another shape raises ValueError, nothing is broadcast.  The
     parameters are read when the graph replays."""
+    _word = "prediction"
 
     def __init__(self, net, pre_u8, post_u8, order='bgr', warmup=2):
         self.net, self.order = net, order
-        net.eval()
         self.inp = ops.xbd_tta_pack(pre_u8, post_u8, order)          # validates the pair; the static input of the forward
-        self.pre, self.post = pre_u8.clone(), post_u8.clone()
-        N, H, W, _ = pre_u8.shape
-        self.out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=pre_u8.device)
-        net._ensure_arena(pre_u8.device)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
-        ops.rekey_workspace(pre_u8.device, s, cs)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=cs):
-            self.logits = self._body()
-        self._pinned = ops.pin_captured_buffers(net)
-        self._generation = net._arena.generation
-        torch.cuda.synchronize()
-
-    def _check(self, pre_u8, post_u8):
-        want = tuple(self.pre.shape)
-        for name, t in (("pre_u8", pre_u8), ("post_u8", post_u8)):
-            if not torch.is_tensor(t) or tuple(t.shape) != want or t.dtype != torch.uint8 or t.device != self.pre.device:
-                raise ValueError("GraphedXbdPredictStep: %s %s %s, the step holds uint8 %s on %s"
-                                 % (name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)), list(want), self.pre.device))
+        self._hold(pre_u8, post_u8)
+        self.logits = self._record([net], pre_u8.device, self._body, warmup=warmup)
 
     def _body(self):
         ops.xbd_tta_pack(self.pre, self.post, self.order, out=self.inp)
@@ -628,24 +574,8 @@ class GraphedXbdPredictStep:
         ops.xbd_tta_merge(logits, out=self.out)
         return logits
 
-    def step(self, pre_u8=None, post_u8=None):
-        if self.net._arena.generation != self._generation:
-            raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt after this prediction step was captured; "
-                               "build a new GraphedXbdPredictStep")
-        if self.net.training:
-            raise RuntimeError("dahitra_amd: GraphedXbdPredictStep replays the eval-mode forward; call net.eval() (a train-mode "
-                               "forward in between re-packs the weights for training)")
-        if pre_u8 is not None or post_u8 is not None:
-            self._check(pre_u8, post_u8)
-            self.pre.copy_(pre_u8, non_blocking=True)
-            self.post.copy_(post_u8, non_blocking=True)
-        self.graph.replay()
-        return self.out
 
-    __call__ = step
-
-
-class GraphedXbdEnsembleStep:
+class GraphedXbdEnsembleStep(_RecordedXbdPair):
     """GraphedXbdPredictStep for a list of snapshots and 4 or 8 views (xBD_code/predict_test_cls.py:38-55, 81-91) as ONE HIP
     graph: dh_xbd_tta_pack_views_u8 once, the eval-mode forward of every net at batch views * N on that one static input, and
     dh_xbd_tta_merge_multi_u8 (sigmoid, un-view, the float32 mean over models and views in the script's order, uint8).
@@ -656,6 +586,8 @@ class GraphedXbdEnsembleStep:
     All nets are on the device of pre_u8; the same net may appear twice (the script's behaviour for a repeated snapshot).  The
     shapes are static and CHECKED: a pair of another shape raises ValueError, nothing is broadcast.  The parameters are read
     when the graph replays."""
+    _word = "ensemble"
+    _whose, _eval_call = "a net's", "net.eval() on every net"
 
     def __init__(self, nets, pre_u8, post_u8, order='bgr', views=4, warmup=2):
         if not isinstance(nets, (list, tuple)) or not 1 <= len(nets) <= ops.XBD_TTA_MAX_MODELS:
@@ -665,34 +597,8 @@ class GraphedXbdEnsembleStep:
         for net in self.nets:
             if next(net.parameters()).device != pre_u8.device:
                 raise ValueError("GraphedXbdEnsembleStep: a net is on %s, the pair on %s" % (next(net.parameters()).device, pre_u8.device))
-            net.eval()
-        self.pre, self.post = pre_u8.clone(), post_u8.clone()
-        N, H, W, _ = pre_u8.shape
-        self.out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=pre_u8.device)
-        for net in self.nets:
-            net._ensure_arena(pre_u8.device)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        cs = self._capture_stream = torch.cuda.Stream()       # (kept: see GraphedTrainStep)
-        ops.rekey_workspace(pre_u8.device, s, cs)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=cs):
-            self.logits = self._body()
-        self._pinned = [ops.pin_captured_buffers(net) for net in self.nets]
-        self._generations = [net._arena.generation for net in self.nets]
-        torch.cuda.synchronize()
-
-    def _check(self, pre_u8, post_u8):
-        want = tuple(self.pre.shape)
-        for name, t in (("pre_u8", pre_u8), ("post_u8", post_u8)):
-            if not torch.is_tensor(t) or tuple(t.shape) != want or t.dtype != torch.uint8 or t.device != self.pre.device:
-                raise ValueError("GraphedXbdEnsembleStep: %s %s %s, the step holds uint8 %s on %s"
-                                 % (name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)), list(want), self.pre.device))
+        self._hold(pre_u8, post_u8)
+        self.logits = self._record(self.nets, pre_u8.device, self._body, warmup=warmup)
 
     def _body(self):
         ops.xbd_tta_pack_views(self.pre, self.post, self.order, self.views, out=self.inp)
@@ -702,26 +608,6 @@ class GraphedXbdEnsembleStep:
                 logits.append(net(self.inp).float().contiguous())
         ops.xbd_tta_merge_multi(logits, self.views, out=self.out)
         return logits
-
-    def stale(self):
-        """whether a net's parameter arena was rebuilt after the capture"""
-        return any(net._arena.generation != g for net, g in zip(self.nets, self._generations))
-
-    def step(self, pre_u8=None, post_u8=None):
-        if self.stale():
-            raise RuntimeError("dahitra_amd: a net's parameter arena was rebuilt after this ensemble step was captured; "
-                               "build a new GraphedXbdEnsembleStep")
-        if any(net.training for net in self.nets):
-            raise RuntimeError("dahitra_amd: GraphedXbdEnsembleStep replays the eval-mode forward; call net.eval() on every net (a "
-                               "train-mode forward in between re-packs the weights for training)")
-        if pre_u8 is not None or post_u8 is not None:
-            self._check(pre_u8, post_u8)
-            self.pre.copy_(pre_u8, non_blocking=True)
-            self.post.copy_(post_u8, non_blocking=True)
-        self.graph.replay()
-        return self.out
-
-    __call__ = step
 
 
 class GraphedXbdStep(GraphedTrainStep):

@@ -186,18 +186,62 @@ def val_score(image_counts, class_counts, empty_score=1.0):
     return sc, {'dice': d0, 'f1': f1, 'f1_per_class': f1_sc}
 
 
-def _eval_step(model, batch, class_counts, thr, select):
-    """the model's recorded validation step for this batch shape (kept on the model: a graph pins its buffers for the life of
-    the process, so an epoch must not record a new one)"""
-    from ..graph import GraphedXbdEvalStep
-    steps = model.__dict__.setdefault('_xbd_eval_steps', {})
-    key = (tuple(batch['img'].shape), float(thr), select, str(batch['img'].device))
+def _device_u8(what, *tensors):
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise _lib.HipLibraryError("dahitra_amd xBD %s runs on MI355X only (no CPU fallback)" % what)
+
+
+def _kept_step(owner, slot, key, build, fresh):
+    """the recorded step kept in the dictionary `slot` of the model `owner` under `key` (kept: a graph pins its buffers for the
+    life of the process, so an epoch must not record a new one); `build()` records it when there is none or `fresh(step)` is
+    no longer true"""
+    steps = owner.__dict__.setdefault(slot, {})
     step = steps.get(key)
-    if step is not None and (step._generation != model._arena.generation or step.class_counts is not class_counts):
-        step = None
-    if step is None:
-        step = steps[key] = GraphedXbdEvalStep(model, batch['img'], batch['msk'], batch['lbl_msk'], class_counts, thr, select)
+    if step is None or not fresh(step):
+        step = steps[key] = build()
     return step
+
+
+def _eval_step(model, batch, class_counts, thr, select):
+    """the model's recorded validation step for this batch shape, threshold, selection and device"""
+    from ..graph import GraphedXbdEvalStep
+    imgs = batch['img']
+    return _kept_step(model, '_xbd_eval_steps', (tuple(imgs.shape), float(thr), select, str(imgs.device)),
+                      lambda: GraphedXbdEvalStep(model, imgs, batch['msk'], batch['lbl_msk'], class_counts, thr, select),
+                      lambda step: step._generation == model._arena.generation and step.class_counts is class_counts)
+
+
+def _epoch(what, model, batches, row_shape, accumulator, replay, eager):
+    """The epoch loop of validate and validate_sweep.  The first batch fixes the shape and the device; accumulator(device) gives
+    the int64 class accumulator (kept on the model: a recorded step holds its address), zeroed here; every image gets one int64
+    row of `row_shape` in a device buffer that doubles when it is full.  A batch of the first shape goes through
+    replay(batch, accumulator) -> the batch's rows (None: no graph), any other through eager(logits, msk, lbl, rows, accumulator).
+    ONE host read when the epoch is over; returns (rows [n_images, *row_shape], accumulator) as numpy integers."""
+    model.eval()
+    acc, rows, n, first, dev = None, None, 0, None, None
+    with torch.no_grad():
+        for batch in batches:
+            imgs, msk, lbl = batch['img'], batch['msk'], batch['lbl_msk']
+            _device_u8("validation", imgs)
+            B = imgs.shape[0]
+            if rows is None:
+                dev, first = imgs.device, tuple(imgs.shape)
+                acc = accumulator(dev)
+                acc.zero_()
+                rows = torch.zeros((max(64, B),) + row_shape, dtype=torch.int64, device=dev)
+            if n + B > rows.shape[0]:            # an iterator does not say how long it is: the buffer doubles, on the device
+                rows = torch.cat([rows, torch.zeros((max(rows.shape[0], B),) + row_shape, dtype=torch.int64, device=dev)])
+            if replay is not None and tuple(imgs.shape) == first:
+                rows[n:n + B].copy_(replay(batch, acc), non_blocking=True)
+            else:
+                eager(model(imgs).float(), msk, lbl, rows[n:n + B], acc)
+            n += B
+    if rows is None:
+        raise ValueError("%s: no batches" % what)
+    both = torch.cat([rows[:n].reshape(-1), acc.reshape(-1)]).cpu().numpy()        # the epoch's one read
+    cut = rows[:n].numel()
+    return both[:cut].reshape((n,) + row_shape), both[cut:].reshape(tuple(acc.shape))
 
 
 def validate(model, batches, thr=0.3, select='reference', graph=True, want_counts=False):
@@ -213,39 +257,46 @@ def validate(model, batches, thr=0.3, select='reference', graph=True, want_count
     class_counts as numpy integers)."""
     if select not in ops.XBD_VAL_SELECT:
         raise ValueError("validate: select %r is not one of %s" % (select, sorted(ops.XBD_VAL_SELECT)))
-    model.eval()
-    class_counts = model.__dict__.get('_xbd_val_class_counts')
-    rows, n, first, dev = None, 0, None, None
-    with torch.no_grad():
-        for batch in batches:
-            imgs, msk, lbl = batch['img'], batch['msk'], batch['lbl_msk']
-            if not imgs.is_cuda:
-                raise _lib.HipLibraryError("dahitra_amd xBD validation runs on MI355X only (no CPU fallback)")
-            B = imgs.shape[0]
-            if rows is None:
-                dev, first = imgs.device, tuple(imgs.shape)
-                if class_counts is None or class_counts.device != dev:
-                    class_counts = model.__dict__['_xbd_val_class_counts'] = torch.zeros(4, 3, dtype=torch.int64, device=dev)
-                class_counts.zero_()
-                rows = torch.zeros(max(64, B), 3, dtype=torch.int64, device=dev)
-            if n + B > rows.shape[0]:            # an iterator does not say how long it is: the buffer doubles, on the device
-                rows = torch.cat([rows, torch.zeros(max(rows.shape[0], B), 3, dtype=torch.int64, device=dev)])
-            if graph and tuple(imgs.shape) == first:
-                step = _eval_step(model, batch, class_counts, thr, select)
-                step(imgs, msk, lbl)
-                rows[n:n + B].copy_(step.image_counts, non_blocking=True)
-            else:
-                ops.xbd_val_count(model(imgs).float(), msk, lbl, rows[n:n + B], class_counts, thr, select)
-            n += B
-    if rows is None:
-        raise ValueError("validate: no batches")
-    both = torch.cat([rows[:n].reshape(-1), class_counts.reshape(-1)]).cpu().numpy()        # the epoch's one read
-    image_counts, cc = both[:n * 3].reshape(n, 3), both[n * 3:].reshape(4, 3)
+
+    def accumulator(dev):
+        cc = model.__dict__.get('_xbd_val_class_counts')
+        if cc is None or cc.device != dev:
+            cc = model.__dict__['_xbd_val_class_counts'] = torch.zeros(4, 3, dtype=torch.int64, device=dev)
+        return cc
+
+    def replay(batch, cc):
+        step = _eval_step(model, batch, cc, thr, select)
+        step(batch['img'], batch['msk'], batch['lbl_msk'])
+        return step.image_counts
+    image_counts, cc = _epoch("validate", model, batches, (3,), accumulator, replay if graph else None,
+                              lambda logits, msk, lbl, rows, cc: ops.xbd_val_count(logits, msk, lbl, rows, cc, thr, select))
     sc, parts = val_score(image_counts, cc)
     f1_sc = parts['f1_per_class']
     print("Val Score: {}, Dice: {}, F1: {}, F1_0: {}, F1_1: {}, F1_2: {}, F1_3: {}".format(sc, parts['dice'], parts['f1'], f1_sc[0],
                                                                                           f1_sc[1], f1_sc[2], f1_sc[3]))
     return (sc, parts, image_counts, cc) if want_counts else sc
+
+
+def _keep_best(d, best_score, model, optimizer, path, current_epoch, thr=None):
+    """the second half of evaluate_val (train.py:296-307): when the score `d` beats `best_score` save the snapshot {'epoch':
+    current_epoch + 1, 'state_dict', 'best_score', 'optimizer'} -- and 'thr', where one is given -- to `path`; print the
+    `score: ... score_best: ...` line and return the best score.  A nan score beats nothing."""
+    if d > best_score:
+        folder = os.path.dirname(path)
+        if folder:
+            os.makedirs(folder, exist_ok=True)
+        snapshot = {
+            'epoch': current_epoch + 1,
+            'state_dict': model.state_dict(),
+            'best_score': d,
+            'optimizer': optimizer.state_dict(),
+        }
+        if thr is not None:
+            snapshot['thr'] = thr
+        torch.save(snapshot, path)
+        best_score = d
+    print("score: {}\tscore_best: {}".format(d, best_score))
+    return best_score
 
 
 def evaluate_val(batches, best_score, model, optimizer, path, current_epoch, thr=0.3, select='reference', graph=True):
@@ -255,19 +306,7 @@ def evaluate_val(batches, best_score, model, optimizer, path, current_epoch, thr
     best score."""
     model = model.eval()
     d = validate(model, batches, thr=thr, select=select, graph=graph)
-    if d > best_score:
-        folder = os.path.dirname(path)
-        if folder:
-            os.makedirs(folder, exist_ok=True)
-        torch.save({
-            'epoch': current_epoch + 1,
-            'state_dict': model.state_dict(),
-            'best_score': d,
-            'optimizer': optimizer.state_dict(),
-        }, path)
-        best_score = d
-    print("score: {}\tscore_best: {}".format(d, best_score))
-    return best_score
+    return _keep_best(d, best_score, model, optimizer, path, current_epoch)
 
 
 # ---- threshold sweep: validate for a whole grid of localisation thresholds from ONE pass ---------------------------------
@@ -359,14 +398,10 @@ class XbdSweep:
 def _sweep_step(model, batch, class_hist, thresholds, select):
     """the model's recorded sweep step for this batch shape, grid, selection and device (kept on the model, as _eval_step does)"""
     from ..graph import GraphedXbdSweepStep
-    steps = model.__dict__.setdefault('_xbd_sweep_steps', {})
-    key = (tuple(batch['img'].shape), thresholds.tobytes(), select, str(batch['img'].device))
-    step = steps.get(key)
-    if step is not None and (step._generation != model._arena.generation or step.class_hist is not class_hist):
-        step = None
-    if step is None:
-        step = steps[key] = GraphedXbdSweepStep(model, batch['img'], batch['msk'], batch['lbl_msk'], class_hist, thresholds, select)
-    return step
+    imgs = batch['img']
+    return _kept_step(model, '_xbd_sweep_steps', (tuple(imgs.shape), thresholds.tobytes(), select, str(imgs.device)),
+                      lambda: GraphedXbdSweepStep(model, imgs, batch['msk'], batch['lbl_msk'], class_hist, thresholds, select),
+                      lambda step: step._generation == model._arena.generation and step.class_hist is class_hist)
 
 
 def validate_sweep(model, batches, thresholds, select='reference', graph=True):
@@ -381,36 +416,20 @@ def validate_sweep(model, batches, thresholds, select='reference', graph=True):
         raise ValueError("validate_sweep: select %r is not one of %s" % (select, sorted(ops.XBD_VAL_SELECT)))
     thr = ops.xbd_sweep_thresholds(thresholds, "validate_sweep")
     T = thr.size
-    model.eval()
-    hists = model.__dict__.setdefault('_xbd_sweep_class_hist', {})
-    class_hist, rows, n, first, dev = None, None, 0, None, None
-    with torch.no_grad():
-        for batch in batches:
-            imgs, msk, lbl = batch['img'], batch['msk'], batch['lbl_msk']
-            if not imgs.is_cuda:
-                raise _lib.HipLibraryError("dahitra_amd xBD validation runs on MI355X only (no CPU fallback)")
-            B = imgs.shape[0]
-            if rows is None:
-                dev, first = imgs.device, tuple(imgs.shape)
-                class_hist = hists.get((T, str(dev)))          # one buffer per grid size: a recorded step holds its address
-                if class_hist is None:
-                    class_hist = hists[(T, str(dev))] = torch.zeros(T + 1, 4, 5, dtype=torch.int64, device=dev)
-                class_hist.zero_()
-                rows = torch.zeros(max(64, B), T + 1, 4, 2, dtype=torch.int64, device=dev)
-            if n + B > rows.shape[0]:            # an iterator does not say how long it is: the buffer doubles, on the device
-                rows = torch.cat([rows, torch.zeros(max(rows.shape[0], B), T + 1, 4, 2, dtype=torch.int64, device=dev)])
-            if graph and tuple(imgs.shape) == first:
-                step = _sweep_step(model, batch, class_hist, thr, select)
-                step(imgs, msk, lbl)
-                rows[n:n + B].copy_(step.image_hist, non_blocking=True)
-            else:
-                ops.xbd_val_sweep(model(imgs).float(), msk, lbl, rows[n:n + B], class_hist, thr, select)
-            n += B
-    if rows is None:
-        raise ValueError("validate_sweep: no batches")
-    both = torch.cat([rows[:n].reshape(-1), class_hist.reshape(-1)]).cpu().numpy()        # the epoch's one read
-    cut = n * (T + 1) * 8
-    sweep = XbdSweep(thr, both[:cut].reshape(n, T + 1, 4, 2), both[cut:].reshape(T + 1, 4, 5))
+
+    def accumulator(dev):
+        hists = model.__dict__.setdefault('_xbd_sweep_class_hist', {})
+        class_hist = hists.get((T, str(dev)))          # one buffer per grid size: a recorded step holds its address
+        if class_hist is None:
+            class_hist = hists[(T, str(dev))] = torch.zeros(T + 1, 4, 5, dtype=torch.int64, device=dev)
+        return class_hist
+
+    def replay(batch, class_hist):
+        step = _sweep_step(model, batch, class_hist, thr, select)
+        step(batch['img'], batch['msk'], batch['lbl_msk'])
+        return step.image_hist
+    sweep = XbdSweep(thr, *_epoch("validate_sweep", model, batches, (T + 1, 4, 2), accumulator, replay if graph else None,
+                                  lambda logits, msk, lbl, rows, ch: ops.xbd_val_sweep(logits, msk, lbl, rows, ch, thr, select)))
     for k in range(T):
         sc, parts = sweep.scores[k], sweep.parts(k)
         f1_sc = parts['f1_per_class']
@@ -425,20 +444,7 @@ def evaluate_val_sweep(batches, best_score, model, optimizer, path, current_epoc
     Prints the `score: ... score_best: ...` line and returns the best score."""
     model = model.eval()
     thr, d = validate_sweep(model, batches, thresholds, select=select, graph=graph).best()
-    if d > best_score:
-        folder = os.path.dirname(path)
-        if folder:
-            os.makedirs(folder, exist_ok=True)
-        torch.save({
-            'epoch': current_epoch + 1,
-            'state_dict': model.state_dict(),
-            'best_score': d,
-            'optimizer': optimizer.state_dict(),
-            'thr': thr,
-        }, path)
-        best_score = d
-    print("score: {}\tscore_best: {}".format(d, best_score))
-    return best_score
+    return _keep_best(d, best_score, model, optimizer, path, current_epoch, thr)
 
 
 # ---- prediction (xBD_code/predict_test_cls.py:58-97) --------------------------------------------------------
@@ -455,14 +461,9 @@ def _one_model(model):
 def _predict_step(model, pre_u8, post_u8, order):
     """the model's recorded prediction step for this shape, order and device (kept on the model, as _eval_step does)"""
     from ..graph import GraphedXbdPredictStep
-    steps = model.__dict__.setdefault('_xbd_predict_steps', {})
-    key = (tuple(pre_u8.shape), order, str(pre_u8.device))
-    step = steps.get(key)
-    if step is not None and step._generation != model._arena.generation:
-        step = None
-    if step is None:
-        step = steps[key] = GraphedXbdPredictStep(model, pre_u8, post_u8, order)
-    return step
+    return _kept_step(model, '_xbd_predict_steps', (tuple(pre_u8.shape), order, str(pre_u8.device)),
+                      lambda: GraphedXbdPredictStep(model, pre_u8, post_u8, order),
+                      lambda step: step._generation == model._arena.generation)
 
 
 def predict_tta(model, pre_u8, post_u8, order='bgr', graph=True):
@@ -480,9 +481,7 @@ def predict_tta(model, pre_u8, post_u8, order='bgr', graph=True):
     model = _one_model(model)
     if order not in ops.XBD_TTA_ORDER:
         raise ValueError("predict_tta: order %r is not one of %s" % (order, sorted(ops.XBD_TTA_ORDER)))
-    for t in (pre_u8, post_u8):
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback)")
+    _device_u8("prediction", pre_u8, post_u8)
     model.eval()
     if graph:
         model._ensure_arena(pre_u8.device)          # a rebuilt arena shows here, before a stale step could be chosen
@@ -514,11 +513,18 @@ def predict_dir(model, test_dir, pred_folder, order='bgr', graph=True):
     so that cv2.imread(..., IMREAD_UNCHANGED) returns exactly those arrays: cv2 stores and returns BGR, so the PIL image is built
     from the channel-reversed slice.  PNG compression level 9; the pixel content is the contract, not the byte stream.
     Returns the list of the pre names whose files were written."""
-    from PIL import Image
     model = _one_model(model)
     device = next(model.parameters()).device
     if device.type != 'cuda':
         raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback): move the model to the GPU")
+    return _predict_pairs(lambda pre, post: predict_tta(model, pre, post, order=order, graph=graph), device, test_dir, pred_folder)
+
+
+def _predict_pairs(predict, device, test_dir, pred_folder, skip=None):
+    """the directory loop of predict_dir and predict_dir_ensemble: predict(pre, post) -> [1, H, W, 5] uint8 for every pair of
+    test_dir whose two shapes agree and for which skip(f, img) (if given; it prints its own line) is false, the three files of
+    each written to pred_folder (created).  Returns the list of the pre names whose files were written."""
+    from PIL import Image
     os.makedirs(pred_folder, exist_ok=True)
     written = []
     for f in sorted(os.listdir(test_dir)):
@@ -527,10 +533,10 @@ def predict_dir(model, test_dir, pred_folder, order='bgr', graph=True):
         fn = os.path.join(test_dir, f)
         img = np.array(Image.open(fn).convert('RGB'))
         img2 = np.array(Image.open(fn.replace('_pre_', '_post_')).convert('RGB'))
-        if img.shape != img2.shape:
+        if img.shape != img2.shape or (skip is not None and skip(f, img)):
             continue
         pre, post = (torch.from_numpy(a).to(device).unsqueeze(0) for a in (img, img2))
-        msk = predict_tta(model, pre, post, order=order, graph=graph)[0].cpu().numpy()
+        msk = predict(pre, post)[0].cpu().numpy()
         full, part1, part2 = predict_names(f)
         np.save(os.path.join(pred_folder, full), msk)
         for name, part in ((part1, msk[..., :3]), (part2, msk[..., 2:])):
@@ -552,14 +558,9 @@ def _ensemble_step(models, pre_u8, post_u8, order, views):
     """the recorded step of this list of models, shape, order, views and device, kept on the first model (as _predict_step
     keeps one per model); rebuilt when any net's arena generation moved.  A kept step holds its nets, so their ids stay theirs."""
     from ..graph import GraphedXbdEnsembleStep
-    steps = models[0].__dict__.setdefault('_xbd_ensemble_steps', {})
     key = (tuple(id(m) for m in models), tuple(pre_u8.shape), order, views, str(pre_u8.device))
-    step = steps.get(key)
-    if step is not None and step.stale():
-        step = None
-    if step is None:
-        step = steps[key] = GraphedXbdEnsembleStep(models, pre_u8, post_u8, order, views)
-    return step
+    return _kept_step(models[0], '_xbd_ensemble_steps', key, lambda: GraphedXbdEnsembleStep(models, pre_u8, post_u8, order, views),
+                      lambda step: not step.stale())
 
 
 def predict_ensemble(models, pre_u8, post_u8, order='bgr', views=4, graph=True):
@@ -581,9 +582,7 @@ def predict_ensemble(models, pre_u8, post_u8, order='bgr', views=4, graph=True):
         raise ValueError("predict_ensemble: order %r is not one of %s" % (order, sorted(ops.XBD_TTA_ORDER)))
     if isinstance(views, bool) or views not in ops.XBD_TTA_VIEWS:
         raise ValueError("predict_ensemble: views=%r is not one of %s" % (views, list(ops.XBD_TTA_VIEWS)))
-    for t in (pre_u8, post_u8):
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback)")
+    _device_u8("prediction", pre_u8, post_u8)
     if pre_u8.dim() != 4 or pre_u8.shape != post_u8.shape:
         raise ValueError("predict_ensemble: pre_u8 %s and post_u8 %s are not two [N, H, W, 3] tensors of one shape"
                          % (tuple(pre_u8.shape), tuple(post_u8.shape)))
@@ -607,33 +606,18 @@ def predict_dir_ensemble(models, test_dir, pred_folder, order='bgr', views=4, gr
     pair whose two shapes differ, the same three files per pair under predict_names(f), written the same way.  With views=8 a
     pair whose image is not square cannot be transposed: it is skipped, and a line says so.  Returns the list of the pre names
     whose files were written."""
-    from PIL import Image
     models = _ensemble("predict_dir_ensemble", models)
     device = next(models[0].parameters()).device
     if device.type != 'cuda':
         raise _lib.HipLibraryError("dahitra_amd xBD prediction runs on MI355X only (no CPU fallback): move the models to the GPU")
-    os.makedirs(pred_folder, exist_ok=True)
-    written = []
-    for f in sorted(os.listdir(test_dir)):
-        if '_pre_' not in f:
-            continue
-        fn = os.path.join(test_dir, f)
-        img = np.array(Image.open(fn).convert('RGB'))
-        img2 = np.array(Image.open(fn.replace('_pre_', '_post_')).convert('RGB'))
-        if img.shape != img2.shape:
-            continue
+
+    def not_square(f, img):
         if views == 8 and img.shape[0] != img.shape[1]:
             print("skipping {}: views=8 needs a square image, got {}x{}".format(f, img.shape[0], img.shape[1]))
-            continue
-        pre, post = (torch.from_numpy(a).to(device).unsqueeze(0) for a in (img, img2))
-        msk = predict_ensemble(models, pre, post, order=order, views=views, graph=graph)[0].cpu().numpy()
-        full, part1, part2 = predict_names(f)
-        np.save(os.path.join(pred_folder, full), msk)
-        for name, part in ((part1, msk[..., :3]), (part2, msk[..., 2:])):
-            Image.fromarray(np.ascontiguousarray(part[..., ::-1])).save(os.path.join(pred_folder, name), format='PNG',
-                                                                        compress_level=9)
-        written.append(f)
-    return written
+            return True
+        return False
+    return _predict_pairs(lambda pre, post: predict_ensemble(models, pre, post, order=order, views=views, graph=graph), device,
+                          test_dir, pred_folder, skip=not_square)
 
 
 def load_snapshot(model, path):
@@ -664,8 +648,7 @@ def damage_map(msk_u8, loc=None):
     p = msk_u8[..., 0] / 255 and sets the dropped pixels to 0 (ops.xbd_damage_map; ops.XBD_LOC_THR is the script's _thr).  The
     script reads p from a separate localisation net, which is not built here; channel 0 of the same prediction, the channel
     validate thresholds, stands in for it."""
-    if not (torch.is_tensor(msk_u8) and msk_u8.is_cuda):
-        raise _lib.HipLibraryError("dahitra_amd xBD damage map runs on MI355X only (no CPU fallback)")
+    _device_u8("damage map", msk_u8)
     return ops.xbd_damage_map(msk_u8, loc)
 
 
@@ -684,10 +667,8 @@ def visual_grid(model, pre_u8, post_u8, gt_u8, order='bgr', loc=None, graph=True
     array is BGR (cv2): this one with the last axis reversed.  Returns a new device tensor.  A label above 4 raises KeyError, as
     the script's colour table does; CPU tensors are refused.  H and W are what the net takes: multiples of 64 (the decoder
     attention batches the 1/16-scale map of each image in rows of 16; ops.linear asserts on anything else)."""
-    for t in (pre_u8, post_u8, gt_u8):
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise _lib.HipLibraryError("dahitra_amd xBD visual grid runs on MI355X only (no CPU fallback)")
-    ops.xbd_loc_bounds(loc)                                  # a bad threshold shows before the forward runs
+    _device_u8("visual grid", pre_u8, post_u8, gt_u8)
+    ops.xbd_loc_bounds(loc)                                 # a bad threshold shows before the forward runs
     _check_labels(gt_u8)
     msk = predict_tta(model, pre_u8, post_u8, order=order, graph=graph)
     return ops.xbd_vis_grid(pre_u8, post_u8, gt_u8, msk, loc)
@@ -742,12 +723,6 @@ def visualize_dir(model, test_dir, mask_dir, out_dir, model_str='TUNet', crop=51
 
 
 # ---- buildings: components, votes and the building-level score (no counterpart in the reference; csrc/xbd_buildings.hip) -----
-def _device_u8(what, *tensors):
-    for t in tensors:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise _lib.HipLibraryError("dahitra_amd xBD %s runs on MI355X only (no CPU fallback)" % what)
-
-
 def buildings(key_u8, connectivity=8, keyed=False):
     """Connected components of a class map on the device: key_u8 [N, H, W] uint8 -> (labels [N, H, W] int32, count [N] int32).
     Neighbouring pixels (connectivity 4 or 8) form one building when both are nonzero, with keyed=True when they are nonzero and

@@ -2032,19 +2032,106 @@ def xbd_val_sweep(logits, msk, lbl, image_hist, class_hist, thresholds, select="
           T, XBD_VAL_SELECT[select], P(image_hist), P(class_hist), S())
 
 
+# ---- arguments, outputs and workspaces of the evaluation wrappers below --------------------------------------
+class _Args:
+    """The argument checker of the evaluation wrappers from here to cd_view_counts: ValueError, before any launch, for whatever
+    the kernel cannot read as it lies.  tensor() refuses at once an argument whose type, dtype or shape does not fit,
+        "<fn>: <name> <shape> <dtype> is not <dtype> <text>",
+    and placed(), called when all of them fit, checks device and storage -- so a wrong shape shows whatever device the tensors
+    are on.  Two placement policies: a tensor that is not on the first one's GPU is a ValueError (the xBD wrappers); with
+    cpu_error=True tensors that are ALL on the CPU are a HipLibraryError (there is no CPU path) and only mixed devices a
+    ValueError (cd_eval_vis, cd_tile_stitch, cd_view_counts)."""
+
+    def __init__(self, what, cpu_error=False):
+        self.what, self.cpu_error, self.checked = what, cpu_error, []
+
+    def tensor(self, name, t, dtype, fits, text=None):
+        """fits: the shape, or a predicate on the tensor; text: how the message describes it (default: the shape).  Returns t"""
+        if not torch.is_tensor(t) or t.dtype != dtype or not (fits(t) if callable(fits) else tuple(t.shape) == tuple(fits)):
+            raise ValueError("%s: %s %s %s is not %s %s" % (self.what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
+                                                            str(dtype).replace("torch.", ""), str(list(fits)) if text is None else text))
+        self.checked.append((name, t))
+        return t
+
+    def image(self, name, t, dtype):
+        """a non-empty [N, H, W] map: returns (N, H, W)"""
+        return tuple(self.tensor(name, t, dtype, lambda t: t.dim() == 3 and t.numel() > 0, "[N, H, W], not empty").shape)
+
+    def out(self, t, dtype, shape, name="out", text=None):
+        """an output buffer: the given one, checked like any argument, or a fresh tensor beside the first argument"""
+        if t is None:
+            return torch.empty(tuple(shape), dtype=dtype, device=self.checked[0][1].device)
+        return self.tensor(name, t, dtype, shape, text)
+
+    def workspace(self, ws):
+        """a caller's workspace, if one is given: uint8 of any shape (_workspace checks its size once the need is known)"""
+        if ws is not None:
+            self.tensor("ws", ws, torch.uint8, lambda t: True, "workspace")
+
+    def placed(self):
+        first_name, first = self.checked[0]
+        if self.cpu_error and not any(t.is_cuda for _, t in self.checked):
+            raise _lib.HipLibraryError("dahitra_amd %s runs on MI355X only (no CPU fallback): its tensors are on the CPU" % self.what)
+        for name, t in self.checked:
+            if not t.is_cuda or t.device != first.device:
+                if self.cpu_error:
+                    raise ValueError("%s: %s is on %s and %s on %s; the kernel takes all its tensors on one GPU"
+                                     % (self.what, name, t.device, first_name, first.device))
+                raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device"
+                                 % (self.what, name, t.device))
+            if not t.is_contiguous():
+                raise ValueError("%s: %s is not contiguous (strides %s)" % (self.what, name, t.stride()))
+
+
+def _ws_bytes(entry, *dims):
+    """what the library's size query `entry` answers for `dims`: the bytes of a kernel's workspace"""
+    n = ctypes.c_long(0)
+    if getattr(_lib.lib(), entry)(*dims, ctypes.byref(n)) != 0:
+        raise ValueError(_lib.lib().dh_last_error().decode())
+    return int(n.value)
+
+
+def _workspace(what, ws, need, device):
+    """the caller's workspace (an _Args-checked uint8 buffer) if it holds `need` 4-byte aligned bytes, or a fresh one"""
+    if ws is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if ws.numel() < need or ws.data_ptr() % 4:
+        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
+    return ws
+
+
 # ---- xBD prediction: 4-flip test-time augmentation (csrc/xbd_predict.hip) ---------------------------------
 XBD_TTA_ORDER = {"rgb": 0, "bgr": 1}
 
 
-def _tta_tensor(what, name, t, dtype, shape_text, ok, device=None):
-    """one argument of the two calls below: ValueError, before any launch, for whatever the kernel cannot read as it lies"""
-    if not torch.is_tensor(t) or t.dtype != dtype or not ok(t):
-        raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
-                                                        str(dtype).replace("torch.", ""), shape_text))
-    if not t.is_cuda or (device is not None and t.device != device):
-        raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device" % (what, name, t.device))
-    if not t.is_contiguous():
-        raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
+def _tta_pack_args(what, pre_u8, post_u8, order, views, out):
+    """the arguments of xbd_tta_pack (views None: its four flips) and xbd_tta_pack_views: returns N, H, W, V and `out`"""
+    if order not in XBD_TTA_ORDER:
+        raise ValueError("%s: order %r is not one of %s" % (what, order, sorted(XBD_TTA_ORDER)))
+    a = _Args(what)
+    N, H, W, _ = a.tensor("pre_u8", pre_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[3] == 3, "[N, H, W, 3]").shape
+    V = 4 if views is None else _tta_views(what, views, H, W)
+    a.tensor("post_u8", post_u8, torch.uint8, (N, H, W, 3), "[%d, %d, %d, 3] like pre_u8" % (N, H, W))
+    out = a.out(out, torch.float32, (V * N, 6, H, W))
+    a.placed()
+    return N, H, W, V, out
+
+
+def _tta_merge_args(what, named, views, out):
+    """the arguments of xbd_tta_merge (views None: four flips) and xbd_tta_merge_multi; named: (name, logits) of every model.
+    Returns N, H, W, V and `out`"""
+    a = _Args(what)
+    first = a.tensor(named[0][0], named[0][1], torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 5,
+                     "[%s, 5, H, W]" % ("4N" if views is None else "views N"))
+    B, _, H, W = first.shape
+    V = 4 if views is None else _tta_views(what, views, H, W)
+    if B % V:
+        raise ValueError("%s: a batch of %d logits is not %s per image" % (what, B, "four flips" if views is None else "%d views" % V))
+    for name, t in named[1:]:
+        a.tensor(name, t, torch.float32, first.shape, "%s like %s" % (list(first.shape), named[0][0]))
+    out = a.out(out, torch.uint8, (B // V, H, W, 5))
+    a.placed()
+    return B // V, H, W, V, out
 
 
 def xbd_tta_pack(pre_u8, post_u8, order="bgr", out=None):
@@ -2055,17 +2142,7 @@ def xbd_tta_pack(pre_u8, post_u8, order="bgr", out=None):
     returns BGR while these sources hold RGB; 'rgb' keeps them, the order train.py's PIL loader and this project's loader feed
     the net.  out: a [4N, 6, H, W] float32 buffer to write into.  ValueError, before any launch, for a wrong rank, dtype or
     device, non-contiguous storage or an unknown order."""
-    if order not in XBD_TTA_ORDER:
-        raise ValueError("xbd_tta_pack: order %r is not one of %s" % (order, sorted(XBD_TTA_ORDER)))
-    _tta_tensor("xbd_tta_pack", "pre_u8", pre_u8, torch.uint8, "[N, H, W, 3]", lambda t: t.dim() == 4 and t.shape[3] == 3)
-    N, H, W, _ = pre_u8.shape
-    _tta_tensor("xbd_tta_pack", "post_u8", post_u8, torch.uint8, "[%d, %d, %d, 3] like pre_u8" % (N, H, W),
-                lambda t: t.shape == pre_u8.shape, pre_u8.device)
-    if out is None:
-        out = torch.empty(4 * N, 6, H, W, dtype=torch.float32, device=pre_u8.device)
-    else:
-        _tta_tensor("xbd_tta_pack", "out", out, torch.float32, "[%d, 6, %d, %d]" % (4 * N, H, W),
-                    lambda t: tuple(t.shape) == (4 * N, 6, H, W), pre_u8.device)
+    N, H, W, _, out = _tta_pack_args("xbd_tta_pack", pre_u8, post_u8, order, None, out)
     _call("dh_xbd_tta_pack_u8", _vp(pre_u8.data_ptr()), _vp(post_u8.data_ptr()), N, H, W, XBD_TTA_ORDER[order],
           _vp(out.data_ptr()), S())
     return out
@@ -2077,16 +2154,7 @@ def xbd_tta_merge(logits, out=None):
     (((u_0 + u_1) + u_2) + u_3) / 4 in float32 in that order (numpy's mean over the stack), uint8(trunc(mean * 255)).  A NaN
     logit gives 0.  out: a [N, H, W, 5] uint8 buffer to write into.  ValueError, before any launch, for a wrong rank, dtype or
     device, non-contiguous storage or a batch that is no multiple of 4."""
-    _tta_tensor("xbd_tta_merge", "logits", logits, torch.float32, "[4N, 5, H, W]", lambda t: t.dim() == 4 and t.shape[1] == 5)
-    B, _, H, W = logits.shape
-    if B % 4:
-        raise ValueError("xbd_tta_merge: a batch of %d logits is not four flips per image" % B)
-    N = B // 4
-    if out is None:
-        out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=logits.device)
-    else:
-        _tta_tensor("xbd_tta_merge", "out", out, torch.uint8, "[%d, %d, %d, 5]" % (N, H, W),
-                    lambda t: tuple(t.shape) == (N, H, W, 5), logits.device)
+    N, H, W, _, out = _tta_merge_args("xbd_tta_merge", [("logits", logits)], None, out)
     _call("dh_xbd_tta_merge_u8", _vp(logits.data_ptr()), N, H, W, _vp(out.data_ptr()), S())
     return out
 
@@ -2111,19 +2179,7 @@ def xbd_tta_pack_views(pre_u8, post_u8, order="bgr", views=4, out=None):
     square: identity, the two flips, rot180, transpose, anti-transpose and both rot90.  views=8 needs H == W.  order and out as
     in xbd_tta_pack.  ValueError, before any launch, for a wrong rank, dtype or device, non-contiguous storage, an unknown
     order, views outside {4, 8} or views=8 on an image that is not square."""
-    what = "xbd_tta_pack_views"
-    if order not in XBD_TTA_ORDER:
-        raise ValueError("%s: order %r is not one of %s" % (what, order, sorted(XBD_TTA_ORDER)))
-    _tta_tensor(what, "pre_u8", pre_u8, torch.uint8, "[N, H, W, 3]", lambda t: t.dim() == 4 and t.shape[3] == 3)
-    N, H, W, _ = pre_u8.shape
-    V = _tta_views(what, views, H, W)
-    _tta_tensor(what, "post_u8", post_u8, torch.uint8, "[%d, %d, %d, 3] like pre_u8" % (N, H, W),
-                lambda t: t.shape == pre_u8.shape, pre_u8.device)
-    if out is None:
-        out = torch.empty(V * N, 6, H, W, dtype=torch.float32, device=pre_u8.device)
-    else:
-        _tta_tensor(what, "out", out, torch.float32, "[%d, 6, %d, %d]" % (V * N, H, W),
-                    lambda t: tuple(t.shape) == (V * N, 6, H, W), pre_u8.device)
+    N, H, W, V, out = _tta_pack_args("xbd_tta_pack_views", pre_u8, post_u8, order, views, out)
     _call("dh_xbd_tta_pack_views_u8", _vp(pre_u8.data_ptr()), _vp(post_u8.data_ptr()), N, H, W, XBD_TTA_ORDER[order], V,
           _vp(out.data_ptr()), S())
     return out
@@ -2141,21 +2197,7 @@ def xbd_tta_merge_multi(logits_list, views=4, out=None):
     if not isinstance(logits_list, (list, tuple)) or not 1 <= len(logits_list) <= XBD_TTA_MAX_MODELS:
         raise ValueError("%s: logits_list is not a list of 1 .. %d tensors (%s)" % (
             what, XBD_TTA_MAX_MODELS, len(logits_list) if isinstance(logits_list, (list, tuple)) else type(logits_list)))
-    first = logits_list[0]
-    _tta_tensor(what, "logits_list[0]", first, torch.float32, "[views N, 5, H, W]", lambda t: t.dim() == 4 and t.shape[1] == 5)
-    B, _, H, W = first.shape
-    V = _tta_views(what, views, H, W)
-    if B % V:
-        raise ValueError("%s: a batch of %d logits is not %d views per image" % (what, B, V))
-    N = B // V
-    for m, t in enumerate(logits_list[1:], 1):
-        _tta_tensor(what, "logits_list[%d]" % m, t, torch.float32, "%s like logits_list[0]" % list(first.shape),
-                    lambda t: t.shape == first.shape, first.device)
-    if out is None:
-        out = torch.empty(N, H, W, 5, dtype=torch.uint8, device=first.device)
-    else:
-        _tta_tensor(what, "out", out, torch.uint8, "[%d, %d, %d, 5]" % (N, H, W),
-                    lambda t: tuple(t.shape) == (N, H, W, 5), first.device)
+    N, H, W, V, out = _tta_merge_args(what, [("logits_list[%d]" % m, t) for m, t in enumerate(logits_list)], views, out)
     table = (ctypes.c_void_p * len(logits_list))(*[t.data_ptr() for t in logits_list])      # read by the entry, not the kernel
     _call("dh_xbd_tta_merge_multi_u8", ctypes.cast(table, ctypes.c_void_p), len(logits_list), V, N, H, W, _vp(out.data_ptr()), S())
     return out
@@ -2191,33 +2233,6 @@ def xbd_loc_bounds(loc):
     return (1,) + tuple(bisect.bisect_right(_XBD_BYTE_P, t) for t in thr)
 
 
-def _vis_tensors(what, msk_u8, others, out, out_shape):
-    """the arguments of the two calls below: ValueError, before any launch.  Rank, dtype and agreement of the shapes are
-    checked on every argument first, then device and storage, so a wrong shape shows whatever device the tensors are on.
-    others: (name, tensor, trailing dims after [N, H, W]); out_shape: N, H, W -> the shape of `out`.  Returns N, H, W"""
-    def typed(name, t, text, ok):
-        if not torch.is_tensor(t) or t.dtype != torch.uint8 or not ok(t):
-            raise ValueError("%s: %s %s %s is not uint8 %s" % (what, name, tuple(getattr(t, "shape", ())),
-                                                               getattr(t, "dtype", type(t)), text))
-    typed("msk_u8", msk_u8, "[N, H, W, 5]", lambda t: t.dim() == 4 and t.shape[3] == 5)
-    N, H, W = msk_u8.shape[:3]
-    checked = [("msk_u8", msk_u8)]
-    for name, t, tail in others:
-        want = (N, H, W) + tail
-        typed(name, t, "%s like msk_u8" % list(want), lambda t: tuple(t.shape) == want)
-        checked.append((name, t))
-    if out is not None:
-        want = out_shape(N, H, W)
-        typed("out", out, str(list(want)), lambda t: tuple(t.shape) == want)
-        checked.append(("out", out))
-    for name, t in checked:
-        if not t.is_cuda or t.device != msk_u8.device:
-            raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device" % (what, name, t.device))
-        if not t.is_contiguous():
-            raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
-    return N, H, W
-
-
 def xbd_damage_map(msk_u8, loc=None, out=None):
     """The damage class of visualize_results.py:206-211 per pixel, on the device.  msk_u8 [N, H, W, 5] uint8, channels last
     (what xbd_tta_merge returns) -> [N, H, W] uint8: 1 + the index of the first maximum of channels 1 .. 4, the script's
@@ -2229,9 +2244,10 @@ def xbd_damage_map(msk_u8, loc=None, out=None):
     here it is channel 0 of the same prediction.  out: a [N, H, W] uint8 buffer to write into.  ValueError, before any launch,
     for a wrong rank, dtype or device, non-contiguous storage or a non-finite threshold."""
     use, b0, b1, b2 = xbd_loc_bounds(loc)
-    N, H, W = _vis_tensors("xbd_damage_map", msk_u8, (), out, lambda N, H, W: (N, H, W))
-    if out is None:
-        out = torch.empty(N, H, W, dtype=torch.uint8, device=msk_u8.device)
+    a = _Args("xbd_damage_map")
+    N, H, W = a.tensor("msk_u8", msk_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[3] == 5, "[N, H, W, 5]").shape[:3]
+    out = a.out(out, torch.uint8, (N, H, W))
+    a.placed()
     _call("dh_xbd_damage_map_u8", _vp(msk_u8.data_ptr()), N, H, W, use, b0, b1, b2, _vp(out.data_ptr()), S())
     return out
 
@@ -2246,10 +2262,12 @@ def xbd_vis_grid(pre_u8, post_u8, gt_u8, msk_u8, loc=None, out=None):
     raises.  out: a [N, H, 4W, 3] uint8 buffer to write into.  ValueError, before any launch, for a wrong rank, dtype or device,
     non-contiguous storage, shapes that do not agree or a non-finite threshold."""
     use, b0, b1, b2 = xbd_loc_bounds(loc)
-    N, H, W = _vis_tensors("xbd_vis_grid", msk_u8, (("pre_u8", pre_u8, (3,)), ("post_u8", post_u8, (3,)), ("gt_u8", gt_u8, ())),
-                           out, lambda N, H, W: (N, H, 4 * W, 3))
-    if out is None:
-        out = torch.empty(N, H, 4 * W, 3, dtype=torch.uint8, device=msk_u8.device)
+    a = _Args("xbd_vis_grid")
+    N, H, W = a.tensor("msk_u8", msk_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[3] == 5, "[N, H, W, 5]").shape[:3]
+    for name, t, tail in (("pre_u8", pre_u8, (3,)), ("post_u8", post_u8, (3,)), ("gt_u8", gt_u8, ())):
+        a.tensor(name, t, torch.uint8, (N, H, W) + tail, "%s like msk_u8" % list((N, H, W) + tail))
+    out = a.out(out, torch.uint8, (N, H, 4 * W, 3))
+    a.placed()
     _call("dh_xbd_vis_grid_u8", _vp(pre_u8.data_ptr()), _vp(post_u8.data_ptr()), _vp(gt_u8.data_ptr()), _vp(msk_u8.data_ptr()),
           N, H, W, use, b0, b1, b2, _vp(out.data_ptr()), S())
     return out
@@ -2261,26 +2279,8 @@ XBD_CC_COLS = 10                 # area, h0 .. h4, y0, x0, y1, x1
 XBD_CC_MODES = {"damage": 0, "all": 1}
 
 
-def _cc_tensors(what, named, device=None):
-    """named: (name, tensor, dtype, shape or None, text).  Rank, dtype and shape of every argument first, then device and
-    storage: ValueError, before any launch."""
-    for name, t, dtype, shape, text in named:
-        if not torch.is_tensor(t) or t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
-            raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
-                                                            str(dtype).replace("torch.", ""), text))
-    device = named[0][1].device if device is None else device
-    for name, t, _, _, _ in named:
-        if not t.is_cuda or t.device != device:
-            raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device" % (what, name, t.device))
-        if not t.is_contiguous():
-            raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
-
-
 def _cc_image(what, name, t, dtype):
-    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 3 or t.numel() == 0:
-        raise ValueError("%s: %s %s %s is not a non-empty %s [N, H, W]" % (what, name, tuple(getattr(t, "shape", ())),
-                                                                          getattr(t, "dtype", type(t)), str(dtype).replace("torch.", "")))
-    return tuple(t.shape)
+    return _Args(what).image(name, t, dtype)
 
 
 def _cc_cap(what, cap):
@@ -2288,12 +2288,18 @@ def _cc_cap(what, cap):
         raise ValueError("%s: cap %r is not an integer >= 1" % (what, cap))
 
 
+def _out_pair(what, out, names):
+    """`out` of a call that returns two tensors: the pair given, or (None, None)"""
+    if out is None:
+        return None, None
+    if not (isinstance(out, (tuple, list)) and len(out) == 2):
+        raise ValueError("%s: out is a pair (%s)" % (what, names))
+    return out
+
+
 def xbd_cc_ws_bytes(N, H, W):
     """bytes of the workspace xbd_cc_label needs for [N, H, W]: parents int32 [N, H W] + block counts [N, ceil(H W / 1024)]"""
-    n = ctypes.c_long(0)
-    if _lib.lib().dh_xbd_cc_ws_bytes(N, H, W, ctypes.byref(n)) != 0:
-        raise ValueError(_lib.lib().dh_last_error().decode())
-    return int(n.value)
+    return _ws_bytes("dh_xbd_cc_ws_bytes", N, H, W)
 
 
 def xbd_cc_label(key_u8, connectivity=8, keyed=False, out=None, ws=None):
@@ -2307,22 +2313,14 @@ def xbd_cc_label(key_u8, connectivity=8, keyed=False, out=None, ws=None):
     what = "xbd_cc_label"
     if connectivity not in (4, 8):
         raise ValueError("%s: connectivity %r is neither 4 nor 8" % (what, connectivity))
-    N, H, W = _cc_image(what, "key_u8", key_u8, torch.uint8)
-    named = [("key_u8", key_u8, torch.uint8, None, "[N, H, W]")]
-    if out is not None:
-        if not (isinstance(out, (tuple, list)) and len(out) == 2):
-            raise ValueError("%s: out is a pair (labels, count)" % what)
-        named += [("out[0]", out[0], torch.int32, (N, H, W), "labels %s" % [N, H, W]), ("out[1]", out[1], torch.int32, (N,), "count %s" % [N])]
-    if ws is not None:
-        named.append(("ws", ws, torch.uint8, None, "workspace"))
-    _cc_tensors(what, named)
-    need = xbd_cc_ws_bytes(N, H, W)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=key_u8.device)
-    elif ws.numel() < need or ws.data_ptr() % 4:
-        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
-    labels, count = out if out is not None else (torch.empty(N, H, W, dtype=torch.int32, device=key_u8.device),
-                                                 torch.empty(N, dtype=torch.int32, device=key_u8.device))
+    a = _Args(what)
+    N, H, W = a.image("key_u8", key_u8, torch.uint8)
+    labels, count = _out_pair(what, out, "labels, count")
+    labels = a.out(labels, torch.int32, (N, H, W), "out[0]", "labels %s" % [N, H, W])
+    count = a.out(count, torch.int32, (N,), "out[1]", "count %s" % [N])
+    a.workspace(ws)
+    a.placed()
+    ws = _workspace(what, ws, xbd_cc_ws_bytes(N, H, W), key_u8.device)
     _call("dh_xbd_cc_label", _vp(key_u8.data_ptr()), N, H, W, connectivity, int(bool(keyed)), _vp(labels.data_ptr()),
           _vp(count.data_ptr()), _vp(ws.data_ptr()), ws.numel(), S())
     return labels, count
@@ -2335,13 +2333,11 @@ def xbd_cc_stats(labels, vote_u8, cap, out=None):
     above cap are ignored.  Every int of the table is written.  out: a [N, cap, 10] int32 buffer to write into."""
     what = "xbd_cc_stats"
     _cc_cap(what, cap)
-    N, H, W = _cc_image(what, "labels", labels, torch.int32)
-    named = [("labels", labels, torch.int32, None, "[N, H, W]"), ("vote_u8", vote_u8, torch.uint8, (N, H, W), "%s like labels" % [N, H, W])]
-    if out is not None:
-        named.append(("out", out, torch.int32, (N, cap, XBD_CC_COLS), str([N, cap, XBD_CC_COLS])))
-    _cc_tensors(what, named)
-    if out is None:
-        out = torch.empty(N, cap, XBD_CC_COLS, dtype=torch.int32, device=labels.device)
+    a = _Args(what)
+    N, H, W = a.image("labels", labels, torch.int32)
+    a.tensor("vote_u8", vote_u8, torch.uint8, (N, H, W), "%s like labels" % [N, H, W])
+    out = a.out(out, torch.int32, (N, cap, XBD_CC_COLS))
+    a.placed()
     _call("dh_xbd_cc_stats", _vp(labels.data_ptr()), _vp(vote_u8.data_ptr()), N, H, W, cap, _vp(out.data_ptr()), S())
     return out
 
@@ -2355,16 +2351,12 @@ def xbd_cc_vote(table, min_area=0, mode="damage", out=None):
         raise ValueError("%s: mode %r is neither 'damage' nor 'all'" % (what, mode))
     if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 0:
         raise ValueError("%s: min_area %r is not an integer >= 0" % (what, min_area))
-    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 3 or table.shape[2] != XBD_CC_COLS or table.numel() == 0:
-        raise ValueError("%s: table %s %s is not a non-empty int32 [N, cap, %d]" % (what, tuple(getattr(table, "shape", ())),
-                                                                                   getattr(table, "dtype", type(table)), XBD_CC_COLS))
+    a = _Args(what)
+    a.tensor("table", table, torch.int32, lambda t: t.dim() == 3 and t.shape[2] == XBD_CC_COLS and t.numel() > 0,
+             "[N, cap, %d], not empty" % XBD_CC_COLS)
     N, cap = table.shape[:2]
-    named = [("table", table, torch.int32, None, "")]
-    if out is not None:
-        named.append(("out", out, torch.uint8, (N, cap), str([N, cap])))
-    _cc_tensors(what, named)
-    if out is None:
-        out = torch.empty(N, cap, dtype=torch.uint8, device=table.device)
+    out = a.out(out, torch.uint8, (N, cap))
+    a.placed()
     _call("dh_xbd_cc_vote", _vp(table.data_ptr()), N, cap, min_area, XBD_CC_MODES[mode], _vp(out.data_ptr()), S())
     return out
 
@@ -2373,16 +2365,11 @@ def xbd_cc_paint(labels, cls_u8, out=None):
     """The one-class-per-component map: labels [N, H, W] int32, cls_u8 [N, cap] uint8 -> [N, H, W] uint8, cls_u8[n, l - 1] for a
     pixel with label l, 0 for l = 0 or l > cap.  Every byte is written.  out: a [N, H, W] uint8 buffer to write into."""
     what = "xbd_cc_paint"
-    N, H, W = _cc_image(what, "labels", labels, torch.int32)
-    if not torch.is_tensor(cls_u8) or cls_u8.dtype != torch.uint8 or cls_u8.dim() != 2 or cls_u8.shape[0] != N or cls_u8.shape[1] < 1:
-        raise ValueError("%s: cls_u8 %s %s is not uint8 [%d, cap >= 1]" % (what, tuple(getattr(cls_u8, "shape", ())),
-                                                                          getattr(cls_u8, "dtype", type(cls_u8)), N))
-    named = [("labels", labels, torch.int32, None, ""), ("cls_u8", cls_u8, torch.uint8, None, "")]
-    if out is not None:
-        named.append(("out", out, torch.uint8, (N, H, W), str([N, H, W])))
-    _cc_tensors(what, named)
-    if out is None:
-        out = torch.empty(N, H, W, dtype=torch.uint8, device=labels.device)
+    a = _Args(what)
+    N, H, W = a.image("labels", labels, torch.int32)
+    a.tensor("cls_u8", cls_u8, torch.uint8, lambda t: t.dim() == 2 and t.shape[0] == N and t.shape[1] >= 1, "[%d, cap >= 1]" % N)
+    out = a.out(out, torch.uint8, (N, H, W))
+    a.placed()
     _call("dh_xbd_cc_paint", _vp(labels.data_ptr()), _vp(cls_u8.data_ptr()), N, H, W, cls_u8.shape[1], _vp(out.data_ptr()), S())
     return out
 
@@ -2404,10 +2391,7 @@ def _cc_iou(what, iou):
 def xbd_cc_match_ws_bytes(N, cap_a, cap_b):
     """bytes of the workspace xbd_cc_match needs: int32 rows [N, cap_a, NB + 1] with NB = cap_b.bit_length(), the areas of B
     [N, cap_b], candidates and intersections [N, cap_a] each"""
-    n = ctypes.c_long(0)
-    if _lib.lib().dh_xbd_cc_match_ws_bytes(N, cap_a, cap_b, ctypes.byref(n)) != 0:
-        raise ValueError(_lib.lib().dh_last_error().decode())
-    return int(n.value)
+    return _ws_bytes("dh_xbd_cc_match_ws_bytes", N, cap_a, cap_b)
 
 
 def xbd_cc_match(labels_a, labels_b, cap_a, cap_b, iou=(1, 2), out=None, ws=None):
@@ -2425,24 +2409,15 @@ def xbd_cc_match(labels_a, labels_b, cap_a, cap_b, iou=(1, 2), out=None, ws=None
     _cc_cap(what, cap_a)
     _cc_cap(what, cap_b)
     num, den = _cc_iou(what, iou)
-    N, H, W = _cc_image(what, "labels_a", labels_a, torch.int32)
-    named = [("labels_a", labels_a, torch.int32, None, "[N, H, W]"),
-             ("labels_b", labels_b, torch.int32, (N, H, W), "%s like labels_a" % [N, H, W])]
-    if out is not None:
-        if not (isinstance(out, (tuple, list)) and len(out) == 2):
-            raise ValueError("%s: out is a pair (match_a, match_b)" % what)
-        named += [("out[0]", out[0], torch.int32, (N, cap_a, XBD_CC_MATCH_COLS), "match_a %s" % [N, cap_a, XBD_CC_MATCH_COLS]),
-                  ("out[1]", out[1], torch.int32, (N, cap_b), "match_b %s" % [N, cap_b])]
-    if ws is not None:
-        named.append(("ws", ws, torch.uint8, None, "workspace"))
-    _cc_tensors(what, named)
-    need = xbd_cc_match_ws_bytes(N, cap_a, cap_b)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=labels_a.device)
-    elif ws.numel() < need or ws.data_ptr() % 4:
-        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
-    match_a, match_b = out if out is not None else (torch.empty(N, cap_a, XBD_CC_MATCH_COLS, dtype=torch.int32, device=labels_a.device),
-                                                    torch.empty(N, cap_b, dtype=torch.int32, device=labels_a.device))
+    a = _Args(what)
+    N, H, W = a.image("labels_a", labels_a, torch.int32)
+    a.tensor("labels_b", labels_b, torch.int32, (N, H, W), "%s like labels_a" % [N, H, W])
+    match_a, match_b = _out_pair(what, out, "match_a, match_b")
+    match_a = a.out(match_a, torch.int32, (N, cap_a, XBD_CC_MATCH_COLS), "out[0]", "match_a %s" % [N, cap_a, XBD_CC_MATCH_COLS])
+    match_b = a.out(match_b, torch.int32, (N, cap_b), "out[1]", "match_b %s" % [N, cap_b])
+    a.workspace(ws)
+    a.placed()
+    ws = _workspace(what, ws, xbd_cc_match_ws_bytes(N, cap_a, cap_b), labels_a.device)
     _call("dh_xbd_cc_match", _vp(labels_a.data_ptr()), _vp(labels_b.data_ptr()), N, H, W, cap_a, cap_b, num, den,
           _vp(match_a.data_ptr()), _vp(match_b.data_ptr()), _vp(ws.data_ptr()), ws.numel(), S())
     return match_a, match_b
@@ -2479,14 +2454,11 @@ def xbd_morph(map_u8, op, k, out=None):
     if not isinstance(op, str) or op not in XBD_MORPH_OPS:
         raise ValueError("%s: op %r is neither 'dilate' nor 'erode'" % (what, op))
     _morph_k(what, k)
-    N, H, W = _cc_image(what, "map_u8", map_u8, torch.uint8)
-    named = [("map_u8", map_u8, torch.uint8, None, "[N, H, W]")]
-    if out is not None:
-        named.append(("out", out, torch.uint8, (N, H, W), str([N, H, W])))
-    _cc_tensors(what, named)
+    a = _Args(what)
+    N, H, W = a.image("map_u8", map_u8, torch.uint8)
+    out = a.out(out, torch.uint8, (N, H, W))
+    a.placed()
     _morph_apart(what, "map_u8", map_u8, out)
-    if out is None:
-        out = torch.empty(N, H, W, dtype=torch.uint8, device=map_u8.device)
     _call("dh_xbd_morph_u8", _vp(map_u8.data_ptr()), N, H, W, k, XBD_MORPH_OPS[op], _vp(out.data_ptr()), S())
     return out
 
@@ -2500,17 +2472,12 @@ def xbd_msk_dilate(msk_u8, k=5, out=None):
     ValueError, before any launch, as xbd_morph."""
     what = "xbd_msk_dilate"
     _morph_k(what, k)
-    if not torch.is_tensor(msk_u8) or msk_u8.dtype != torch.uint8 or msk_u8.dim() != 4 or msk_u8.shape[1] != 5 or msk_u8.numel() == 0:
-        raise ValueError("%s: msk_u8 %s %s is not a non-empty uint8 [N, 5, H, W]" % (what, tuple(getattr(msk_u8, "shape", ())),
-                                                                                    getattr(msk_u8, "dtype", type(msk_u8))))
+    a = _Args(what)
+    a.tensor("msk_u8", msk_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[1] == 5 and t.numel() > 0, "[N, 5, H, W], not empty")
     N, _, H, W = msk_u8.shape
-    named = [("msk_u8", msk_u8, torch.uint8, None, "[N, 5, H, W]")]
-    if out is not None:
-        named.append(("out", out, torch.uint8, (N, 5, H, W), str([N, 5, H, W])))
-    _cc_tensors(what, named)
+    out = a.out(out, torch.uint8, (N, 5, H, W))
+    a.placed()
     _morph_apart(what, "msk_u8", msk_u8, out)
-    if out is None:
-        out = torch.empty(N, 5, H, W, dtype=torch.uint8, device=msk_u8.device)
     _call("dh_xbd_msk_dilate_u8", _vp(msk_u8.data_ptr()), N, H, W, k, _vp(out.data_ptr()), S())
     return out
 
@@ -2518,10 +2485,7 @@ def xbd_msk_dilate(msk_u8, k=5, out=None):
 def xbd_fill_holes_ws_bytes(N, H, W):
     """bytes of the workspace xbd_fill_holes needs for [N, H, W]: labels int32 [N, H W] and count [N], xbd_cc_label's own
     workspace, the key uint8 [N, H W] and the marks uint8 [N, H W + 1] (each padded to four bytes)"""
-    n = ctypes.c_long(0)
-    if _lib.lib().dh_xbd_fill_holes_ws_bytes(N, H, W, ctypes.byref(n)) != 0:
-        raise ValueError(_lib.lib().dh_last_error().decode())
-    return int(n.value)
+    return _ws_bytes("dh_xbd_fill_holes_ws_bytes", N, H, W)
 
 
 def xbd_fill_holes(map_u8, background=4, out=None, ws=None):
@@ -2535,21 +2499,13 @@ def xbd_fill_holes(map_u8, background=4, out=None, ws=None):
     what = "xbd_fill_holes"
     if isinstance(background, bool) or not isinstance(background, int) or background not in (4, 8):
         raise ValueError("%s: background connectivity %r is neither 4 nor 8" % (what, background))
-    N, H, W = _cc_image(what, "map_u8", map_u8, torch.uint8)
-    named = [("map_u8", map_u8, torch.uint8, None, "[N, H, W]")]
-    if out is not None:
-        named.append(("out", out, torch.uint8, (N, H, W), str([N, H, W])))
-    if ws is not None:
-        named.append(("ws", ws, torch.uint8, None, "workspace"))
-    _cc_tensors(what, named)
+    a = _Args(what)
+    N, H, W = a.image("map_u8", map_u8, torch.uint8)
+    out = a.out(out, torch.uint8, (N, H, W))
+    a.workspace(ws)
+    a.placed()
     _morph_apart(what, "map_u8", map_u8, out)
-    need = xbd_fill_holes_ws_bytes(N, H, W)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=map_u8.device)
-    elif ws.numel() < need or ws.data_ptr() % 4:
-        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
-    if out is None:
-        out = torch.empty(N, H, W, dtype=torch.uint8, device=map_u8.device)
+    ws = _workspace(what, ws, xbd_fill_holes_ws_bytes(N, H, W), map_u8.device)
     _call("dh_xbd_fill_holes_u8", _vp(map_u8.data_ptr()), N, H, W, int(background), _vp(out.data_ptr()), _vp(ws.data_ptr()),
           ws.numel(), S())
     return out
@@ -2570,33 +2526,16 @@ def cd_eval_vis(a, b, logits, label, out=None):
     [N, 1, H, W]: white where it is >= 1.  Tile positions beyond N are black.  out: a uint8 buffer of that shape to write into.
     One launch writes every byte.  ValueError, before any launch, for a wrong rank or dtype, shapes that do not agree, tensors
     on different devices or non-contiguous storage; HipLibraryError for CPU tensors (there is no CPU path)."""
-    what = "cd_eval_vis"
-
-    def typed(name, t, dtype, text, ok):
-        if not torch.is_tensor(t) or t.dtype != dtype or not ok(t):
-            raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
-                                                            str(dtype).replace("torch.", ""), text))
-    typed("a", a, torch.float32, "[N, 3, H, W]", lambda t: t.dim() == 4 and t.shape[1] == 3 and t.numel() > 0)
+    args = _Args("cd_eval_vis", cpu_error=True)
+    args.tensor("a", a, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 3 and t.numel() > 0, "[N, 3, H, W]")
     N, _, H, W = a.shape
-    typed("b", b, torch.float32, "%s like a" % [N, 3, H, W], lambda t: tuple(t.shape) == (N, 3, H, W))
-    typed("logits", logits, torch.float32, "[%d, C, %d, %d] like a" % (N, H, W),
-          lambda t: t.dim() == 4 and t.shape[1] >= 1 and (t.shape[0],) + tuple(t.shape[2:]) == (N, H, W))
-    typed("label", label, torch.int64, "%s or %s like a" % ([N, H, W], [N, 1, H, W]),
-          lambda t: tuple(t.shape) in ((N, H, W), (N, 1, H, W)))
-    checked = [("a", a), ("b", b), ("logits", logits), ("label", label)]
-    want = cd_vis_shape(N, H, W)
-    if out is not None:
-        typed("out", out, torch.uint8, str(list(want)), lambda t: tuple(t.shape) == want)
-        checked.append(("out", out))
-    if not any(t.is_cuda for _, t in checked):
-        raise _lib.HipLibraryError("dahitra_amd %s runs on MI355X only (no CPU fallback): its tensors are on the CPU" % what)
-    for name, t in checked:
-        if not t.is_cuda or t.device != a.device:
-            raise ValueError("%s: %s is on %s and a on %s; the kernel takes all its tensors on one GPU" % (what, name, t.device, a.device))
-        if not t.is_contiguous():
-            raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
-    if out is None:
-        out = torch.empty(want, dtype=torch.uint8, device=a.device)
+    args.tensor("b", b, torch.float32, (N, 3, H, W), "%s like a" % [N, 3, H, W])
+    args.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and t.shape[1] >= 1 and (t.shape[0],) + tuple(t.shape[2:]) == (N, H, W),
+                "[%d, C, %d, %d] like a" % (N, H, W))
+    args.tensor("label", label, torch.int64, lambda t: tuple(t.shape) in ((N, H, W), (N, 1, H, W)),
+                "%s or %s like a" % ([N, H, W], [N, 1, H, W]))
+    out = args.out(out, torch.uint8, cd_vis_shape(N, H, W))
+    args.placed()
     _call("dh_cd_eval_vis_u8", _vp(a.data_ptr()), _vp(b.data_ptr()), _vp(logits.data_ptr()), _vp(label.data_ptr()), N,
           logits.shape[1], H, W, _vp(out.data_ptr()), S())
     return out
@@ -2628,28 +2567,6 @@ def tile_tables(plan, device):
     return t
 
 
-def _tile_checker(what):
-    checked = []
-
-    def typed(name, t, dtype, text, ok):
-        if not torch.is_tensor(t) or t.dtype != dtype or not ok(t):
-            raise ValueError("%s: %s %s %s is not %s %s" % (what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
-                                                            str(dtype).replace("torch.", ""), text))
-        checked.append((name, t))
-
-    def placed():
-        first = checked[0][1]
-        if not any(t.is_cuda for _, t in checked):
-            raise _lib.HipLibraryError("dahitra_amd %s runs on MI355X only (no CPU fallback): its tensors are on the CPU" % what)
-        for name, t in checked:
-            if not t.is_cuda or t.device != first.device:
-                raise ValueError("%s: %s is on %s and %s on %s; the kernel takes all its tensors on one GPU"
-                                 % (what, name, t.device, checked[0][0], first.device))
-            if not t.is_contiguous():
-                raise ValueError("%s: %s is not contiguous (strides %s)" % (what, name, t.stride()))
-    return typed, placed
-
-
 def cd_tile_stitch(logits, plan, out_logits=None, out_mask=None, label=None, counts=None, label_index=None):
     """The change map of a whole tile from the net's answers to its windows (tiles.TilePlan), on the device.
     logits float32 [P, C, h, w], view p of `plan` each, still flipped -> (mask uint8 [H, W], blended logits float32 [C, H, W]).
@@ -2664,33 +2581,26 @@ def cd_tile_stitch(logits, plan, out_logits=None, out_mask=None, label=None, cou
     devices or non-contiguous storage; HipLibraryError for CPU tensors (there is no CPU path)."""
     what = "cd_tile_stitch"
     plan._need_stitchable(what)
-    typed, placed = _tile_checker(what)
+    a = _Args(what, cpu_error=True)
     P, h, w, H, W = plan.P, plan.h, plan.w, plan.H, plan.W
-    typed("logits", logits, torch.float32, "[%d, C <= 8, %d, %d] as the plan has it" % (P, h, w),
-          lambda t: t.dim() == 4 and 1 <= t.shape[1] <= 8 and (t.shape[0],) + tuple(t.shape[2:]) == (P, h, w))
+    a.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and 1 <= t.shape[1] <= 8 and (t.shape[0],) + tuple(t.shape[2:]) == (P, h, w),
+             "[%d, C <= 8, %d, %d] as the plan has it" % (P, h, w))
     C = logits.shape[1]
-    if out_logits is not None:
-        typed("out_logits", out_logits, torch.float32, str([C, H, W]), lambda t: tuple(t.shape) == (C, H, W))
-    if out_mask is not None:
-        typed("out_mask", out_mask, torch.uint8, str([H, W]), lambda t: tuple(t.shape) == (H, W))
+    out_logits = a.out(out_logits, torch.float32, (C, H, W), "out_logits")
+    out_mask = a.out(out_mask, torch.uint8, (H, W), "out_mask")
     if (label is None) != (counts is None):
         raise ValueError("%s: a label tile and counts come together" % what)
     if label_index is not None and label is None:
         raise ValueError("%s: a label index without labels" % what)
     if label is not None:
         if label_index is None:
-            typed("label", label, torch.uint8, str([H, W]), lambda t: tuple(t.shape) == (H, W))
+            a.tensor("label", label, torch.uint8, (H, W))
         else:
-            typed("label", label, torch.uint8, "[S, %d, %d]" % (H, W), lambda t: t.dim() == 3 and tuple(t.shape[1:]) == (H, W))
-            typed("label_index", label_index, torch.int32, "of one element", lambda t: t.numel() == 1)
-        typed("counts", counts, torch.int64, str([C, C]), lambda t: tuple(t.shape) == (C, C))
-    placed()
-    dev = logits.device
-    if out_logits is None:
-        out_logits = torch.empty(C, H, W, dtype=torch.float32, device=dev)
-    if out_mask is None:
-        out_mask = torch.empty(H, W, dtype=torch.uint8, device=dev)
-    t = tile_tables(plan, dev)
+            a.tensor("label", label, torch.uint8, lambda t: t.dim() == 3 and tuple(t.shape[1:]) == (H, W), "[S, %d, %d]" % (H, W))
+            a.tensor("label_index", label_index, torch.int32, lambda t: t.numel() == 1, "of one element")
+        a.tensor("counts", counts, torch.int64, (C, C))
+    a.placed()
+    t = tile_tables(plan, logits.device)
     vp = lambda x: _vp(x.data_ptr()) if x is not None else _vp(0)
     _call("dh_cd_tile_stitch", vp(logits), P, C, h, w, vp(t["ys"]), plan.ny, vp(t["xs"]), plan.nx, vp(t["flips"]), plan.nf,
           vp(t["wy"]), vp(t["wx"]), vp(t["rows"]), vp(t["cols"]), plan.x_align(), H, W, vp(out_logits), vp(out_mask), vp(label),
@@ -2704,13 +2614,13 @@ def cd_view_counts(logits, labels, counts):
     orientation counts[p, label, class].  One launch for what P evaluators each keep.  ValueError, before any launch, for a
     wrong rank, dtype or shape, tensors on different devices or non-contiguous storage; HipLibraryError for CPU tensors."""
     what = "cd_view_counts"
-    typed, placed = _tile_checker(what)
-    typed("logits", logits, torch.float32, "[P, C <= 8, h, w]", lambda t: t.dim() == 4 and 1 <= t.shape[1] <= 8 and t.numel() > 0)
+    a = _Args(what, cpu_error=True)
+    a.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and 1 <= t.shape[1] <= 8 and t.numel() > 0, "[P, C <= 8, h, w]")
     P, C, h, w = logits.shape
-    typed("labels", labels, torch.uint8, "%s or %s like logits" % ([P, h, w], [P, 1, h, w]),
-          lambda t: tuple(t.shape) in ((P, h, w), (P, 1, h, w)))
-    typed("counts", counts, torch.int64, str([P, C, C]), lambda t: tuple(t.shape) == (P, C, C))
-    placed()
+    a.tensor("labels", labels, torch.uint8, lambda t: tuple(t.shape) in ((P, h, w), (P, 1, h, w)),
+             "%s or %s like logits" % ([P, h, w], [P, 1, h, w]))
+    a.tensor("counts", counts, torch.int64, (P, C, C))
+    a.placed()
     _call("dh_cd_view_counts", _vp(logits.data_ptr()), _vp(labels.data_ptr()), P, C, h, w, _vp(counts.data_ptr()), S())
     return counts
 

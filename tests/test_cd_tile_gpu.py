@@ -322,7 +322,7 @@ def test_one_recorded_step_follows_its_device_index(world):
         with pytest.raises(ValueError):
             step.step(bad)
     world.net.train()
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="eval-mode forward"):
         step.step(0)
     world.net.eval()
     with pytest.raises(ValueError):
@@ -409,3 +409,26 @@ def test_recorded_steps_are_kept_once_and_can_be_dropped(world):
     assert forget_tile_steps(world.net, world.pipe) == 2 and forget_tile_steps(world.net) == 0
     again, _ = predict_tile(world.net, world.pipe, 0, world.plan_b)               # recorded anew, the same bytes
     assert torch.equal(again, m0) and not torch.equal(m0, m1)
+
+
+def test_recorded_step_leaves_its_counts_alone_and_refuses_a_rebuilt_arena(world):
+    """(last in the file: it replaces a parameter of the shared net)"""
+    from dahitra_amd.graph import GraphedTileStep, TileBuffers
+    prefill = torch.tensor([[11, 22], [33, 44]], dtype=torch.int64, device=DEV)
+    conf = prefill.clone()
+    step = GraphedTileStep(world.net, world.pipe, world.plan_b, confusion=conf)
+    assert torch.equal(conf, prefill), "warm-up and capture leave the counts as they were"
+    eager = prefill.clone()
+    buf = TileBuffers(world.net, world.pipe, world.plan_b, eager)
+    for index in (0, 2):                                                           # two replays against two eager bodies
+        mask, logits = step.step(index)
+        buf.aim(index)
+        buf.run()
+        assert torch.equal(mask, buf.mask) and np.array_equal(bits(logits), bits(buf.logits)) and torch.equal(conf, eager), index
+    assert int(conf.sum()) == int(prefill.sum()) + 2 * 512 * 512
+    p = next(world.net.parameters())
+    p.data = p.data.clone()
+    world.net._ensure_arena(p.device)
+    with pytest.raises(RuntimeError, match="rebuilt"):
+        step.step(0)
+    assert torch.equal(conf, eager)

@@ -520,7 +520,14 @@ def test_hip_graph_eval_step_equals_the_eager_evaluation_forward(name, cdtype):
     assert not torch.equal(lo3, lo1)
     assert torch.equal(step(a, b, lab), lo3)
     net.train()
-    with pytest.raises(RuntimeError, match="eval"):
+    with pytest.raises(RuntimeError, match="eval-mode forward"):
+        step(a, b, lab)
+    # the arena is rebuilt (a parameter replaced): the graph holds the old one's addresses and refuses to replay
+    net.eval()
+    p = next(net.parameters())
+    p.data = p.data.clone()
+    net._ensure_arena(p.device)
+    with pytest.raises(RuntimeError, match="rebuilt"):
         step(a, b, lab)
 
 

@@ -300,13 +300,20 @@ def test_recorded_step_and_validate_sweep_give_the_eager_integers(model_case, ca
             step(*bad)
     assert torch.equal(ch, before)
     net.train()
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="eval-mode forward"):
         step(b0["img"], b0["msk"], b0["lbl_msk"])
     net.eval()
     with pytest.raises(ValueError):
         xbd.validate_sweep(net, batches, [0.5, 0.3])
     with pytest.raises(ValueError):
         xbd.validate_sweep(net, [], THR19)
+    # the arena is rebuilt (a parameter replaced): the stale step refuses to replay and leaves the histogram alone
+    p = next(net.parameters())
+    p.data = p.data.clone()
+    net._ensure_arena(p.device)
+    with pytest.raises(RuntimeError, match="rebuilt"):
+        step(b0["img"], b0["msk"], b0["lbl_msk"])
+    assert torch.equal(ch, before)
 
 
 def test_evaluate_val_sweep_saves_the_snapshot_with_its_threshold_only_when_the_score_improves(model_case, tmp_path, capsys):

@@ -221,9 +221,19 @@ def test_graphed_step_replays_bit_equal_to_the_eager_path_and_checks_shapes(mode
             step(*bad)
     assert torch.equal(cc, before)
     net.train()
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="eval-mode forward"):
         step(b0["img"], b0["msk"], b0["lbl_msk"])
     net.eval()
+    # the arena is rebuilt (a parameter replaced): validate records a new step, the stale one refuses to replay
+    p = next(net.parameters())
+    p.data = p.data.clone()
+    net._ensure_arena(p.device)
+    _, _, ric, rcc = xbd.validate(net, batches, graph=True, want_counts=True)
+    assert np.array_equal(ric, ic) and np.array_equal(rcc, ecc_epoch)
+    assert any(kept._generation == net._arena.generation != step._generation for kept in net._xbd_eval_steps.values())
+    with pytest.raises(RuntimeError, match="rebuilt"):
+        step(b0["img"], b0["msk"], b0["lbl_msk"])
+    assert torch.equal(cc, before)
 
 
 def test_evaluate_val_saves_the_snapshot_only_when_the_score_improves(model_case, tmp_path, capsys):
