@@ -1,2 +1,2 @@
-from .xbd_pipeline import (GpuXbdPipeline, draw_jitter_params, draw_train_params, jitter_reference_u8,  # noqa: F401
-                           resize_coeffs)
+from .xbd_pipeline import (GpuXbdPipeline, draw_jitter_params, draw_train_params, draw_unet_params,  # noqa: F401
+                           jitter_reference_u8, resize_coeffs, unet_reference_u8, unet_warp_table, warp_affine_u8)

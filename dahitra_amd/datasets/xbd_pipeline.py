@@ -24,8 +24,25 @@ Differences from the reference, all deliberate:
     Pillow's (`jitter_reference_u8` states it).
   * `dilate=k` (off by default) replaces `msk` of a training batch by the dilated, prioritised channels that
     xBD_code/train_unettransformer.py:262-273 builds with dilation(., square(5)) -- lines that train.py, which this loader
-    follows, has commented out -- in one more launch (dh_xbd_msk_dilate_u8).  That script's other augmentations are not built.
+    follows, has commented out -- in one more launch (dh_xbd_msk_dilate_u8).
+
+xBD_code/train_unettransformer.py, the script that trains DAHiTra proper, augments differently: vertical flip, np.rot90, a
+reflect-101 shift, a cv2.warpAffine rotate / scale and shift_channels.  `make_unet_batch` / `unet_batches` are that loader,
+one launch per batch as well (dh_xbd_augment_warp_u8), with `draw_unet_params` for its draws:
+
+    for batch in pipe.unet_batches(16, 256, random.Random(0)):                    # dilate=5: the script's targets
+        loss = step(batch['img'], batch['msk'])
+
+  * The byte contract of the warp is `warp_affine_u8`, a numpy restatement of OpenCV's fixed-point path for 8-bit images
+    (INTER_LINEAR, BORDER_REFLECT_101; OpenCV 4.x up to 4.10, imgwarp.cpp), and `unet_reference_u8` around it.  It was written
+    from that code, not compared with it: no OpenCV is installed where this was built and tested, so equality with a cv2 build
+    has not been run.  OpenCV 4.11 and later take another path for linear warpAffine, and the matrix's cos / sin come from the
+    libm of the host that writes the tables.
+  * Not built: the script's colour operations (change_hsv, clahe, gauss_noise, blur, saturation, brightness, contrast) and
+    imgaug's elastic transform, each drawn by under 2 % of the samples.  `draw_unet_params` draws them, so the `random` stream
+    stands where the script's does, and reports them as `skipped`; they are not applied.
 """
+import collections
 import ctypes
 import functools
 import glob
@@ -230,6 +247,237 @@ def coef_table(params, crop):
     return torch.from_numpy(table)
 
 
+# ---- xBD_code/train_unettransformer.py's TrainData: vflip, rot90, shift_image, rotate_image, shift_channels ----
+
+UNET_SKIPPED = tuple("%s_%s" % (op, im) for op in ("change_hsv", "clahe", "gauss_noise", "blur", "saturation", "brightness",
+                                                   "contrast", "elastic") for im in ("pre", "post"))
+UNET_MAX_SHIFT = 1 << 20   # |sx|, |sy| the kernel takes as they are (the script draws -320 .. 320)
+
+
+def draw_unet_params(rng, H, W, crop):
+    """One training sample's draws of xBD_code/train_unettransformer.py:109-253 from `rng` (a random.Random, or the `random`
+    module), in the script's order and count, so the stream stands where the script's stands after the sample.  Returns
+    (row, skipped).
+    row: a dict of the operations that are built --
+        x0, y0   the crop origin (randint(0, W - crop), randint(0, H - crop))
+        vflip    0 / 1: random() > 0.5
+        rot      k of np.rot90, 0 .. 3: randrange(4) if random() > 0.05
+        shift    None or (sx, sy), two randint(-320, 320): if random() > 0.9
+        warp     None or (angle, scale, (cx, cy)): if random() > 0.6 the centre crop // 2 + randint(-320, 320) twice, scale =
+                 0.9 + random() * 0.2, angle = randint(0, 20) - 10; the script skips the warp, not its draws, when angle == 0
+                 and scale == 1 (line 160)
+        channels None or (image, b, g, r), image 1 = pre, 2 = post, three randint(-5, 5) in the script's (BGR) order: the
+                 if / elif pair of lines 206-209, whose second random() is drawn only when the first test fails.
+    skipped: the names (UNET_SKIPPED) of the operations the sample drew that are NOT built and not applied: change_hsv (three
+    randint(-5, 5)), clahe, gauss_noise, blur, saturation / brightness / contrast (one random() each) and elastic, each
+    with _pre or _post.  (gauss_noise and elastic draw their own numbers from numpy's generators, not from `random`.)"""
+    if crop > H or crop > W:
+        raise ValueError("crop %d is larger than the %dx%d image" % (crop, H, W))
+    row = {"x0": rng.randint(0, W - crop), "y0": rng.randint(0, H - crop), "vflip": 0, "rot": 0, "shift": None, "warp": None,
+           "channels": None}
+    skipped = []
+    row["vflip"] = int(rng.random() > 0.5)
+    if rng.random() > 0.05:
+        row["rot"] = rng.randrange(4)
+    if rng.random() > 0.9:
+        row["shift"] = (rng.randint(-320, 320), rng.randint(-320, 320))
+    if rng.random() > 0.6:
+        centre = (crop // 2 + rng.randint(-320, 320), crop // 2 + rng.randint(-320, 320))
+        scale = 0.9 + rng.random() * 0.2
+        angle = rng.randint(0, 20) - 10
+        if angle != 0 or scale != 1:
+            row["warp"] = (angle, scale, centre)
+    three = lambda: (rng.randint(-5, 5), rng.randint(-5, 5), rng.randint(-5, 5))
+    if rng.random() > 0.985:
+        row["channels"] = (1,) + three()
+    elif rng.random() > 0.985:
+        row["channels"] = (2,) + three()
+    if rng.random() > 0.985:
+        three()
+        skipped.append("change_hsv_pre")
+    elif rng.random() > 0.985:
+        three()
+        skipped.append("change_hsv_post")
+    for im in ("pre", "post"):                                # lines 216-244: the same nested block for either image
+        if rng.random() > 0.98:
+            if rng.random() > 0.985:
+                skipped.append("clahe_" + im)
+            elif rng.random() > 0.985:
+                skipped.append("gauss_noise_" + im)
+            elif rng.random() > 0.985:
+                skipped.append("blur_" + im)
+        elif rng.random() > 0.98:
+            for op in ("saturation", "brightness", "contrast"):
+                if rng.random() > 0.985:
+                    rng.random()                              # the factor 0.9 + random() * 0.2
+                    skipped.append("%s_%s" % (op, im))
+                    break
+    for im in ("pre", "post"):
+        if rng.random() > 0.983:
+            skipped.append("elastic_" + im)
+    return row, skipped
+
+
+def rotation_matrix(centre, angle, scale):
+    """cv2.getRotationMatrix2D(centre, angle, scale) as a [2, 3] float64 array; cos / sin are this libm's"""
+    a = angle * math.pi / 180.0
+    alpha, beta = math.cos(a) * scale, math.sin(a) * scale
+    cx, cy = float(centre[0]), float(centre[1])
+    return np.array([[alpha, beta, (1 - alpha) * cx - beta * cy], [-beta, alpha, beta * cx + (1 - alpha) * cy]], dtype=np.float64)
+
+
+def shift_matrix(shift):
+    """the matrix of the script's shift_image(img, (sx, sy))"""
+    return np.array([[1.0, 0.0, float(shift[0])], [0.0, 1.0, float(shift[1])]], dtype=np.float64)
+
+
+def warp_tables(M, width, height):
+    """(adelta[width], bdelta[width], X0[height], Y0[height]) int64: the tables of cv2.warpAffine(img, M, (width, height),
+    flags=INTER_LINEAR) without WARP_INVERSE_MAP (OpenCV 4.x up to 4.10, imgwarp.cpp).  M [2, 3] float64 is inverted as
+    warpAffine does it -- D = M0 M4 - M1 M3, D = 1 / D if D != 0 else 0, A11 = M4 D, A22 = M0 D, M0 = A11, M1 *= -D, M3 *= -D,
+    M4 = A22, b1 = -M0 M2 - M1 M5, b2 = -M3 M2 - M4 M5 --, then adelta[x] = rint(M0 x 1024), bdelta[x] = rint(M3 x 1024), X0[y] =
+    rint((M1 y + M2) 1024) + 16, Y0[y] = rint((M4 y + M5) 1024) + 16, rint to even.  An output pixel reads the taps at ((X0[y] +
+    adelta[x]) >> 10, (Y0[y] + bdelta[x]) >> 10); OpenCV saturates that origin to int16, which no warp of the script comes near:
+    ValueError where an origin leaves -32768 .. 32767, or a table entry int32."""
+    m = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(6)]
+    if not all(math.isfinite(v) for v in m):
+        raise ValueError("warp_tables: the matrix %r is not finite" % (m,))
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[4] * D, m[0] * D
+    m[0], m[1], m[3], m[4] = A11, m[1] * -D, m[3] * -D, A22
+    b1, b2 = -m[0] * m[2] - m[1] * m[5], -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    x, y = np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64)
+    with np.errstate(over='ignore', invalid='ignore'):
+        f = [m[0] * x * 1024, m[3] * x * 1024, (m[1] * y + m[2]) * 1024, (m[4] * y + m[5]) * 1024]
+    if not all(np.isfinite(t).all() and (np.abs(t) < 2.0 ** 30).all() for t in f):
+        raise ValueError("warp_tables: a table entry leaves the int32 range")
+    ad, bd, X0, Y0 = (np.rint(t).astype(np.int64) for t in f)
+    X0, Y0 = X0 + 16, Y0 + 16
+    # rint is monotone, so the extremes of X0[y] + adelta[x] are sums of the tables' extremes
+    for a, b in ((X0, ad), (Y0, bd)):
+        if (int(a.min()) + int(b.min())) >> 10 < -32768 or (int(a.max()) + int(b.max())) >> 10 > 32767:
+            raise ValueError("warp_tables: a tap origin leaves the int16 range (OpenCV saturates there; not built)")
+    return ad, bd, X0, Y0
+
+
+def _reflect101(p, n):
+    """cv2.BORDER_REFLECT_101 of an integer array into 0 .. n - 1"""
+    if n == 1:
+        return np.zeros_like(p)
+    m = 2 * (n - 1)
+    p = np.mod(p, m)
+    return np.where(p >= n, m - p, p)
+
+
+def warp_affine_u8(img_u8, M):
+    """cv2.warpAffine(img, M, (w, h), flags=cv2.INTER_LINEAR, borderMode=cv2.BORDER_REFLECT_101) of an [h, w] or [h, w, c]
+    uint8 image, restated from OpenCV's fixed-point path for CV_8U (4.x up to 4.10; 4.11 and later take another path for
+    linear warpAffine): with warp_tables' four tables, X = (X0[y] + adelta[x]) >> 5 and Y = (Y0[y] + bdelta[x]) >> 5; the four
+    taps are (X >> 5, Y >> 5), its right, lower and lower-right neighbour, each coordinate reflected (101) into the image; fx =
+    X & 31, fy = Y & 31; the weights are (32 - fx)(32 - fy) 32, fx (32 - fy) 32, (32 - fx) fy 32, fx fy 32 (OpenCV's 32 x 32
+    bilinear table scaled by 32768; exact products here, the sum is 32768); byte = (sum w v + 16384) >> 15.  This restatement,
+    not an installed OpenCV, is the byte contract of dh_xbd_augment_warp_u8; tests/test_xbd_unet_cpu.py holds it to identities
+    that do not depend on it."""
+    img = np.asarray(img_u8)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError("warp_affine_u8: an [h, w] or [h, w, c] uint8 image, got %s %s" % (img.shape, img.dtype))
+    h, w = img.shape[:2]
+    ad, bd, X0, Y0 = warp_tables(M, w, h)
+    X, Y = (X0[:, None] + ad[None, :]) >> 5, (Y0[:, None] + bd[None, :]) >> 5
+    u0, v0, fx, fy = _reflect101(X >> 5, w), _reflect101(Y >> 5, h), X & 31, Y & 31
+    u1, v1 = _reflect101((X >> 5) + 1, w), _reflect101((Y >> 5) + 1, h)
+    a = img.astype(np.int64).reshape(h, w, -1)
+    acc = (((32 - fx) * (32 - fy) * 32)[..., None] * a[v0, u0] + (fx * (32 - fy) * 32)[..., None] * a[v0, u1]
+           + ((32 - fx) * fy * 32)[..., None] * a[v1, u0] + (fx * fy * 32)[..., None] * a[v1, u1])
+    return ((acc + 16384) >> 15).astype(np.uint8).reshape(img.shape)
+
+
+def check_unet_rows(rows, H, W, crop):
+    """the rows of a batch (draw_unet_params' dicts) as they are; ValueError for a crop that does not fit the image, a window
+    outside it, a flip that is not 0 / 1, a rot outside 0 .. 3, a shift that is no pair of integers within +-2^20, a warp that is
+    no (angle, scale, (cx, cy)) of finite numbers, or channels that are no (1 or 2, b, g, r) with integer shifts within +-255"""
+    if crop < 1 or crop > H or crop > W:
+        raise ValueError("crop %d does not fit the %dx%d image" % (crop, H, W))
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    for n, row in enumerate(rows):
+        if not isinstance(row, dict) or set(row) != {"x0", "y0", "vflip", "rot", "shift", "warp", "channels"}:
+            raise ValueError("rows[%d]: a dict of x0, y0, vflip, rot, shift, warp, channels (draw_unet_params), got %r" % (n, row))
+        if not (is_int(row["x0"]) and is_int(row["y0"]) and 0 <= row["x0"] <= W - crop and 0 <= row["y0"] <= H - crop):
+            raise ValueError("rows[%d]: crop window (%r, %r) + %d leaves the %dx%d image" % (n, row["x0"], row["y0"], crop, H, W))
+        if row["vflip"] not in (0, 1) or not is_int(row["rot"]) or not 0 <= row["rot"] <= 3:
+            raise ValueError("rows[%d]: vflip %r is not 0 / 1 or rot %r not 0 .. 3" % (n, row["vflip"], row["rot"]))
+        s = row["shift"]
+        if s is not None and not (len(s) == 2 and all(is_int(v) and abs(v) <= UNET_MAX_SHIFT for v in s)):
+            raise ValueError("rows[%d]: shift %r is no pair of integers within +-%d" % (n, s, UNET_MAX_SHIFT))
+        w = row["warp"]
+        if w is not None:
+            ok = len(w) == 3 and len(w[2]) == 2 and all(isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
+                                                         for v in (w[0], w[1]) + tuple(w[2]))
+            if not ok:
+                raise ValueError("rows[%d]: warp %r is no (angle, scale, (cx, cy)) of finite numbers" % (n, w))
+        c = row["channels"]
+        if c is not None and not (len(c) == 4 and c[0] in (1, 2) and all(is_int(v) and abs(v) <= 255 for v in c[1:])):
+            raise ValueError("rows[%d]: channels %r is no (1 = pre or 2 = post, b, g, r) with shifts within +-255" % (n, c))
+    return rows
+
+
+def unet_param_rows(rows):
+    """[n, 12] int32 numpy rows of dh_xbd_augment_warp_u8 from checked rows: x0, y0, vflip, rot, sx, sy, warp, chan, dR, dG, dB,
+    0.  The pipeline stores RGB and the script's images are BGR: its b_shift goes to plane 2."""
+    p = np.zeros((len(rows), ops.XBD_WARP_PARAM_WORDS), dtype=np.int32)
+    for n, row in enumerate(rows):
+        sx, sy = row["shift"] or (0, 0)
+        chan, b, g, r = row["channels"] or (0, 0, 0, 0)
+        p[n, :11] = [row["x0"], row["y0"], row["vflip"], row["rot"], sx, sy, int(row["warp"] is not None), chan, r, g, b]
+    return p
+
+
+def unet_warp_table(rows, crop):
+    """[n, 4, crop] int32 numpy tables (adelta, bdelta, X0, Y0: warp_tables of rotation_matrix(centre, angle, scale)) for
+    dh_xbd_augment_warp_u8, or None when no row warps; rows of samples without a warp stay 0 and are not read.  A shift needs
+    no table: shift_image's matrix [[1, 0, sx], [0, 1, sy]] through the same tables is the single tap (x - sx, y - sy) at full
+    weight, which the kernel takes from the row (tests/test_xbd_unet_cpu.py shows the two equal).  ValueError where a tap origin
+    would leave the int16 range (OpenCV saturates there)."""
+    if not any(row["warp"] is not None for row in rows):
+        return None
+    table = np.zeros((len(rows), 4, crop), dtype=np.int32)
+    for n, row in enumerate(rows):
+        if row["warp"] is not None:
+            angle, scale, centre = row["warp"]
+            table[n] = np.stack(warp_tables(rotation_matrix(centre, angle, scale), crop, crop))
+    return table
+
+
+def unet_reference_u8(pre, post, label, row, crop):
+    """What TrainData.__getitem__ of xBD_code/train_unettransformer.py computes for one sample, line by line and through every
+    intermediate image, on the operations that are built: pre, post [H, W, 3] uint8 RGB and label [H, W] uint8 -> (img uint8
+    [6, crop, crop], the planes pre R G B, post R G B in front of preprocess_inputs; msk uint8 [5, crop, crop], 0 / 1, in front of
+    the dilation of lines 265-273).  The crop; [::-1] if vflip; np.rot90(., rot); shift_image and rotate_image as
+    warp_affine_u8 of shift_matrix / rotation_matrix, on both images and on the four 0 / 255 planes of (label == c), which are
+    thresholded > 127 afterwards (channel 0 = any of them); shift_channels on the image that drew it (b to plane 2: RGB here).
+    dh_xbd_augment_warp_u8 equals it byte for byte (tests/test_xbd_unet_gpu.py)."""
+    x0, y0 = row["x0"], row["y0"]
+    win = lambda a: a[y0:y0 + crop, x0:x0 + crop]
+    planes = [win(np.asarray(pre)), win(np.asarray(post))] + [((win(np.asarray(label)) == c) * 255).astype(np.uint8) for c in (1, 2, 3, 4)]
+    if row["vflip"]:
+        planes = [a[::-1] for a in planes]
+    planes = [np.ascontiguousarray(np.rot90(a, row["rot"])) for a in planes]
+    if row["shift"] is not None:
+        planes = [warp_affine_u8(a, shift_matrix(row["shift"])) for a in planes]
+    if row["warp"] is not None:
+        angle, scale, centre = row["warp"]
+        planes = [warp_affine_u8(a, rotation_matrix(centre, angle, scale)) for a in planes]
+    if row["channels"] is not None:
+        chan, b, g, r = row["channels"]
+        planes[chan - 1] = np.clip(planes[chan - 1].astype(np.int64) + np.array([r, g, b]), 0, 255).astype(np.uint8)
+    img = np.concatenate([planes[0], planes[1]], axis=2).transpose(2, 0, 1)
+    m = np.stack(planes[2:]) > 127
+    msk = np.concatenate([m.any(axis=0, keepdims=True), m]).astype(np.uint8)
+    return np.ascontiguousarray(img), msk
+
+
 class GpuXbdPipeline:
     def __init__(self, pre_u8, post_u8, pre_mask_u8, post_label_u8, files=None):
         """pre_u8, post_u8: [n_src, H, W, 3] uint8 device tensors; pre_mask_u8 (0 / 255) and post_label_u8 (0 .. 4):
@@ -243,6 +491,7 @@ class GpuXbdPipeline:
         self.files = list(files) if files is not None else [str(i) for i in range(pre_u8.shape[0])]
         self._zero_lbl = None
         self._jitter_ws = None
+        self.unet_skipped = collections.Counter()      # unet_batches: the drawn operations of the last epoch that are not built
 
     @classmethod
     def from_image_dir(cls, images_dir, device='cuda:0', files=None):
@@ -290,10 +539,9 @@ class GpuXbdPipeline:
         through the priority rule of its lines 262-273 (class 2 over 3 over 4, any of them over 1; channel 0 = any).  The
         dilation acts on the augmented crop, as in the script, which dilates after its crop and flips: a building just outside
         the crop window contributes nothing.  `img`, `lbl_msk` (still all zeros: channel 0 is set wherever another is) and `fn`
-        are untouched.  What this is NOT: that script's rot90, its reflect-101 shift, its cv2.warpAffine rotate / scale and its
-        rare colour operations are not built (cv2's arithmetic, which no test here has an oracle for), so the switch gives
-        train.py's geometry with train_unettransformer.py's targets.  The script's ValData does not dilate: train=False is
-        refused.
+        are untouched.  What this is NOT: that script's geometry -- the switch gives train.py's geometry with
+        train_unettransformer.py's targets; make_unet_batch is the script's own loader (rot90, reflect-101 shift,
+        cv2.warpAffine rotate / scale, shift_channels).  The script's ValData does not dilate: train=False is refused.
         ValueError for a crop larger than the image, a window outside it, a resize box that leaves the crop, jitter in a
         validation batch, jitter rows that do not match the samples, an order that is no permutation, a factor that is not
         finite, a `dilate` that is not 0 or an odd integer of 3 .. 31, or `dilate` in a validation batch."""
@@ -380,3 +628,56 @@ class GpuXbdPipeline:
                 jitter.append((draw_jitter_params(jitter_gen), draw_jitter_params(jitter_gen))
                               if flag and jitter_gen is not None else None)
             yield self.make_batch(ind, crop, params, train, jitter if jitter_gen is not None else None, dilate)
+
+    def make_unet_batch(self, indices, crop, rows, dilate=5):
+        """A training batch of xBD_code/train_unettransformer.py's TrainData, the script that trains DAHiTra proper: rows is one
+        draw_unet_params dict per sample (crop, vflip, rot90, reflect-101 shift, cv2.warpAffine rotate / scale, shift_channels),
+        applied in ONE launch (ops.xbd_augment_warp, dh_xbd_augment_warp_u8), byte for byte unet_reference_u8.  dilate: the
+        script's square(5) dilation and priority rule of lines 262-273 on top (ops.xbd_msk_dilate, one more launch; any odd
+        window of 3 .. 31), 0 for the undilated channels.  Returns make_batch's dict; `lbl_msk` is the shared zero tensor, as
+        the script's argmax gives it (channel 0 is set wherever another one is): read it, never write to it.  Not applied: the
+        colour operations and the elastic transform that draw_unet_params reports as skipped.  The script's ValData is
+        make_batch(ind, 256, [[512, 512, 0, 0, 0, 0, 0, 256, 256]] * len(ind), train=False) as it stands.
+        ValueError for rows that do not fit (check_unet_rows), a warp whose taps leave the int16 range, indices outside the
+        samples, or a `dilate` that is not 0 or an odd integer of 3 .. 31."""
+        n = len(indices)
+        if isinstance(dilate, bool) or not isinstance(dilate, int) or (dilate != 0 and not (3 <= dilate <= ops.XBD_MORPH_MAX_K
+                                                                                             and dilate % 2 == 1)):
+            raise ValueError("dilate: %r is neither 0 nor an odd window of 3 .. %d" % (dilate, ops.XBD_MORPH_MAX_K))
+        _, H, W, _ = self.pre.shape
+        rows = check_unet_rows(list(rows), H, W, crop)
+        if len(rows) != n:
+            raise ValueError("rows: %d rows for %d samples" % (len(rows), n))
+        if n == 0 or any(not 0 <= int(i) < len(self) for i in indices):
+            raise ValueError("indices %r outside the %d samples" % (list(indices), len(self)))
+        tab = unet_warp_table(rows, crop)
+        dev = self.pre.device
+        idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int32).to(dev)
+        p = torch.from_numpy(unet_param_rows(rows)).to(dev)
+        tab = torch.from_numpy(tab).to(dev) if tab is not None else None
+        img, msk = ops.xbd_augment_warp(self.pre, self.post, self.post_label, idx, p, tab, crop)
+        if self._zero_lbl is None or self._zero_lbl.shape != (n, crop, crop):
+            self._zero_lbl = torch.zeros(n, crop, crop, dtype=torch.uint8, device=dev)
+        if dilate:
+            msk = ops.xbd_msk_dilate(msk, dilate)
+        return {'img': img, 'msk': msk, 'lbl_msk': self._zero_lbl, 'fn': [self.files[int(i)] for i in indices]}
+
+    def unet_batches(self, batch_size, crop, rng, dilate=5):
+        """one training epoch of xBD_code/train_unettransformer.py's loader: `rng` (a random.Random) shuffles the samples, then
+        every sample draws with draw_unet_params, in batch order (the sample order is this loader's own, as in `batches`; a
+        sample's draws are the script's).  Yields make_unet_batch's dicts.  `self.unet_skipped` counts, over the epoch, the
+        drawn operations that are not built (collections.Counter of draw_unet_params' names)."""
+        if rng is None:
+            raise ValueError("a training epoch draws from `rng` (a random.Random)")
+        _, H, W, _ = self.pre.shape
+        order = list(range(len(self)))
+        rng.shuffle(order)
+        self.unet_skipped = collections.Counter()
+        for s in range(0, len(order), batch_size):
+            ind = order[s:s + batch_size]
+            rows = []
+            for _ in ind:
+                row, skipped = draw_unet_params(rng, H, W, crop)
+                rows.append(row)
+                self.unet_skipped.update(skipped)
+            yield self.make_unet_batch(ind, crop, rows, dilate)

@@ -2482,6 +2482,35 @@ def xbd_msk_dilate(msk_u8, k=5, out=None):
     return out
 
 
+XBD_WARP_TILE = (32, 32)         # (TH, TW) of dh_xbd_augment_warp_u8's output tile: dh_xbd_augment_warp_tile_h / _tile_w
+XBD_WARP_PARAM_WORDS = 12        # x0, y0, vflip, rot, sx, sy, warp, chan, dR, dG, dB, 0
+
+
+def xbd_augment_warp(pre_u8, post_u8, label_u8, idx, params, tab, crop, out_img=None, out_msk=None):
+    """One batch of xBD_code/train_unettransformer.py's TrainData.__getitem__ on the device (dh_xbd_augment_warp_u8; the header
+    states the arithmetic): pre_u8, post_u8 [n_src, H, W, 3] uint8 RGB, label_u8 [n_src, H, W] uint8, idx [N] int32, params
+    [N, 12] int32 rows, tab [N, 4, crop] int32 warp tables or None (no sample warps) -> (out_img fp32 [N, 6, crop, crop],
+    out_msk uint8 [N, 5, crop, crop]).  One launch.  The rows and tables are datasets/xbd_pipeline's (unet_param_rows, unet_warp_table), which
+    checks them; the kernel reads inside its sources whatever they hold.  ValueError, before any launch, for a wrong rank,
+    dtype, shape or device or non-contiguous storage."""
+    a = _Args("xbd_augment_warp")
+    a.tensor("pre_u8", pre_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[3] == 3 and t.numel() > 0, "[n_src, H, W, 3], not empty")
+    n_src, H, W, _ = pre_u8.shape
+    a.tensor("post_u8", post_u8, torch.uint8, (n_src, H, W, 3))
+    a.tensor("label_u8", label_u8, torch.uint8, (n_src, H, W))
+    a.tensor("idx", idx, torch.int32, lambda t: t.dim() == 1 and t.numel() > 0, "[N], not empty")
+    N = idx.numel()
+    a.tensor("params", params, torch.int32, (N, XBD_WARP_PARAM_WORDS))
+    if tab is not None:
+        a.tensor("tab", tab, torch.int32, (N, 4, crop))
+    out_img = a.out(out_img, torch.float32, (N, 6, crop, crop), "out_img")
+    out_msk = a.out(out_msk, torch.uint8, (N, 5, crop, crop), "out_msk")
+    a.placed()
+    _call("dh_xbd_augment_warp_u8", P(pre_u8), P(post_u8), P(label_u8), P(idx), P(params), P(tab), N, H, W, crop, P(out_img),
+          P(out_msk), S())
+    return out_img, out_msk
+
+
 def xbd_fill_holes_ws_bytes(N, H, W):
     """bytes of the workspace xbd_fill_holes needs for [N, H, W]: labels int32 [N, H W] and count [N], xbd_cc_label's own
     workspace, the key uint8 [N, H W] and the marks uint8 [N, H W + 1] (each padded to four bytes)"""

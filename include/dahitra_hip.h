@@ -411,6 +411,30 @@ int dh_xbd_augment_jitter_u8(const unsigned char* pre, const unsigned char* post
                              const unsigned char* post_label, const int* idx, const int* params, const int* coef,
                              const int* jitter_host, int N, int H, int W, int S, int mode, float* out_img, unsigned char* out_msk,
                              unsigned char* out_lbl, void* workspace, long workspace_bytes, void* stream);
+/* Input pipeline of DAHiTra's own training script (TrainData.__getitem__, xBD_code/train_unettransformer.py:109-167, 206-209,
+ * 255-279, for pre-decoded samples) in one launch: pre, post [n_src][H][W][3] uint8 RGB and post_label (0 .. 4) [n_src][H][W]
+ * uint8 (the pre mask is not an argument: the script overwrites its channel, line 264).  Output sample n takes source idx[n] with
+ * params[n] = 12 int32 {x0, y0, vflip, rot, sx, sy, warp, chan, dR, dG, dB, 0}: the S x S crop at (x0, y0); rows reversed if
+ * `vflip`; np.rot90(., rot), rot = 0 .. 3 (1 is counter-clockwise: out[i][j] = in[j][S-1-i]); shift_image by (sx, sy), i.e.
+ * dst(x, y) = src(x - sx, y - sy) with cv2.BORDER_REFLECT_101 (0, 0: none); if `warp`, rotate_image = cv2.warpAffine(INTER_LINEAR,
+ * BORDER_REFLECT_101) in OpenCV's fixed-point arithmetic for CV_8U (4.x up to 4.10) from tab [N][4][S] int32 = adelta[x],
+ * bdelta[x], X0[y], Y0[y] as datasets/xbd_pipeline.unet_warp_table writes them: X = (X0[y] + adelta[x]) >> 5, Y likewise, taps at
+ * (X >> 5, Y >> 5) and its right / lower neighbours, fractions X & 31 and Y & 31, weights (32 - fx)(32 - fy) 32 .. fx fy 32, byte
+ * = (sum w v + 16384) >> 15; then shift_channels: dR, dG, dB added to the planes of the pre (chan 1) or post (chan 2) image and
+ * clipped to 0 .. 255 (chan 0: nobody).  All of it is one gather from the sources: no intermediate image.  Rows of `tab` of
+ * samples without the flag are not read, and tab == NULL means that no sample warps.  Every tap index is reflected into the crop
+ * and clamped into the image whatever the rows and tables hold.  out_img fp32 [N][6][S][S] = preprocess_inputs(concat(pre,
+ * post)) = x / 127 - 1; out_msk uint8 [N][5][S][S], 0 / 1: channel c = 1 .. 4 is the warped 0 / 255 plane of (label == c)
+ * thresholded > 127, ((255 * (weights of the taps whose label == c) + 16384) >> 15) > 127, channel 0 any of them.  A row of zeros
+ * but for (x0, y0) gives dh_xbd_augment_u8's train-mode bytes.
+ * Refused (nothing is written, non-zero, dh_last_error begins with xbd_augment_warp): a null pointer other than tab, S < 1,
+ * S > H, S > W, N < 1 or beyond the launch grid (65535).
+ * dh_xbd_augment_warp_tile_h / _w: the output tile of a workgroup. */
+int dh_xbd_augment_warp_tile_h(void);
+int dh_xbd_augment_warp_tile_w(void);
+int dh_xbd_augment_warp_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* post_label, const int* idx,
+                           const int* params, const int* tab, int N, int H, int W, int S, float* out_img, unsigned char* out_msk,
+                           void* stream);
 int dh_nchw_to_nhwc(int dtype, const float* src, void* dst, int N, int C, long HW, int CP, void* stream);
 /* data gradient of the class head (3x3 / s1 / p1, 32 -> n_class <= 8 channels; help_funcs.py:13-14, networks.py:1247):
  * dy [N][H][W][CP] (CP = 8 bf16 / 4 or 8 fp32 channels per pixel, the first NC real), w_oihw [NC][32][3][3] fp32,
