@@ -29,6 +29,10 @@ $(OBJ)/norm.o: EXTRA := -mllvm -amdgpu-mfma-vgpr-form
 # note at that kernel); the other kernels of the file are bit-identical and time-neutral under the flag
 $(OBJ)/conv_wreg.o: EXTRA := -mllvm -pragma-unroll-threshold=262144 -fno-slp-vectorize
 
+# augment_xbd_colour: its float64 blends and float32 HSV return are byte contracts stated product by product; a fused multiply-add
+# (hipcc contracts by default) rounds once where they round twice
+$(OBJ)/augment_xbd_colour.o: EXTRA := -ffp-contract=off
+
 $(OBJ)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/conv_mfma_impl.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(FLAGS) $(EXTRA) -c $< -o $@

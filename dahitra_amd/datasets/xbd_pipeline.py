@@ -38,9 +38,16 @@ one launch per batch as well (dh_xbd_augment_warp_u8), with `draw_unet_params` f
     from that code, not compared with it: no OpenCV is installed where this was built and tested, so equality with a cv2 build
     has not been run.  OpenCV 4.11 and later take another path for linear warpAffine, and the matrix's cos / sin come from the
     libm of the host that writes the tables.
-  * Not built: the script's colour operations (change_hsv, clahe, gauss_noise, blur, saturation, brightness, contrast) and
-    imgaug's elastic transform, each drawn by under 2 % of the samples.  `draw_unet_params` draws them, so the `random` stream
-    stands where the script's does, and reports them as `skipped`; they are not applied.
+  * The script's colour stage (lines 211-244: change_hsv, then gauss_noise, cv2.blur, saturation, brightness or contrast) is
+    opt-in: `unet_batches(16, 256, rng, colour=True, np_rng=np.random.RandomState(0))` draws with `draw_unet_colour` --
+    `draw_unet_params`' stream -- and applies it in place in two more launches per batch that drew any (dh_xbd_unet_colour_u8),
+    byte for byte `unet_colour_reference_u8`.  The blends and the noise equal the reference's utils.py on a committed fixture;
+    contrast's mean is defined from the exact channel sums (`contrast_mean`: against numpy's pairwise mean a byte can move only
+    where a blended value lies within about 1e-11 of an integer); cv2.blur and change_hsv's 8-bit cv2.cvtColor are restated from
+    OpenCV 4.x's scalar paths, and equality with a cv2 build has not been run (a vectorised build may fuse multiply-adds and
+    differ by one in a byte).  Without `colour=True` the operations are drawn, reported as `skipped` and not applied.
+  * Not built: clahe (OpenCV's 8-bit Lab tables) and imgaug's elastic transform, each drawn by under 2 % of the samples.  Both
+    draw functions draw them, so the `random` stream stands where the script's does, and report them as `skipped`.
 """
 import collections
 import ctypes
@@ -268,14 +275,23 @@ def draw_unet_params(rng, H, W, crop):
                  and scale == 1 (line 160)
         channels None or (image, b, g, r), image 1 = pre, 2 = post, three randint(-5, 5) in the script's (BGR) order: the
                  if / elif pair of lines 206-209, whose second random() is drawn only when the first test fails.
-    skipped: the names (UNET_SKIPPED) of the operations the sample drew that are NOT built and not applied: change_hsv (three
+    skipped: the names (UNET_SKIPPED) of the operations the sample drew that a batch of these rows does NOT apply (draw_unet_colour
+    keeps the values of those that are built, for make_unet_batch's `colour`; clahe and elastic are not built): change_hsv (three
     randint(-5, 5)), clahe, gauss_noise, blur, saturation / brightness / contrast (one random() each) and elastic, each
     with _pre or _post.  (gauss_noise and elastic draw their own numbers from numpy's generators, not from `random`.)"""
+    row, drawn = _draw_unet_sample(rng, H, W, crop)
+    return row, [name for name, _ in drawn]
+
+
+def _draw_unet_sample(rng, H, W, crop):
+    """the draws of draw_unet_params and draw_unet_colour: (row, drawn) with `drawn` the colour operations and elastic transforms
+    the sample drew, in the script's order, as (name, value): the (h, s, v) of change_hsv, the factor 0.9 + random() * 0.2 of
+    saturation / brightness / contrast, None for the others"""
     if crop > H or crop > W:
         raise ValueError("crop %d is larger than the %dx%d image" % (crop, H, W))
     row = {"x0": rng.randint(0, W - crop), "y0": rng.randint(0, H - crop), "vflip": 0, "rot": 0, "shift": None, "warp": None,
            "channels": None}
-    skipped = []
+    drawn = []
     row["vflip"] = int(rng.random() > 0.5)
     if rng.random() > 0.05:
         row["rot"] = rng.randrange(4)
@@ -293,29 +309,26 @@ def draw_unet_params(rng, H, W, crop):
     elif rng.random() > 0.985:
         row["channels"] = (2,) + three()
     if rng.random() > 0.985:
-        three()
-        skipped.append("change_hsv_pre")
+        drawn.append(("change_hsv_pre", three()))
     elif rng.random() > 0.985:
-        three()
-        skipped.append("change_hsv_post")
+        drawn.append(("change_hsv_post", three()))
     for im in ("pre", "post"):                                # lines 216-244: the same nested block for either image
         if rng.random() > 0.98:
             if rng.random() > 0.985:
-                skipped.append("clahe_" + im)
+                drawn.append(("clahe_" + im, None))
             elif rng.random() > 0.985:
-                skipped.append("gauss_noise_" + im)
+                drawn.append(("gauss_noise_" + im, None))
             elif rng.random() > 0.985:
-                skipped.append("blur_" + im)
+                drawn.append(("blur_" + im, None))
         elif rng.random() > 0.98:
             for op in ("saturation", "brightness", "contrast"):
                 if rng.random() > 0.985:
-                    rng.random()                              # the factor 0.9 + random() * 0.2
-                    skipped.append("%s_%s" % (op, im))
+                    drawn.append(("%s_%s" % (op, im), 0.9 + rng.random() * 0.2))
                     break
     for im in ("pre", "post"):
         if rng.random() > 0.983:
-            skipped.append("elastic_" + im)
-    return row, skipped
+            drawn.append(("elastic_" + im, None))
+    return row, drawn
 
 
 def rotation_matrix(centre, angle, scale):
@@ -478,6 +491,265 @@ def unet_reference_u8(pre, post, label, row, crop):
     return np.ascontiguousarray(img), msk
 
 
+# ---- the script's colour stage (lines 211-244): change_hsv, gauss_noise, cv2.blur, saturation, brightness, contrast ----
+# Images here are [h, w, 3] uint8 in the pipeline's R, G, B order; the script's are BGR, so its channel 0 is plane 2.
+
+UNET_COLOUR_OPS = {"gauss_noise": 1, "blur": 2, "saturation": 3, "brightness": 4, "contrast": 5}    # the kernel's op codes
+UNET_COLOUR_NOT_BUILT = ("clahe", "elastic")
+HSV_SHIFT = 12
+
+
+def _rgb_u8(img, who):
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("%s: an [h, w, 3] uint8 image, got %s %s" % (who, img.shape, img.dtype))
+    return img
+
+
+def _grey(img):
+    """the script's _grayscale of an RGB image, float64 [h, w]: (0.114 b + 0.587 g) + 0.299 r, the order in which numpy sums
+    the three products"""
+    c = img.astype(np.float64)
+    return (0.114 * c[..., 2] + 0.587 * c[..., 1]) + 0.299 * c[..., 0]
+
+
+def _blend(img, gs, alpha):
+    """the script's _blend: clip(img * alpha + (1 - alpha) * gs, 0, 255) in float64, truncated.  (A NaN, which only a factor
+    near the end of the float64 range can give, becomes 0.)"""
+    alpha = float(alpha)
+    with np.errstate(over='ignore', invalid='ignore'):
+        x = img.astype(np.float64) * alpha + (1 - alpha) * gs
+    return np.clip(np.nan_to_num(x, nan=0.0, posinf=255.0, neginf=0.0), 0, 255).astype(np.uint8)
+
+
+def saturation_u8(img, alpha):
+    """utils.saturation: every channel blended with the pixel's grey"""
+    img = _rgb_u8(img, "saturation_u8")
+    return _blend(img, _grey(img)[..., None], alpha)
+
+
+def brightness_u8(img, alpha):
+    """utils.brightness: every channel blended with 0"""
+    return _blend(_rgb_u8(img, "brightness_u8"), 0.0, alpha)
+
+
+def contrast_mean(img):
+    """the grey mean contrast blends with, DEFINED from the exact channel sums: ((0.114 Sb + 0.587 Sg) + 0.299 Sr) / (h w).  The
+    script takes numpy's pairwise mean of the per-pixel greys, which may differ in the last bits; that moves a byte only where a
+    blended value lies within about 1e-11 of an integer."""
+    img = _rgb_u8(img, "contrast_mean")
+    sr, sg, sb = (int(v) for v in img.reshape(-1, 3).astype(np.int64).sum(axis=0))
+    return ((0.114 * float(sb) + 0.587 * float(sg)) + 0.299 * float(sr)) / float(img.shape[0] * img.shape[1])
+
+
+def contrast_u8(img, alpha):
+    """utils.contrast: every channel blended with contrast_mean"""
+    img = _rgb_u8(img, "contrast_u8")
+    return _blend(img, contrast_mean(img), alpha)
+
+
+def draw_unet_noise(np_rng, S):
+    """utils.gauss_noise's draw for an S x S image from `np_rng` (a np.random.RandomState, or the np.random module: the
+    RandomState(k) stream is the one np.random.seed(k) gives): normal(30, 30 ** 0.5, (S, S, 3)) minus its minimum, truncated to
+    uint8, in the script's (BGR) channel order"""
+    g = np_rng.normal(30, 30 ** 0.5, (S, S, 3))
+    return (g - g.min()).astype(np.uint8)
+
+
+def gauss_noise_u8(img, noise_u8):
+    """utils.gauss_noise with the noise already drawn (draw_unet_noise, BGR): min(img + noise, 255)"""
+    img = _rgb_u8(img, "gauss_noise_u8")
+    noise = np.asarray(noise_u8)
+    if noise.dtype != np.uint8 or noise.shape != img.shape:
+        raise ValueError("gauss_noise_u8: noise %s %s is not uint8 %s" % (noise.shape, noise.dtype, img.shape))
+    return np.minimum(img.astype(np.int32) + noise[..., ::-1], 255).astype(np.uint8)
+
+
+def blur_u8(img):
+    """cv2.blur(img, (3, 3)): the 3 x 3 sum under BORDER_REFLECT_101, rounded to the nearest ninth as (2 sum + 9) // 18 (no sum
+    of nine bytes over nine is a tie, and float64, float32 and OpenCV's fixed-point forms agree with it on every sum)"""
+    img = _rgb_u8(img, "blur_u8")
+    h, w = img.shape[:2]
+    ys, xs = _reflect101(np.arange(-1, h + 1), h), _reflect101(np.arange(-1, w + 1), w)
+    p = img.astype(np.int64)[ys][:, xs]
+    total = sum(p[dy:dy + h, dx:dx + w] for dy in range(3) for dx in range(3))
+    return ((2 * total + 9) // 18).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def _hsv_div_tables():
+    i = np.arange(1, 256, dtype=np.float64)
+    sdiv, hdiv = np.zeros(256, dtype=np.int64), np.zeros(256, dtype=np.int64)
+    sdiv[1:] = np.rint((255 << HSV_SHIFT) / (1. * i))
+    hdiv[1:] = np.rint((180 << HSV_SHIFT) / (6. * i))
+    return sdiv, hdiv
+
+
+def rgb_to_hsv_u8(img):
+    """8-bit cv2.COLOR_BGR2HSV of an RGB-ordered image -> [h, w, 3] uint8 H (0 .. 179), S, V: OpenCV's integer path with
+    hsv_shift = 12.  V = max, d = V - min, S = (d sdiv[V] + 2048) >> 12, H0 = g - b where V == r, else b - r + 2 d where V == g,
+    else r - g + 4 d; H = (H0 hdiv[d] + 2048) >> 12 (arithmetic), plus 180 where negative."""
+    c = _rgb_u8(img, "rgb_to_hsv_u8").astype(np.int64)
+    r, g, b = c[..., 0], c[..., 1], c[..., 2]
+    sdiv, hdiv = _hsv_div_tables()
+    V = np.maximum(np.maximum(b, g), r)
+    d = V - np.minimum(np.minimum(b, g), r)
+    S = (d * sdiv[V] + (1 << (HSV_SHIFT - 1))) >> HSV_SHIFT
+    H0 = np.where(V == r, g - b, np.where(V == g, b - r + 2 * d, r - g + 4 * d))
+    H = (H0 * hdiv[d] + (1 << (HSV_SHIFT - 1))) >> HSV_SHIFT
+    H = H + np.where(H < 0, 180, 0)
+    return np.clip(np.stack([H, S, V], axis=-1), 0, 255).astype(np.uint8)
+
+
+_HSV_SECTORS = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])     # (b, g, r) of a sector
+
+
+def hsv_to_rgb_u8(hsv):
+    """8-bit cv2.COLOR_HSV2BGR into an RGB-ordered image: OpenCV's scalar float32 path, every product and difference rounded to
+    float32 on its own (no fused multiply-add).  h = H float32(6 / 180), s = S float32(1 / 255), v = V float32(1 / 255); h =
+    fmod(h, 6), k = floor(h), f = h - k (a sector outside 0 .. 5 is sector 0 with f = 0); t = [v, v (1 - s), v (1 - s f),
+    v (1 - s (1 - f))] and (b, g, r) = t[_HSV_SECTORS[k]]; s == 0 gives b = g = r = v; a byte is rint(x 255) saturated."""
+    c = np.asarray(hsv)
+    if c.dtype != np.uint8 or c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("hsv_to_rgb_u8: an [h, w, 3] uint8 image, got %s %s" % (c.shape, c.dtype))
+    f32, one = np.float32, np.float32(1)
+    h = c[..., 0].astype(f32) * f32(6 / 180)
+    s, v = c[..., 1].astype(f32) * f32(1 / 255), c[..., 2].astype(f32) * f32(1 / 255)
+    h = np.fmod(h, f32(6))
+    k = np.floor(h)
+    f = h - k
+    sector = k.astype(np.int64)
+    outside = (sector < 0) | (sector > 5)
+    sector, f = np.where(outside, 0, sector), np.where(outside, f32(0), f)
+    t = np.stack([v, v * (one - s), v * (one - s * f), v * (one - s * (one - f))])
+    assert t.dtype == np.float32
+    bgr = np.take_along_axis(t, np.moveaxis(_HSV_SECTORS[sector], -1, 0), axis=0)
+    bgr = np.where((s == 0)[None], v[None], bgr)
+    byte = np.clip(np.rint(bgr * f32(255)), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.moveaxis(byte[::-1], 0, -1))
+
+
+def change_hsv_u8(img, h, s, v):
+    """utils.change_hsv: rgb_to_hsv_u8, the three shifts added and clipped to 0 .. 255 (hue as well, as the script does: a hue
+    above 179 then wraps in the return, one below 0 stays 0), hsv_to_rgb_u8.  Written from OpenCV 4.x's scalar path; equality
+    with a cv2 build has not been run, and a vectorised build may use fused multiply-adds and differ by one in a byte."""
+    hsv = rgb_to_hsv_u8(img).astype(np.int64) + np.array([int(h), int(s), int(v)])
+    return hsv_to_rgb_u8(np.clip(hsv, 0, 255).astype(np.uint8))
+
+
+def draw_unet_colour(rng, H, W, crop, np_rng=None):
+    """draw_unet_params with the colour operations kept: the same draws from `rng`, in the same order and count.  Returns
+    (row, colour, skipped).  row: draw_unet_params' dict.  colour: {"hsv": None or (image, h, s, v), "pre": None or (op, value),
+    "post": None or (op, value)}, image 1 = pre, 2 = post, op one of gauss_noise, blur, saturation, brightness, contrast (an
+    image draws one of them at most) and value the factor 0.9 + random() * 0.2, the noise array (draw_unet_noise(np_rng, crop),
+    drawn as the sample reaches it, pre before post) or None.  skipped: the names of what is NOT applied -- clahe_*, elastic_*
+    and, when np_rng is None, gauss_noise_*."""
+    row, drawn = _draw_unet_sample(rng, H, W, crop)
+    colour, skipped = {"hsv": None, "pre": None, "post": None}, []
+    for name, value in drawn:
+        op, im = name.rsplit("_", 1)
+        if op == "change_hsv":
+            colour["hsv"] = (1 if im == "pre" else 2,) + tuple(value)
+        elif op in UNET_COLOUR_NOT_BUILT or (op == "gauss_noise" and np_rng is None):
+            skipped.append(name)
+        else:
+            colour[im] = (op, draw_unet_noise(np_rng, crop) if op == "gauss_noise" else value)
+    return row, colour, skipped
+
+
+def unet_colour_names(colour):
+    """the operations of one sample's colour dict under draw_unet_params' names (change_hsv_pre, blur_post, ..)"""
+    colour = colour or {}
+    names = ["change_hsv_" + ("pre", "post")[colour["hsv"][0] - 1]] if colour.get("hsv") is not None else []
+    return names + ["%s_%s" % (colour[im][0], im) for im in ("pre", "post") if colour.get(im) is not None]
+
+
+def check_unet_colour(colour, crop):
+    """the colour dicts of a batch (draw_unet_colour's; None or a missing key is no operation) as they are; ValueError for an
+    entry that is no dict of hsv, pre, post, an hsv that is no (1 or 2, h, s, v) with integer shifts within +-255, an operation
+    that is none of UNET_COLOUR_OPS, a factor that is no finite number or a noise array that is not [crop, crop, 3] uint8"""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    for n, col in enumerate(colour):
+        if col is None:
+            continue
+        if not isinstance(col, dict) or not set(col) <= {"hsv", "pre", "post"}:
+            raise ValueError("colour[%d]: None or a dict of hsv, pre, post (draw_unet_colour), got %r" % (n, col))
+        c = col.get("hsv")
+        if c is not None and not (isinstance(c, (tuple, list)) and len(c) == 4 and c[0] in (1, 2)
+                                  and all(is_int(v) and abs(v) <= 255 for v in c[1:])):
+            raise ValueError("colour[%d]: hsv %r is no (1 = pre or 2 = post, h, s, v) with shifts within +-255" % (n, c))
+        for im in ("pre", "post"):
+            e = col.get(im)
+            if e is None:
+                continue
+            if not (isinstance(e, (tuple, list)) and len(e) == 2 and isinstance(e[0], str) and e[0] in UNET_COLOUR_OPS):
+                raise ValueError("colour[%d]: %s %r is no (op, value) with op one of %s" % (n, im, e, sorted(UNET_COLOUR_OPS)))
+            op, value = e
+            if op == "gauss_noise":
+                if not (isinstance(value, np.ndarray) and value.dtype == np.uint8 and value.shape == (crop, crop, 3)):
+                    raise ValueError("colour[%d]: the noise of %s is no uint8 array [%d, %d, 3] (draw_unet_noise), got %s"
+                                     % (n, im, crop, crop, getattr(value, "shape", type(value))))
+            elif op == "blur":
+                if value is not None:
+                    raise ValueError("colour[%d]: blur of %s takes no value, got %r" % (n, im, value))
+            elif not (isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool)
+                      and math.isfinite(value)):
+                raise ValueError("colour[%d]: the %s factor %r of %s is no finite number" % (n, op, value, im))
+    return colour
+
+
+def unet_colour_jobs(colour, crop):
+    """(jobs, noise) for dh_xbd_unet_colour_u8 from checked colour dicts: jobs [J, 12] int32 numpy, one row per (sample, image)
+    that drew anything = sample, image (0 pre, 1 post), hsv flag, h, s, v, op code, the factor's float64 bits (low word, high
+    word), the noise plane, 0, 0; noise [K, crop, crop, 3] uint8 (BGR, as drawn) or None.  (None, None) without a job."""
+    rows, planes = [], []
+    for n, col in enumerate(colour):
+        col = col or {}
+        for im in (0, 1):
+            hsv = col.get("hsv")
+            hsv = hsv if hsv is not None and hsv[0] == im + 1 else None
+            e = col.get(("pre", "post")[im])
+            if hsv is None and e is None:
+                continue
+            job = [n, im, int(hsv is not None)] + [int(v) for v in (hsv[1:] if hsv is not None else (0, 0, 0))] + [0] * 6
+            if e is not None:
+                job[6] = UNET_COLOUR_OPS[e[0]]
+                if e[0] == "gauss_noise":
+                    job[9] = len(planes)
+                    planes.append(e[1])
+                elif e[0] != "blur":
+                    job[7:9] = np.array([float(e[1])], dtype=np.float64).view(np.int32).tolist()
+            rows.append(job)
+    if not rows:
+        return None, None
+    return np.array(rows, dtype=np.int32).reshape(-1, ops.XBD_COLOUR_JOB_WORDS), (np.stack(planes) if planes else None)
+
+
+def unet_colour_reference_u8(img6_u8, colour):
+    """The script's colour stage on one sample: img6_u8 [6, S, S] uint8 (unet_reference_u8's img, shift_channels inside) and the
+    sample's colour dict -> [6, S, S] uint8.  Per image the script's order: change_hsv, then the one block operation it drew.
+    clahe and the elastic transform are never applied.  dh_xbd_unet_colour_u8 equals it byte for byte
+    (tests/test_xbd_unet_colour_gpu.py)."""
+    img6 = np.asarray(img6_u8)
+    if img6.dtype != np.uint8 or img6.ndim != 3 or img6.shape[0] != 6:
+        raise ValueError("unet_colour_reference_u8: a [6, S, S] uint8 image pair, got %s %s" % (img6.shape, img6.dtype))
+    check_unet_colour([colour], img6.shape[1])
+    out, colour = img6.copy(), colour or {}
+    for im in (0, 1):
+        a = np.ascontiguousarray(img6[3 * im:3 * im + 3].transpose(1, 2, 0))
+        hsv = colour.get("hsv")
+        if hsv is not None and hsv[0] == im + 1:
+            a = change_hsv_u8(a, *hsv[1:])
+        e = colour.get(("pre", "post")[im])
+        if e is not None:
+            op, value = e
+            a = {"gauss_noise": lambda: gauss_noise_u8(a, value), "blur": lambda: blur_u8(a),
+                 "saturation": lambda: saturation_u8(a, value), "brightness": lambda: brightness_u8(a, value),
+                 "contrast": lambda: contrast_u8(a, value)}[op]()
+        out[3 * im:3 * im + 3] = a.transpose(2, 0, 1)
+    return out
+
+
 class GpuXbdPipeline:
     def __init__(self, pre_u8, post_u8, pre_mask_u8, post_label_u8, files=None):
         """pre_u8, post_u8: [n_src, H, W, 3] uint8 device tensors; pre_mask_u8 (0 / 255) and post_label_u8 (0 .. 4):
@@ -492,6 +764,8 @@ class GpuXbdPipeline:
         self._zero_lbl = None
         self._jitter_ws = None
         self.unet_skipped = collections.Counter()      # unet_batches: the drawn operations of the last epoch that are not built
+        self.unet_applied = collections.Counter()      # ... and, with colour=True, the colour operations that were applied
+        self._colour_ws = None
 
     @classmethod
     def from_image_dir(cls, images_dir, device='cuda:0', files=None):
@@ -629,17 +903,26 @@ class GpuXbdPipeline:
                               if flag and jitter_gen is not None else None)
             yield self.make_batch(ind, crop, params, train, jitter if jitter_gen is not None else None, dilate)
 
-    def make_unet_batch(self, indices, crop, rows, dilate=5):
+    def make_unet_batch(self, indices, crop, rows, dilate=5, colour=None):
         """A training batch of xBD_code/train_unettransformer.py's TrainData, the script that trains DAHiTra proper: rows is one
         draw_unet_params dict per sample (crop, vflip, rot90, reflect-101 shift, cv2.warpAffine rotate / scale, shift_channels),
         applied in ONE launch (ops.xbd_augment_warp, dh_xbd_augment_warp_u8), byte for byte unet_reference_u8.  dilate: the
         script's square(5) dilation and priority rule of lines 262-273 on top (ops.xbd_msk_dilate, one more launch; any odd
         window of 3 .. 31), 0 for the undilated channels.  Returns make_batch's dict; `lbl_msk` is the shared zero tensor, as
-        the script's argmax gives it (channel 0 is set wherever another one is): read it, never write to it.  Not applied: the
-        colour operations and the elastic transform that draw_unet_params reports as skipped.  The script's ValData is
+        the script's argmax gives it (channel 0 is set wherever another one is): read it, never write to it.
+        colour: None, or one draw_unet_colour dict (or None) per sample: the script's colour stage of lines 211-244 --
+        change_hsv, then gauss_noise, cv2.blur, saturation, brightness or contrast -- on the images the warp launch wrote, in
+        place, in two more launches whatever the jobs (ops.xbd_unet_colour, dh_xbd_unet_colour_u8), byte for byte
+        unet_colour_reference_u8.  None, or dicts that hold no operation, is the batch as without the argument: the same bytes
+        and the same launches.  The limits of that contract: change_hsv restates OpenCV 4.x's scalar 8-bit path and equality
+        with a cv2 build has not been run (a vectorised build may fuse multiply-adds and differ by one in a byte); contrast's
+        mean is defined from the exact channel sums (contrast_mean), which can move a byte against numpy's pairwise mean only
+        where a blended value lies within about 1e-11 of an integer.  Not built and never applied: clahe and imgaug's elastic
+        transform, which draw_unet_colour reports as skipped.  The script's ValData is
         make_batch(ind, 256, [[512, 512, 0, 0, 0, 0, 0, 256, 256]] * len(ind), train=False) as it stands.
         ValueError for rows that do not fit (check_unet_rows), a warp whose taps leave the int16 range, indices outside the
-        samples, or a `dilate` that is not 0 or an odd integer of 3 .. 31."""
+        samples, a `dilate` that is not 0 or an odd integer of 3 .. 31, or colour entries that do not match the samples or do
+        not fit (check_unet_colour)."""
         n = len(indices)
         if isinstance(dilate, bool) or not isinstance(dilate, int) or (dilate != 0 and not (3 <= dilate <= ops.XBD_MORPH_MAX_K
                                                                                              and dilate % 2 == 1)):
@@ -650,34 +933,55 @@ class GpuXbdPipeline:
             raise ValueError("rows: %d rows for %d samples" % (len(rows), n))
         if n == 0 or any(not 0 <= int(i) < len(self) for i in indices):
             raise ValueError("indices %r outside the %d samples" % (list(indices), len(self)))
+        jobs = noise = None
+        if colour is not None:
+            colour = check_unet_colour(list(colour), crop)
+            if len(colour) != n:
+                raise ValueError("colour: %d entries for %d samples" % (len(colour), n))
+            jobs, noise = unet_colour_jobs(colour, crop)
         tab = unet_warp_table(rows, crop)
         dev = self.pre.device
         idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int32).to(dev)
         p = torch.from_numpy(unet_param_rows(rows)).to(dev)
         tab = torch.from_numpy(tab).to(dev) if tab is not None else None
         img, msk = ops.xbd_augment_warp(self.pre, self.post, self.post_label, idx, p, tab, crop)
+        if jobs is not None:
+            need = ops.xbd_unet_colour_ws_bytes(len(jobs), crop)
+            if self._colour_ws is None or self._colour_ws.numel() < need:
+                self._colour_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            ops.xbd_unet_colour(img, torch.from_numpy(jobs).to(dev), torch.from_numpy(noise).to(dev) if noise is not None else None,
+                                ws=self._colour_ws)
         if self._zero_lbl is None or self._zero_lbl.shape != (n, crop, crop):
             self._zero_lbl = torch.zeros(n, crop, crop, dtype=torch.uint8, device=dev)
         if dilate:
             msk = ops.xbd_msk_dilate(msk, dilate)
         return {'img': img, 'msk': msk, 'lbl_msk': self._zero_lbl, 'fn': [self.files[int(i)] for i in indices]}
 
-    def unet_batches(self, batch_size, crop, rng, dilate=5):
+    def unet_batches(self, batch_size, crop, rng, dilate=5, colour=False, np_rng=None):
         """one training epoch of xBD_code/train_unettransformer.py's loader: `rng` (a random.Random) shuffles the samples, then
         every sample draws with draw_unet_params, in batch order (the sample order is this loader's own, as in `batches`; a
         sample's draws are the script's).  Yields make_unet_batch's dicts.  `self.unet_skipped` counts, over the epoch, the
-        drawn operations that are not built (collections.Counter of draw_unet_params' names)."""
+        drawn operations that are not applied (collections.Counter of draw_unet_params' names).
+        colour=True draws with draw_unet_colour instead -- the same stream -- and applies the colour operations
+        (make_unet_batch's `colour`); `self.unet_applied` counts them under the same names.  np_rng: the np.random.RandomState
+        gauss_noise draws from (the script draws from numpy's global legacy generator); without one gauss_noise stays skipped."""
         if rng is None:
             raise ValueError("a training epoch draws from `rng` (a random.Random)")
         _, H, W, _ = self.pre.shape
         order = list(range(len(self)))
         rng.shuffle(order)
         self.unet_skipped = collections.Counter()
+        self.unet_applied = collections.Counter()
         for s in range(0, len(order), batch_size):
             ind = order[s:s + batch_size]
-            rows = []
+            rows, colours = [], []
             for _ in ind:
-                row, skipped = draw_unet_params(rng, H, W, crop)
+                if colour:
+                    row, col, skipped = draw_unet_colour(rng, H, W, crop, np_rng)
+                    colours.append(col)
+                    self.unet_applied.update(unet_colour_names(col))
+                else:
+                    row, skipped = draw_unet_params(rng, H, W, crop)
                 rows.append(row)
                 self.unet_skipped.update(skipped)
-            yield self.make_unet_batch(ind, crop, rows, dilate)
+            yield self.make_unet_batch(ind, crop, rows, dilate, colours if colour else None)

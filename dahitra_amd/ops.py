@@ -2511,6 +2511,43 @@ def xbd_augment_warp(pre_u8, post_u8, label_u8, idx, params, tab, crop, out_img=
     return out_img, out_msk
 
 
+XBD_COLOUR_TILE = 32             # the side of dh_xbd_unet_colour_u8's square tile: dh_xbd_unet_colour_tile
+XBD_COLOUR_JOB_WORDS = 12        # sample, image, hsv flag, h, s, v, op, factor bits (low, high), noise plane, 0, 0
+
+
+def xbd_unet_colour_ws_bytes(J, crop):
+    """bytes of the workspace xbd_unet_colour needs for J jobs on crop x crop images: their bytes [J, 3, crop, crop] and one
+    int32 sum per tile and channel"""
+    return _ws_bytes("dh_xbd_unet_colour_ws_bytes", J, crop)
+
+
+def xbd_unet_colour(img, jobs, noise, ws=None):
+    """The colour stage of xBD_code/train_unettransformer.py's TrainData (lines 211-244: change_hsv, then gauss_noise, cv2.blur,
+    saturation, brightness or contrast) on the device, IN PLACE on img fp32 [N, 6, S, S] as xbd_augment_warp wrote it
+    (dh_xbd_unet_colour_u8; the header states the arithmetic).  jobs [J, 12] int32 rows, one per (sample, image) that drew
+    anything, and noise [K, S, S, 3] uint8 or None, both datasets/xbd_pipeline.unet_colour_jobs'.  Two launches whatever the
+    jobs; samples without a row are not touched.  Returns img.  ws: a uint8 device buffer of xbd_unet_colour_ws_bytes(J, S)
+    bytes or more (default: a fresh one).  The kernels stay inside their buffers whatever the rows hold.  ValueError, before
+    any launch, for a wrong rank, dtype, shape or device, non-contiguous storage or a `ws` that does not fit."""
+    what = "xbd_unet_colour"
+    a = _Args(what)
+    a.tensor("img", img, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 6 and t.shape[2] == t.shape[3] and t.numel() > 0,
+             "[N, 6, S, S], not empty")
+    N, _, side, _ = img.shape
+    a.tensor("jobs", jobs, torch.int32, lambda t: t.dim() == 2 and t.shape[1] == XBD_COLOUR_JOB_WORDS and t.shape[0] > 0,
+             "[J, %d], not empty" % XBD_COLOUR_JOB_WORDS)
+    J, K = jobs.shape[0], 0
+    if noise is not None:
+        a.tensor("noise", noise, torch.uint8, lambda t: t.dim() == 4 and tuple(t.shape[1:]) == (side, side, 3) and t.shape[0] > 0,
+                 "[K, %d, %d, 3], not empty" % (side, side))
+        K = noise.shape[0]
+    a.workspace(ws)
+    a.placed()
+    ws = _workspace(what, ws, xbd_unet_colour_ws_bytes(J, side), img.device)
+    _call("dh_xbd_unet_colour_u8", P(img), P(jobs), P(noise), N, side, J, K, P(ws), ws.numel(), S())
+    return img
+
+
 def xbd_fill_holes_ws_bytes(N, H, W):
     """bytes of the workspace xbd_fill_holes needs for [N, H, W]: labels int32 [N, H W] and count [N], xbd_cc_label's own
     workspace, the key uint8 [N, H W] and the marks uint8 [N, H W + 1] (each padded to four bytes)"""

@@ -435,6 +435,30 @@ int dh_xbd_augment_warp_tile_w(void);
 int dh_xbd_augment_warp_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* post_label, const int* idx,
                            const int* params, const int* tab, int N, int H, int W, int S, float* out_img, unsigned char* out_msk,
                            void* stream);
+/* The colour stage of the same script (xBD_code/train_unettransformer.py:211-244) IN PLACE on img fp32 [N][6][S][S], the batch
+ * dh_xbd_augment_warp_u8 wrote: a value decodes to its byte as rint((f + 1) 127) and encodes as x / 127 - 1 again.  jobs [J][12]
+ * int32 (device), one row per (sample, image) that drew anything, in any order, at most one per pair: {sample, image (0 pre,
+ * 1 post), hsv flag, h, s, v, op, the float64 bits of the factor (low word, high word), noise plane, 0, 0}.  First change_hsv if
+ * flagged: 8-bit COLOR_BGR2HSV in OpenCV's integer form (hsv_shift 12: V = max, d = V - min, S = (d sdiv[V] + 2048) >> 12, H0 =
+ * g - b / b - r + 2 d / r - g + 4 d where V is r / g / b, H = (H0 hdiv[d] + 2048) >> 12, + 180 if negative), h, s, v added and
+ * clipped to 0 .. 255 each, and 8-bit COLOR_HSV2BGR in OpenCV's scalar float32 form (h = H (6 / 180), s = S / 255, v = V / 255 as
+ * products with float32 constants; h = fmod(h, 6), k = floor(h), f = h - k; t = {v, v (1 - s), v (1 - s f), v (1 - s (1 - f))}
+ * selected by sector; s == 0 is the grey v; byte = rint(255 x), saturated; every operation rounded on its own).  Then op: 0 none;
+ * 1 gauss_noise, min(byte + noise, 255) with noise [K][S][S][3] uint8 in the script's B, G, R order; 2 cv2.blur(3 x 3),
+ * (2 sum + 9) / 18 of the window under BORDER_REFLECT_101; 3 saturation, 4 brightness, 5 contrast = clip(byte * factor +
+ * (1 - factor) * gs, 0, 255) in float64, truncated, with gs = (0.114 b + 0.587 g) + 0.299 r of the pixel, 0, or that grey of the
+ * exact channel sums over S * S.  No operation is contracted into a fused multiply-add.  Two launches whatever the jobs; samples
+ * without a row are not touched; the result is deterministic.  The sample and noise indices are clamped, the image is one bit,
+ * the shifts are clamped to +-255 and an unknown op is none: no table content makes the kernels read or write outside img, noise
+ * and the workspace.  workspace: device memory, 4-byte aligned, dh_xbd_unet_colour_ws_bytes(J, S) bytes (the bytes of the jobs'
+ * images and one integer sum per tile and channel).
+ * Refused (nothing is written, non-zero, dh_last_error begins with xbd_unet_colour): a null img, jobs or workspace, noise NULL
+ * with K > 0 or not NULL with K == 0, N < 1, S < 1 or > 4096, J < 1 or > 65535, K < 0, a workspace that is too small or not
+ * aligned.  dh_xbd_unet_colour_tile: the side of a workgroup's square tile. */
+int dh_xbd_unet_colour_tile(void);
+int dh_xbd_unet_colour_ws_bytes(int J, int S, long* bytes);
+int dh_xbd_unet_colour_u8(float* img, const int* jobs, const unsigned char* noise, int N, int S, int J, int K, void* workspace,
+                          long workspace_bytes, void* stream);
 int dh_nchw_to_nhwc(int dtype, const float* src, void* dst, int N, int C, long HW, int CP, void* stream);
 /* data gradient of the class head (3x3 / s1 / p1, 32 -> n_class <= 8 channels; help_funcs.py:13-14, networks.py:1247):
  * dy [N][H][W][CP] (CP = 8 bf16 / 4 or 8 fp32 channels per pixel, the first NC real), w_oihw [NC][32][3][3] fp32,
