@@ -669,3 +669,89 @@ class GraphedXbdStep(GraphedTrainStep):
             ops.scale_into(grad, self._inv_world, grad)
         xbd.clip_grad_norm_(self.net.parameters(), self.max_norm)
         self.opt.step()
+
+
+class GraphedXbdUnetStep(GraphedXbdStep):
+    """The step of xBD_code/train_unettransformer.py:436-481, the script that trains DAHiTra proper, as one HIP graph: forward of
+    the 6-channel model, its loss (models/xbd.unet_loss: five ComboLoss terms weighted 0.1, 0.1, 0.6, 0.3, 1 plus 8 * the
+    class-weighted cross-entropy of the masked logits) at engine level, backward, NO gradient clip (commented out at line 480)
+    and the hand-rolled AdamW.  msks are the loader's uint8 bytes and stay bytes: the loss kernels read them as they lie.
+
+        step = GraphedXbdUnetStep(net, xbd.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-6, capturable=True), imgs, msks, lbl_msk)
+        loss = step(imgs, msks, lbl_msk)          # step.parts: the static [8] tensor of ops.XBD_UNET_PARTS, valid after every replay
+
+    labels: 'lbl_msk' (the script as executed; lbl_msk uint8 [B, H, W] is needed) or 'damage' (the label is derived from msks in
+    the kernel; lbl_msk is neither kept nor copied).  A scheduler's learning rate reaches the replay through opt.sync_hyper, as in
+    the parent.  ValueError for a label mode, dtype or shape that does not fit, before anything is recorded."""
+
+    def __init__(self, net, opt, imgs, msks, lbl_msk=None, labels='lbl_msk', warmup=3):
+        what = "GraphedXbdUnetStep"
+        if labels not in ops.XBD_UNET_LABELS:
+            raise ValueError("%s: labels %r is not one of %s" % (what, labels, sorted(ops.XBD_UNET_LABELS)))
+        if labels == 'lbl_msk' and lbl_msk is None:
+            raise ValueError("%s: labels='lbl_msk' reads lbl_msk, which is None" % what)
+        a = ops._Args(what, cpu_error=True)
+        B, _, H, W = a.tensor("imgs", imgs, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 6 and t.numel() > 0,
+                              "[B, 6, H, W], not empty").shape
+        a.tensor("msks", msks, torch.uint8, (B, 5, H, W), "[%d, 5, %d, %d] like imgs" % (B, H, W))
+        if labels == 'lbl_msk':
+            a.tensor("lbl_msk", lbl_msk, torch.uint8, (B, H, W), "[%d, %d, %d] like imgs" % (B, H, W))
+        a.placed()
+        self.labels, self.parts = labels, None
+        GraphedTrainStep.__init__(self, net, opt, imgs, lbl_msk if labels == 'lbl_msk' else None, msks, warmup=warmup)
+
+    def _set_inputs(self, imgs, lbl_msk, msks):
+        from .models import xbd
+        self.a, self.lab = imgs.clone(), msks.clone()
+        self.lbl = lbl_msk.clone() if lbl_msk is not None else None
+        self._w = xbd.unet_weights_dev(imgs.device)        # made here: no host-to-device copy inside the capture
+
+    def _copy_inputs(self, imgs, msks, lbl_msk=None):
+        self.a.copy_(imgs, non_blocking=True)
+        self.lab.copy_(msks, non_blocking=True)            # bytes to bytes
+        if self.lbl is not None and lbl_msk is not None:
+            self.lbl.copy_(lbl_msk, non_blocking=True)
+
+    def _eager_body(self, include_opt):
+        from .models import xbd
+        self.net.zero_grad()
+        logits = self.net(self.a)
+        self.logits = logits.detach()
+        loss, self.parts = xbd.unet_loss(logits, self.lab, self.lbl, self.labels, want_parts=True)
+        loss.backward()
+        if include_opt:
+            self.opt.step()
+        return loss.detach()
+
+    def _body(self, include_opt):
+        """the one-graph step at engine level: the kernels of `_eager_body` without what autograd adds around them (the fill of
+        the upstream gradient and the copies at its boundary).  DAHITRA_GRAPH_AUTOGRAD=1 switches back to the autograd step."""
+        if os.environ.get("DAHITRA_GRAPH_AUTOGRAD") == "1":
+            return self._eager_body(include_opt)
+        net = self.net
+        logits = self._forward_split()
+        bwd = net._engine.take_backward()
+        self.logits = logits
+        loss, dl = self._loss_and_grad(logits)
+        net._arena.grad.zero_()
+        net._engine.backward(dl, bwd)
+        net._bind_grad_views()           # the optimizer skips parameters without a .grad, as torch does
+        if include_opt:
+            self.opt.step()
+        return loss
+
+    def _loss_and_grad(self, logits):
+        """the script's loss and its gradient at engine level: two launches forward, one backward, the masks read as bytes"""
+        from .models import xbd
+        lo = logits.float().contiguous()
+        loss, self.parts, sums = ops.xbd_unet_loss_fwd(lo, self.lab, self.lbl, self.labels, self._w, 1.0, 8.0, xbd.UNET_CE_SCALE)
+        return loss, ops.xbd_unet_loss_bwd(lo, self.lab, self.lbl, self.labels, sums, self._w, None, 1.0, 8.0, xbd.UNET_CE_SCALE)
+
+    def _update(self):
+        """mean over the ranks, then the hand-rolled AdamW: the script does not clip"""
+        if self.world > 1:
+            _, grad = self.net.flat_params()
+            if getattr(self, "_inv_world", None) is None:
+                self._inv_world = torch.tensor([1.0 / self.world], device=grad.device)
+            ops.scale_into(grad, self._inv_world, grad)
+        self.opt.step()

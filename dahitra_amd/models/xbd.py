@@ -5,6 +5,12 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
         net(x) with ONE [B, 6, H, W] tensor (pre | post), logits [B, 5, H, W]; built at xBD_code/train.py:44-45
     ComboLoss(weights, per_image=False)               xBD_code/losses.py:95-126   (dice + focal on the sigmoid)
     xbd_loss(out, msks)                               xBD_code/train.py:348-353   (the five weighted channel losses)
+    unet_loss(out, msks, lbl_msk, labels)             xBD_code/train_unettransformer.py:438-456 (five ComboLoss terms + 8 * the
+        class-weighted cross-entropy of the logits masked by lbl_msk > 0; uint8 masks, one pass; labels='damage' derives the label)
+    unet_scheduler(optimizer)                         train_unettransformer.py:536      (MultiStepLR, gamma 0.6)
+    unet_val_batches(pipe, batch_size, crop)          train_unettransformer.py:288-352  (ValData: the fixed crop at (512, 512))
+    train_epoch_unet(current_epoch, model, optimizer, scheduler, batches)   train_unettransformer.py:421-486 (no clip; the meters
+        Loss / loss2 / loss3 / Dice from ONE host read per epoch; `seg_loss`, `ce_loss` and `scaler` are not arguments here)
     clip_grad_norm_(parameters, max_norm)             torch.nn.utils.clip_grad_norm_ as called at train.py:373
     AdamW(params, lr, weight_decay)                   xBD_code/adamw.py:6-86      (hand-rolled; eps before bias correction)
     validate(model, data_loader)                      xBD_code/train.py:247-290   (dice of the localisation + harmonic F1)
@@ -26,7 +32,7 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
         damage class per building by vote, and the building-level confusion and F1 against the ground truth
     dilate / erode / opening / closing / fill_holes / clean_footprint   no counterpart: square-window morphology and hole
         filling of a footprint before its buildings are counted (scipy.ndimage's binary_* functions are the oracle)
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_ensemble.hip, csrc/xbd_visual.hip,
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_unet_loss.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_ensemble.hip, csrc/xbd_visual.hip,
 csrc/xbd_buildings.hip, csrc/xbd_morph.hip + the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
@@ -39,6 +45,11 @@ from ..optim import AdamW as _ArenaAdamW
 from .networks import CDNet
 
 CHANNEL_WEIGHTS = (0.05, 0.2, 0.8, 0.7, 0.4)          # xBD_code/train.py:353
+UNET_CHANNEL_WEIGHTS = (0.1, 0.1, 0.6, 0.3, 1.0)      # xBD_code/train_unettransformer.py:456
+UNET_CE_WEIGHTS = (0.01, 0.10, 1.0, 0.80, 1.0)        # ... :563
+UNET_CE_SCALE = 8.0                                   # ... :456 (loss5 * 8)
+UNET_MILESTONES = (5, 11, 17, 23, 29, 33, 47, 50, 60, 70, 90, 110, 130, 150, 170, 180, 190)      # ... :536
+UNET_GAMMA = 0.6
 _weights = {}
 
 
@@ -130,6 +141,60 @@ def xbd_loss(out, msks, channel_weights=CHANNEL_WEIGHTS, dice=1.0, focal=8.0, wa
         w = _weights[key] = torch.tensor(key[1], dtype=torch.float32, device=out.device)
     loss, channel = _Combo.apply(out.float().contiguous(), msks.float().contiguous(), w, float(dice), float(focal))
     return (loss, channel) if want_channels else loss
+
+
+# ---- loss of xBD_code/train_unettransformer.py (lines 438-461, 562-564) --------------------------------------
+class _UnetLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, msks, lbl, labels, weights_dev, dice_w, focal_w, ce_w):
+        loss, parts, sums = ops.xbd_unet_loss_fwd(logits, msks, lbl, labels, weights_dev, dice_w, focal_w, ce_w)
+        ctx.save_for_backward(logits, msks, lbl, sums, weights_dev)
+        ctx.how = (labels, dice_w, focal_w, ce_w)
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, dloss, _dparts):
+        logits, msks, lbl, sums, weights_dev = ctx.saved_tensors
+        labels, dice_w, focal_w, ce_w = ctx.how
+        up = dloss.detach().to(torch.float32).reshape(1).contiguous()
+        return (ops.xbd_unet_loss_bwd(logits, msks, lbl, labels, sums, weights_dev, up, dice_w, focal_w, ce_w),) + (None,) * 7
+
+
+def unet_weights_dev(device, channel_weights=UNET_CHANNEL_WEIGHTS, ce_weights=UNET_CE_WEIGHTS):
+    """the 5 channel weights and the 5 class weights as ONE cached device tensor [10], the form ops.xbd_unet_loss_fwd takes (no
+    host-to-device copy inside a HIP-graph capture).  ValueError unless both hold 5 numbers."""
+    key = (str(device), tuple(float(v) for v in channel_weights), tuple(float(v) for v in ce_weights))
+    if len(key[1]) != 5 or len(key[2]) != 5:
+        raise ValueError("unet_loss: channel_weights %r and ce_weights %r must hold 5 numbers each" % (key[1], key[2]))
+    w = _weights.get(key)
+    if w is None:
+        w = _weights[key] = torch.tensor(key[1] + key[2], dtype=torch.float32, device=device)
+    return w
+
+
+def unet_loss(out, msks, lbl_msk=None, labels='lbl_msk', channel_weights=UNET_CHANNEL_WEIGHTS, ce_weights=UNET_CE_WEIGHTS,
+              dice=1.0, focal=8.0, ce=UNET_CE_SCALE, want_parts=False):
+    """The loss of train_unettransformer.py:438-456 in one pass over the pixels (ops.xbd_unet_loss_fwd; one more for the gradient):
+        sum_c channel_weights[c] * ComboLoss{dice, focal}(out[:, c], msks[:, c])
+        + ce * CrossEntropyLoss(weight=ce_weights)(out * (y > 0), y)
+    out: logits [B, 5, H, W]; msks: uint8 [B, 5, H, W] AS THE LOADER YIELDS THEM (no float copy is made; another dtype is
+    refused).  labels='lbl_msk' is the script as executed: y = lbl_msk, uint8 [B, H, W] -- which its TrainData makes zero at
+    every pixel, so the cross-entropy term is the constant ln 5 and has no gradient.  labels='damage' is the term as intended
+    ("ce loss only on building"): y = the first set channel among 1 .. 4 of msks, 0 where none is set; lbl_msk is not read.
+    want_parts: also return the device tensor parts [8] = ops.XBD_UNET_PARTS: the five channel losses, the cross-entropy, the
+    script's Dice meter (line 460: on channel 0 AFTER the in-place masking, so 0.5-sigmoids wherever y is 0) and the number of
+    label bytes above 4 (they add nothing to the cross-entropy and get no gradient from it; torch raises IndexError there,
+    train_epoch_unet does so at the end of the epoch).  No host synchronisation."""
+    if not (torch.is_tensor(out) and out.is_cuda):
+        raise _lib.HipLibraryError("dahitra_amd xBD loss runs on MI355X only (no CPU fallback)")
+    w = unet_weights_dev(out.device, channel_weights, ce_weights)
+    lbl = lbl_msk.contiguous() if torch.is_tensor(lbl_msk) and labels != 'damage' else None
+    if labels == 'lbl_msk' and lbl is None:
+        raise ValueError("unet_loss: labels='lbl_msk' reads lbl_msk, which is %r" % (lbl_msk,))
+    loss, parts = _UnetLoss.apply(out.float().contiguous(), msks.contiguous() if torch.is_tensor(msks) else msks, lbl, labels, w,
+                                  float(dice), float(focal), float(ce))
+    return (loss, parts) if want_parts else loss
 
 
 # ---- clip + optimizer ------------------------------------------------------------------------------------
@@ -445,6 +510,98 @@ def evaluate_val_sweep(batches, best_score, model, optimizer, path, current_epoc
     model = model.eval()
     thr, d = validate_sweep(model, batches, thresholds, select=select, graph=graph).best()
     return _keep_best(d, best_score, model, optimizer, path, current_epoch, thr)
+
+
+# ---- the epoch of xBD_code/train_unettransformer.py (lines 421-486, 532-575) ----------------------------------------
+def unet_scheduler(optimizer):
+    """lr_scheduler.MultiStepLR(optimizer, milestones=[5, 11, 17, 23, 29, 33, 47, 50, 60, ...], gamma=0.6) of line 536"""
+    return torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=list(UNET_MILESTONES), gamma=UNET_GAMMA)
+
+
+def unet_val_batches(pipe, batch_size=16, crop=256):
+    """The script's ValData (lines 288-352) from a GpuXbdPipeline: the samples in order, the fixed crop at x0 = y0 = 512, no
+    augmentation, ValData's masks (train=False) -- what validate / evaluate_val take.  The script's val_batch_size is 16 and its
+    DataLoader keeps the ragged last batch."""
+    for s in range(0, len(pipe), batch_size):
+        ind = list(range(s, min(s + batch_size, len(pipe))))
+        yield pipe.make_batch(ind, crop, [[512, 512, 0, 0, 0, 0, 0, crop, crop]] * len(ind), train=False)
+
+
+def _unet_train_step(model, optimizer, first, labels, graph):
+    """run(batch) -> (loss, parts) device tensors for the batches of one epoch: batches of the first batch's shape replay the
+    model's recorded GraphedXbdUnetStep (kept on the model per shape, label mode, optimizer and device), any other shape -- a
+    ragged last batch -- and graph=False take the eager step"""
+    _device_u8("training", first['img'], first['msk'])
+
+    def eager(batch):
+        model.zero_grad()
+        loss, parts = unet_loss(model(batch['img']), batch['msk'], batch['lbl_msk'], labels, want_parts=True)
+        loss.backward()
+        optimizer.step()
+        return loss.detach(), parts
+    if not graph:
+        return eager
+    from ..graph import GraphedXbdUnetStep
+    imgs = first['img']
+    model._ensure_arena(imgs.device)
+    step = _kept_step(model, '_xbd_unet_steps', (tuple(imgs.shape), labels, id(optimizer), str(imgs.device)),
+                      lambda: GraphedXbdUnetStep(model, optimizer, imgs, first['msk'], first['lbl_msk'], labels),
+                      lambda step: step._generation == model._arena.generation and step.opt is optimizer)
+
+    def replay(batch):
+        if tuple(batch['img'].shape) != tuple(imgs.shape):
+            return eager(batch)
+        return step(batch['img'], batch['msk'], batch['lbl_msk']), step.parts
+    return replay
+
+
+def train_epoch_unet(current_epoch, model, optimizer, scheduler, batches, labels='lbl_msk', graph=True):
+    """train_epoch of xBD_code/train_unettransformer.py:421-486 on the device.  batches: dicts {'img' fp32 [B, 6, H, W], 'msk' uint8
+    [B, 5, H, W], 'lbl_msk' uint8 [B, H, W]} as GpuXbdPipeline.unet_batches yields them.  Per batch: forward, unet_loss, backward,
+    NO gradient clip (commented out at line 480) and the hand-rolled AdamW -- with graph=True one replay of a GraphedXbdUnetStep
+    (optimizer: AdamW(..., capturable=True)).  labels: unet_loss's ('lbl_msk': the script as executed; 'damage': its
+    cross-entropy term as intended).  Every step's loss and parts go into a row of a device buffer by asynchronous device copies;
+    the host reads ONCE, when the epoch is over, where the script reads four .item() values per step.  The meters are
+    AverageMeter's means, weighted by the batch size: Loss, loss2 (channel 2) and loss3 (channel 3) as the script passes them,
+    Dice.  Then scheduler.step(), and the script's final line
+        epoch: ..; lr ..; Loss ..; loss2 ..; Dice ..
+    IndexError if the epoch counted a label byte above 4 (torch raises it at that step), before the scheduler moves.
+    Returns {'loss', 'loss2', 'loss3', 'dice', 'ce', 'lr', 'steps', 'samples'}.
+    Deliberate differences: the printed lr is optimizer.param_groups[-1]['lr'], the rate the next epoch runs at -- the script's
+    deprecated scheduler.get_lr() reports that rate times 0.6 once more at a milestone epoch; amp.autocast and GradScaler (fp16,
+    a dynamic loss scale, skipped steps) are not reproduced: the net's compute_dtype decides the precision, nothing is scaled."""
+    if labels not in ops.XBD_UNET_LABELS:
+        raise ValueError("train_epoch_unet: labels %r is not one of %s" % (labels, sorted(ops.XBD_UNET_LABELS)))
+    model.train()
+    run, rows, sizes = None, None, []
+    for batch in batches:
+        if run is None:
+            run = _unet_train_step(model, optimizer, batch, labels, graph)
+        loss, parts = run(batch)
+        n = len(sizes)
+        if rows is None:
+            rows = torch.zeros(64, 9, dtype=torch.float32, device=loss.device)
+        if n == rows.shape[0]:                # an iterator does not say how long it is: the buffer doubles, on the device
+            rows = torch.cat([rows, torch.zeros_like(rows)])
+        rows[n, 0:1].copy_(loss.reshape(1), non_blocking=True)
+        rows[n, 1:].copy_(parts, non_blocking=True)
+        sizes.append(int(batch['img'].shape[0]))
+    if rows is None:
+        raise ValueError("train_epoch_unet: no batches")
+    host = rows[:len(sizes)].cpu().numpy().astype(np.float64)          # the epoch's one read
+    bad = int(host[:, 8].sum())
+    if bad:
+        raise IndexError("train_epoch_unet: %d label bytes above 4 in epoch %s (steps %s); CrossEntropyLoss has 5 classes"
+                         % (bad, current_epoch, np.nonzero(host[:, 8])[0].tolist()))
+    w = np.asarray(sizes, dtype=np.float64)
+    avg = lambda col: float((host[:, col] * w).sum() / w.sum())        # AverageMeter: sum(val * n) / sum(n)
+    meters = {'loss': avg(0), 'loss2': avg(3), 'loss3': avg(4), 'dice': avg(7), 'ce': avg(6)}
+    scheduler.step()
+    lr = optimizer.param_groups[-1]['lr']
+    print("epoch: {}; lr {:.7f}; Loss {:.4f}; loss2 {:.4f}; Dice {:.4f}".format(current_epoch, lr, meters['loss'], meters['loss2'],
+                                                                              meters['dice']))
+    meters.update(lr=lr, steps=len(sizes), samples=int(w.sum()))
+    return meters
 
 
 # ---- prediction (xBD_code/predict_test_cls.py:58-97) --------------------------------------------------------

@@ -1924,6 +1924,67 @@ def adamw_xbd_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weig
           step, P(grad_scale_dev), S())
 
 
+# ---- loss of xBD_code/train_unettransformer.py's step (csrc/xbd_unet_loss.hip) ---------------------------
+XBD_UNET_LABELS = {"lbl_msk": 0, "damage": 1}
+# lanes of one forward grid pass (dh_xbd_unet_loss_grid_pass): that many pixels where H * W is no multiple of 4 (one pixel per
+# lane), four times as many where it is; a batch beyond it is strided over
+XBD_UNET_LOSS_PASS = 1024 * 256
+XBD_UNET_PARTS = ("loss0", "loss1", "loss2", "loss3", "loss4", "ce", "dice", "bad_labels")
+
+
+def _xbd_unet_loss_args(what, logits, msk, lbl, labels, weights_dev, extra=()):
+    """the tensors of xbd_unet_loss_fwd / _bwd, refused before any launch: ValueError for a label mode, dtype or shape that does not
+    fit and for mixed devices, HipLibraryError when everything is on the CPU.  Returns label_mode, B, H, W"""
+    if labels not in XBD_UNET_LABELS:
+        raise ValueError("%s: labels %r is not one of %s" % (what, labels, sorted(XBD_UNET_LABELS)))
+    if labels == "lbl_msk" and lbl is None:
+        raise ValueError("%s: labels='lbl_msk' reads lbl, which is None" % what)
+    a = _Args(what, cpu_error=True)
+    B, _, H, W = a.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 5 and t.numel() > 0,
+                          "[B, 5, H, W], not empty").shape
+    a.tensor("msk", msk, torch.uint8, (B, 5, H, W), "[%d, 5, %d, %d] like logits" % (B, H, W))
+    if lbl is not None:
+        a.tensor("lbl", lbl, torch.uint8, (B, H, W), "[%d, %d, %d] like logits" % (B, H, W))
+    a.tensor("weights_dev", weights_dev, torch.float32, (10,), "[10]: 5 channel weights, 5 class weights")
+    for name, t, shape in extra:
+        if t is not None:
+            a.tensor(name, t, torch.float32, lambda t, n=math.prod(shape): t.numel() == n, str(list(shape)))
+    a.placed()
+    return XBD_UNET_LABELS[labels], B, H, W
+
+
+def xbd_unet_loss_fwd(logits, msk, lbl, labels, weights_dev, dice_weight=1.0, focal_weight=8.0, ce_weight=8.0):
+    """The loss of xBD_code/train_unettransformer.py:438-461 in one pass and a finalize launch (dh_xbd_unet_loss_fwd): five weighted
+    ComboLoss{dice, focal} terms + ce_weight * the class-weighted cross-entropy of the logits multiplied by (y > 0).
+    logits fp32 [B, 5, H, W]; msk uint8 [B, 5, H, W], the loader's bytes; labels 'lbl_msk': y = lbl, uint8 [B, H, W]; labels
+    'damage': y = the first set channel among 1 .. 4 of msk (lbl is not read and may be None); weights_dev fp32 [10] = the 5
+    channel weights, then the 5 class weights.  Returns (loss [], parts [8] = XBD_UNET_PARTS, sums [24] for xbd_unet_loss_bwd),
+    all on the device; nothing is read by the host."""
+    mode, B, H, W = _xbd_unet_loss_args("xbd_unet_loss_fwd", logits, msk, lbl, labels, weights_dev)
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty(8, dtype=torch.float32, device=dev)
+    sums = torch.empty(24, dtype=torch.float32, device=dev)
+    need = _ws_bytes("dh_xbd_unet_loss_workspace_size")
+    ws = workspace(need, dev)
+    _call("dh_xbd_unet_loss_fwd", P(logits), P(msk), P(lbl if mode == 0 else None), mode, B, H * W, P(weights_dev),
+          float(dice_weight), float(focal_weight), float(ce_weight), P(sums), P(parts), P(loss), P(ws), ws.numel(), S())
+    return loss, parts, sums
+
+
+def xbd_unet_loss_bwd(logits, msk, lbl, labels, sums, weights_dev, upstream=None, dice_weight=1.0, focal_weight=8.0, ce_weight=8.0):
+    """dloss / dlogits of xbd_unet_loss_fwd, one pass (dh_xbd_unet_loss_bwd): fp32 [B, 5, H, W].  sums: the forward's third result;
+    upstream: a device scalar fp32 [1] that multiplies the gradient, or None for 1."""
+    if sums is None:
+        raise ValueError("xbd_unet_loss_bwd: sums is None; it is xbd_unet_loss_fwd's third result")
+    mode, B, H, W = _xbd_unet_loss_args("xbd_unet_loss_bwd", logits, msk, lbl, labels, weights_dev,
+                                        (("sums", sums, (24,)), ("upstream", upstream, (1,))))
+    dl = torch.empty_like(logits)
+    _call("dh_xbd_unet_loss_bwd", P(logits), P(msk), P(lbl if mode == 0 else None), mode, P(sums), P(weights_dev), P(upstream),
+          float(dice_weight), float(focal_weight), float(ce_weight), B, H * W, P(dl), S())
+    return dl
+
+
 # ---- xBD validation count (csrc/xbd_eval.hip) -----------------------------------------------------------
 XBD_VAL_SELECT = {"reference": 0, "building": 1}
 

@@ -787,6 +787,30 @@ int dh_adamw_xbd_step(float* param, const float* grad, float* exp_avg, float* ex
 int dh_adamw_xbd_step_graph(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float* hyper_dev,
                             int* step_dev, const float* grad_scale_dev, void* stream);
 
+/* ---- loss of xBD_code/train_unettransformer.py's step (lines 438-461; csrc/xbd_unet_loss.hip) -------------------
+ * loss = sum_c cw_c * ComboLoss{dice, focal}(logits[:, c], msk[:, c]) + ce_weight * CrossEntropyLoss(weight=w)(z, y) with
+ * z = logits * (y > 0), in ONE pass over the pixels plus a finalize launch.  logits fp32 [B][5][HW]; msk uint8 [B][5][HW]
+ * (bytes 0 / 1, the loader's); label_mode 0: y = lbl [B][HW] uint8; label_mode 1 ("damage"): y = the first set channel among
+ * 1 .. 4 of msk, 0 if none, and lbl may be null.  weights_dev: the 5 channel weights cw, then the 5 class weights w.
+ * The combo sums and channel losses are dh_combo_loss_fwd's float expressions; ce = (sum w_y nll) / (sum w_y) over ALL pixels
+ * (torch's weighted mean), nll = logsumexp(z) - z_y.  A label byte above 4 adds nothing to the two cross-entropy sums, has no
+ * cross-entropy gradient and is counted.  fwd writes loss_out [1], parts_out [8] = the five channel losses, ce, the script's
+ * Dice meter (2 I + 1e-6) / (S + T + 1e-6) on sigmoid(z_0), the bad-label count; sums_out [24] = [c][4] combo sums, sum w_y,
+ * sum w_y nll, the meter's I and S (what bwd reads).  Sums in fp64 through a fixed tree: deterministic.  The 4-pixel form
+ * (16-byte logit loads) runs where HW % 4 == 0 and the planes are aligned, the one-pixel form otherwise.
+ * dh_xbd_unet_loss_grid_pass: the lanes of one forward grid pass (pixels in the one-pixel form, quads in the other).
+ * bwd: dlogits [B][5][HW] = upstream * (cw_c * combo gradient + ce_weight * [y > 0] * w_y / (sum w_y) * (softmax(z)_c - [c == y])),
+ * upstream_dev a device scalar or NULL for 1.  Refused (nothing is launched): a null pointer, an empty input, label_mode
+ * outside {0, 1}, label_mode 0 without lbl, a workspace smaller than dh_xbd_unet_loss_workspace_size answers. */
+int dh_xbd_unet_loss_workspace_size(long* bytes);
+int dh_xbd_unet_loss_grid_pass(void);
+int dh_xbd_unet_loss_fwd(const float* logits, const unsigned char* msk, const unsigned char* lbl, int label_mode, int B, long HW,
+                         const float* weights_dev, float dice_weight, float focal_weight, float ce_weight, float* sums_out,
+                         float* parts_out, float* loss_out, void* workspace, long workspace_bytes, void* stream);
+int dh_xbd_unet_loss_bwd(const float* logits, const unsigned char* msk, const unsigned char* lbl, int label_mode,
+                         const float* sums, const float* weights_dev, const float* upstream_dev, float dice_weight,
+                         float focal_weight, float ce_weight, int B, long HW, float* dlogits, void* stream);
+
 /* ---- xBD validation count (xBD_code/train.py:258-279; csrc/xbd_eval.hip) -------------------------------
  * One pass over logits [B][5][H][W] fp32: s = sigmoid in fp32, loc = s[0] > thr (strict, in float32), pred = argmax(s[1:]) * loc
  * with the first maximum of the fp32 sigmoids winning.  msk0: image j's ground-truth localisation plane [H][W] (nonzero = set) at
