@@ -20,7 +20,11 @@ torch.distributed the step is TWO graphs around the exchange:
 DAHITRA_OVERLAP=auto (default) takes this form only where the all-reduce it hides is modelled longer than the form costs
 (parallel.split_offset: world size and tail bytes; 1 forces it, 0 / DAHITRA_NO_OVERLAP=1 gives one graph, then one all-reduce and
 the update).  The warm-up steps torch needs before capture are
-undone (parameters, BN buffers and optimizer state are restored), so the first graphed step is step 1."""
+undone (parameters, BN buffers and optimizer state are restored), so the first graphed step is step 1.
+
+How launches become a graph is written once, `_Recorded._capture`, for the train steps (GraphedTrainStep and the two xBD steps
+that derive from it) and for the recorded evaluation steps (`_RecordedEval`).  A train step is its hooks: `_forward_split`,
+`_loss_and_grad`, `_eager_body` and `_update`, the class attributes INPUTS and ENGINE_LEVEL, and `max_norm`."""
 import os
 
 import torch
@@ -30,48 +34,24 @@ from . import ops, parallel
 from .models import losses
 
 
-class GraphedTrainStep:
-    CHECK_EVERY = 64          # replays between two read-backs of the persistent-BatchNorm error words
+class _Recorded:
+    """How launches become a HIP graph, for train and evaluation steps alike.  A subclass says what the warm-up disturbs
+    (`_snapshot` -> saved, `_restore(saved)`) and sets the nets' mode; `stale()` tells whether a replay is still safe."""
 
-    def __init__(self, net, opt, a, b, lab, warmup=3, confusion=None):
-        """confusion: an int64 [n_class, n_class] device tensor; the recorded step then also counts arg-max(logits) against
-        the labels into it (dh_confusion_matrix, one more kernel inside the graph: the running metric of the reference's
-        trainer without any per-step launch or host read)"""
-        if not getattr(opt, "capturable", False):
-            raise ValueError("GraphedTrainStep needs dahitra_amd.optim.AdamW(..., capturable=True)")
-        self.net, self.opt = net, opt
-        self.confusion = confusion
-        self.world = dist.get_world_size() if dist.is_initialized() else 1
-        self.exchange = parallel.exchange_enabled()      # gradient all-reduce + AdamW after the replay
-        self.split_off = None                            # arena offset where the overlapped (two-graph) form splits
-        self.persist_bn_launches = None                  # (graph 1, graph 2) counts of the overlapped form
-        self._set_inputs(a, b, lab)
-        net._ensure_arena(a.device)
-        # ---- snapshot the training state, warm up eagerly on a side stream, restore -------------------
-        flat0 = net._arena.flat.clone()
-        bufs0 = [t.clone() for t in net.buffers()]
-        conf0 = confusion.clone() if confusion is not None else None
-        opt0 = opt.snapshot_flat_state(net)
+    def _capture(self, nets, device, warm, bodies, warmup):
+        """`warmup` times `warm()` eagerly on a side stream, the state put back, then bodies[0]() captured into self.graph and --
+        the overlapped train step -- bodies[1]() into self.graph2, which shares its pool.  Returns what the bodies returned
+        (their static outputs)."""
+        self._nets = list(nets)
+        saved = self._snapshot()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        split = self.exchange and self._can_split()
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                if split:      # the same launches the two captures make (the split backward has its own reduce tables)
-                    self._split_first()
-                    self._second()
-                    self._update()
-                else:
-                    self._body(include_opt=True)
+                warm()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        net._arena.flat.copy_(flat0)
-        for t, t0 in zip(net.buffers(), bufs0):
-            t.copy_(t0)
-        opt.restore_flat_state(net, opt0)     # the optimizer keeps what it carried (e.g. a resumed checkpoint)
-        if confusion is not None:
-            confusion.copy_(conf0)
-        # ---- capture ---------------------------------------------------------------------------------
+        self._restore(saved)
         # A captured graph holds RAW pointers: the shared scratch workspace, the weight-gradient plan's slabs and
         # job table, the packed-weight buffers.  ops.pin_captured_buffers() makes every buffer the capture touched
         # immutable for the life of the process (a later, larger eager call allocates a NEW buffer instead of
@@ -81,38 +61,102 @@ class GraphedTrainStep:
         # (kept for the life of the step: released, PyTorch's stream pool could hand its handle to a later torch.cuda.Stream(),
         # whose eager launches would then look up -- and scribble over -- the workspace the recorded graph reads and writes)
         cs = self._capture_stream = torch.cuda.Stream()
-        ops.rekey_workspace(a.device, s, cs)
+        ops.rekey_workspace(device, s, cs)
         self.graph = torch.cuda.CUDAGraph()
-        if split:
+        with torch.cuda.graph(self.graph, stream=cs):
+            outs = [bodies[0]()]
+        if len(bodies) > 1:
             self.graph2 = torch.cuda.CUDAGraph()
-            n0 = ops.BN_PERSIST_LAUNCHES
-            with torch.cuda.graph(self.graph, stream=cs):
-                self.loss = self._split_first()
-            n1 = ops.BN_PERSIST_LAUNCHES
             with torch.cuda.graph(self.graph2, pool=self.graph.pool(), stream=cs):
+                outs.append(bodies[1]())
+        self._pinned = [ops.pin_captured_buffers(net) for net in self._nets]
+        self._generations = [net._arena.generation for net in self._nets]
+        torch.cuda.synchronize()
+        return outs
+
+    @property
+    def _generation(self):
+        """the arena generation of the (first) net at the capture"""
+        return self._generations[0]
+
+    def stale(self):
+        """whether a net's parameter arena was rebuilt after the capture"""
+        return any(net._arena.generation != g for net, g in zip(self._nets, self._generations))
+
+
+class GraphedTrainStep(_Recorded):
+    CHECK_EVERY = 64          # replays between two read-backs of the persistent-BatchNorm error words
+    INPUTS = ("a", "b", "lab")          # the static inputs this step holds, in call order
+    ENGINE_LEVEL = True       # the one-graph form records `_engine_pass` (no autograd graph); False: it records `_eager_body`
+    max_norm = None           # clip_grad_norm_ before the update (the xBD step of train.py)
+
+    def __init__(self, net, opt, a, b, lab, warmup=3, confusion=None):
+        """confusion: an int64 [n_class, n_class] device tensor; the recorded step then also counts arg-max(logits) against
+        the labels into it (dh_confusion_matrix, one more kernel inside the graph: the running metric of the reference's
+        trainer without any per-step launch or host read)"""
+        self._build(net, opt, (a, b, lab), warmup, confusion)
+
+    def _build(self, net, opt, inputs, warmup, confusion=None):
+        """hold `inputs` (one per name of INPUTS; None: not held), warm up, record; the state is what it was before"""
+        if not getattr(opt, "capturable", False):
+            raise ValueError("GraphedTrainStep needs dahitra_amd.optim.AdamW(..., capturable=True)")
+        dev = inputs[0].device
+        self.net, self.opt = net, opt
+        self.confusion = confusion
+        self.world = dist.get_world_size() if dist.is_initialized() else 1
+        # the mean over the ranks for an update that cannot fold 1 / world into the optimizer's grad_scale (the xBD steps)
+        self._inv_world = torch.tensor([1.0 / self.world], device=dev) if self.world > 1 else None
+        self.exchange = parallel.exchange_enabled()      # gradient all-reduce + AdamW after the replay
+        self.split_off = None                            # arena offset where the overlapped (two-graph) form splits
+        self.persist_bn_launches = None                  # (graph 1, graph 2) counts of the overlapped form
+        for name, t in zip(self.INPUTS, inputs):
+            setattr(self, name, t.clone() if t is not None else None)
+        net._ensure_arena(dev)
+        counts = []
+
+        def counted(body):          # the persistent BatchNorm launches a capture records
+            def run():
+                n0 = ops.BN_PERSIST_LAUNCHES
+                out = body()
+                counts.append(ops.BN_PERSIST_LAUNCHES - n0)
+                return out
+            return run
+        if self.exchange and self._can_split():
+            def warm():          # the same launches the two captures make (the split backward has its own reduce tables)
+                self._split_first()
                 self._second()
-            # persistent BatchNorm launches recorded into (graph 1, graph 2): graph 2 replays beside RCCL's kernels and must hold none
-            self.persist_bn_launches = (n1 - n0, ops.BN_PERSIST_LAUNCHES - n1)
+                self._update()
+            self.loss = self._capture([net], dev, warm, [counted(self._split_first), counted(self._second)], warmup)[0]
+            # graph 2 replays beside RCCL's kernels and must hold none
+            self.persist_bn_launches = tuple(counts)
             if self.persist_bn_launches[1] and os.environ.get("DAHITRA_OVERLAP_PERSIST_BN") != "1":
                 raise RuntimeError("dahitra_amd: %d persistent BatchNorm launches were recorded into the graph that overlaps the "
                                    "gradient all-reduce" % self.persist_bn_launches[1])
         else:
-            self.split_off = None
-            with torch.cuda.graph(self.graph, stream=cs):
-                self.loss = self._body(include_opt=not self.exchange)
-        self._pinned = ops.pin_captured_buffers(net)
-        self._generation = net._arena.generation
+            self.loss = self._capture([net], dev, lambda: self._body(include_opt=True),
+                                      [lambda: self._body(include_opt=not self.exchange)], warmup)[0]
         self._calls = 0
-        torch.cuda.synchronize()
-        ops.bn_persist_check(a.device)         # the warm-up steps and the capture left no barrier timeout behind
+        ops.bn_persist_check(dev)         # the warm-up steps and the capture left no barrier timeout behind
 
-    def _set_inputs(self, a, b, lab):
-        self.a, self.b, self.lab = a.clone(), b.clone(), lab.clone()
+    def _snapshot(self):
+        """parameters, BatchNorm buffers, the confusion matrix and the optimizer's state"""
+        tensors = [self.net._arena.flat] + list(self.net.buffers()) + ([self.confusion] if self.confusion is not None else [])
+        return tensors, [t.clone() for t in tensors], self.opt.snapshot_flat_state(self.net)
 
-    def _copy_inputs(self, a, b, lab):
-        self.a.copy_(a, non_blocking=True)
-        self.b.copy_(b, non_blocking=True)
-        self.lab.copy_(lab, non_blocking=True)
+    def _restore(self, saved):
+        tensors, clones, opt_state = saved
+        for t, t0 in zip(tensors, clones):
+            t.copy_(t0)
+        self.opt.restore_flat_state(self.net, opt_state)     # the optimizer keeps what it carried (e.g. a resumed checkpoint)
+
+    def _copy_inputs(self, *inputs):
+        """one per name of INPUTS; None, or an input the step does not hold, leaves what is held"""
+        if len(inputs) != len(self.INPUTS):
+            raise TypeError("%s is called with (%s) or with nothing" % (type(self).__name__, ", ".join(self.INPUTS)))
+        for name, t in zip(self.INPUTS, inputs):
+            held = getattr(self, name)
+            if held is not None and t is not None:
+                held.copy_(t, non_blocking=True)
 
     def _eager_body(self, include_opt):
         logits = self.net(self.a, self.b)
@@ -125,12 +169,10 @@ class GraphedTrainStep:
             self.opt.step()
         return loss.detach()
 
-    def _body(self, include_opt):
-        """the one-graph step.  The focal-loss step runs at engine level (no autograd graph): the same kernels as
-        `_eager_body` minus what autograd adds around them -- the fill of the upstream gradient 1.0 and the pass that scales
-        dloss/dlogits by it (two launches, 34 MB per step at batch 32).  Subclasses with their own `_eager_body` keep it."""
-        if type(self)._eager_body is not GraphedTrainStep._eager_body or os.environ.get("DAHITRA_GRAPH_AUTOGRAD") == "1":
-            return self._eager_body(include_opt)           # (DAHITRA_GRAPH_AUTOGRAD=1: A/B switch back to the autograd step)
+    def _engine_pass(self, backward):
+        """forward, loss, zero_grad and `backward(dloss/dlogits, saved)` at engine level (no autograd graph): the same kernels
+        as `_eager_body` minus what autograd adds around them -- the fill of the upstream gradient 1.0, the pass that scales
+        dloss/dlogits by it and the copies at its boundary (34 MB per step at batch 32)"""
         net = self.net
         logits = self._forward_split()
         bwd = net._engine.take_backward()
@@ -138,8 +180,16 @@ class GraphedTrainStep:
         loss, dl = self._loss_and_grad(logits)
         self._count(logits)
         net._arena.grad.zero_()
-        net._engine.backward(dl, bwd)
+        backward(dl, bwd)
         net._bind_grad_views()           # the optimizer skips parameters without a .grad, as torch does
+        return loss
+
+    def _body(self, include_opt):
+        """the one-graph step: `_engine_pass` with the whole backward for an ENGINE_LEVEL class, the autograd step
+        `_eager_body` otherwise (DAHITRA_GRAPH_AUTOGRAD=1: A/B switch of an ENGINE_LEVEL class back to it)"""
+        if not self.ENGINE_LEVEL or os.environ.get("DAHITRA_GRAPH_AUTOGRAD") == "1":
+            return self._eager_body(include_opt)
+        loss = self._engine_pass(self.net._engine.backward)
         if include_opt:
             self.opt.step()
         return loss
@@ -167,17 +217,8 @@ class GraphedTrainStep:
         return self.split_off is not None
 
     def _split_first(self):
-        """forward, loss and the first part of the backward, called under capture (engine level: one autograd-free pass)"""
-        net = self.net
-        logits = self._forward_split()
-        bwd = net._engine.take_backward()
-        self.logits = logits
-        loss, dl = self._loss_and_grad(logits)
-        self._count(logits)
-        net._arena.grad.zero_()
-        net._engine.backward_first(dl, bwd)
-        net._bind_grad_views()           # the optimizer skips parameters without a .grad, as torch does
-        return loss
+        """graph 1: forward, loss and the first part of the backward (every class, ENGINE_LEVEL or not)"""
+        return self._engine_pass(self.net._engine.backward_first)
 
     def _second(self):
         """graph 2 (layer2 / layer1 / stem backward) replays WHILE the all-reduce of the arena tail runs on RCCL's stream: its
@@ -187,11 +228,6 @@ class GraphedTrainStep:
             return
         with ops.no_persist_bn():
             self.net._engine.backward_second()
-
-    def _after_replay(self):
-        """world > 1: the exchange step and the update run eagerly after the replayed forward/backward"""
-        parallel.allreduce_net_grads_(self.net)
-        self._update()
 
     def _replay_overlapped(self):
         _, grad = self.net.flat_params()
@@ -204,13 +240,13 @@ class GraphedTrainStep:
         self._update()
 
     def _update(self):
-        """after both all-reduces: the (eager) parameter update"""
+        """world > 1, after the all-reduces have landed: the (eager) parameter update"""
         self.opt.step()
 
     def __call__(self, *inputs):
-        if self.net._arena.generation != self._generation:
+        if self.stale():
             raise RuntimeError("dahitra_amd: the net's parameter arena was rebuilt (moved to another device / "
-                               "parameters replaced) after this step was captured; build a new GraphedTrainStep")
+                               "parameters replaced) after this step was captured; build a new %s" % type(self).__name__)
         if inputs and inputs[0] is not None:
             self._copy_inputs(*inputs)
         self._calls += 1
@@ -223,12 +259,13 @@ class GraphedTrainStep:
             self._replay_overlapped()
             return self.loss
         self.graph.replay()
-        if self.exchange:
-            self._after_replay()
+        if self.exchange:      # the exchange step and the update run eagerly after the replayed forward / backward
+            parallel.allreduce_net_grads_(self.net)
+            self._update()
         return self.loss
 
 
-class _RecordedEval:
+class _RecordedEval(_Recorded):
     """What the recorded evaluation steps below share: how an eval-mode body becomes one HIP graph (`_record`) and what a replay
     refuses (`_guard`).  A subclass holds its static buffers, its `_body`, its input copy and its shape check."""
     _word = "evaluation"                                  # "... after this <word> step was captured"
@@ -238,45 +275,18 @@ class _RecordedEval:
         """net.eval() on every net, `warmup` eager bodies on a side stream, then `body()` captured into self.graph; returns what
         the captured body returned (its static output).  accumulators: the tensors the body adds to (None entries are skipped);
         they are as they were before, since neither the warm-up nor the capture is part of any count."""
-        self._nets = list(nets)
-        for net in self._nets:
+        for net in nets:
             net.eval()
             net._ensure_arena(device)
-        accumulators = [t for t in accumulators if t is not None]
-        saved = [t.clone() for t in accumulators]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        for t, t0 in zip(accumulators, saved):
-            t.copy_(t0)
-        # The capture stream inherits the warm-up stream's scratch workspace and is KEPT for the life of the step: released,
-        # PyTorch's stream pool could hand its handle to a later torch.cuda.Stream(), whose eager launches would then look up -- and
-        # scribble over -- the workspace the recorded graph reads and writes.  The captured buffers are pinned for the same
-        # reason (the full account stands at GraphedTrainStep's capture).
-        cs = self._capture_stream = torch.cuda.Stream()
-        ops.rekey_workspace(device, s, cs)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=cs):
-            out = body()
-        self._pinned = [ops.pin_captured_buffers(net) for net in self._nets]
-        self._generations = [net._arena.generation for net in self._nets]
-        torch.cuda.synchronize()
-        for t, t0 in zip(accumulators, saved):
-            t.copy_(t0)
-        return out
+        self._accumulators = [t for t in accumulators if t is not None]
+        return self._capture(nets, device, body, [body], warmup)[0]
 
-    @property
-    def _generation(self):
-        """the arena generation of the (first) net at the capture"""
-        return self._generations[0]
+    def _snapshot(self):
+        return [t.clone() for t in self._accumulators]
 
-    def stale(self):
-        """whether a net's parameter arena was rebuilt after the capture"""
-        return any(net._arena.generation != g for net, g in zip(self._nets, self._generations))
+    def _restore(self, saved):
+        for t, t0 in zip(self._accumulators, saved):
+            t.copy_(t0)
 
     def _guard(self):
         """what every replay refuses: a rebuilt arena (the graph holds the old one's addresses) and a net in train mode"""
@@ -616,17 +626,12 @@ class GraphedXbdStep(GraphedTrainStep):
 
         step = GraphedXbdStep(net, xbd.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-6, capturable=True), imgs, msks)
         loss = step(imgs, msks)"""
+    INPUTS = ("a", "lab")          # imgs, msks
+    ENGINE_LEVEL = False           # the one-graph form records the autograd step, clip_grad_norm_ included
 
     def __init__(self, net, opt, imgs, msks, max_norm=0.999, warmup=3):
         self.max_norm = max_norm
-        super().__init__(net, opt, imgs, None, msks, warmup=warmup)
-
-    def _set_inputs(self, imgs, _unused, msks):
-        self.a, self.lab = imgs.clone(), msks.clone()
-
-    def _copy_inputs(self, imgs, msks):
-        self.a.copy_(imgs, non_blocking=True)
-        self.lab.copy_(msks, non_blocking=True)
+        self._build(net, opt, (imgs, msks), warmup)
 
     def _eager_body(self, include_opt):
         from .models import xbd
@@ -654,20 +659,16 @@ class GraphedXbdStep(GraphedTrainStep):
         self._one = one
         return loss, ops.combo_loss_bwd(lo, ms, sums, w, one, 1.0, 8.0)
 
-    def _after_replay(self):
-        parallel.allreduce_net_grads_(self.net)
-        self._update()
-
     def _update(self):
-        """mean over the ranks, clip_grad_norm_(0.999) over the WHOLE (now complete) arena, then the hand-rolled AdamW:
-        the clip needs the total norm, so it cannot start before both all-reduces have landed (train.py:373-374)"""
+        """mean over the ranks, clip_grad_norm_(max_norm) over the WHOLE (now complete) arena where the step clips, then the
+        hand-rolled AdamW: the clip needs the total norm, so it cannot start before both all-reduces have landed
+        (train.py:373-374)"""
         from .models import xbd
-        _, grad = self.net.flat_params()
-        if self.world > 1:
-            if getattr(self, "_inv_world", None) is None:
-                self._inv_world = torch.tensor([1.0 / self.world], device=grad.device)
+        if self._inv_world is not None:
+            _, grad = self.net.flat_params()
             ops.scale_into(grad, self._inv_world, grad)
-        xbd.clip_grad_norm_(self.net.parameters(), self.max_norm)
+        if self.max_norm is not None:
+            xbd.clip_grad_norm_(self.net.parameters(), self.max_norm)
         self.opt.step()
 
 
@@ -683,8 +684,12 @@ class GraphedXbdUnetStep(GraphedXbdStep):
     labels: 'lbl_msk' (the script as executed; lbl_msk uint8 [B, H, W] is needed) or 'damage' (the label is derived from msks in
     the kernel; lbl_msk is neither kept nor copied).  A scheduler's learning rate reaches the replay through opt.sync_hyper, as in
     the parent.  ValueError for a label mode, dtype or shape that does not fit, before anything is recorded."""
+    INPUTS = ("a", "lab", "lbl")          # imgs, msks, lbl_msk (lbl is None under labels='damage')
+    ENGINE_LEVEL = True
+    max_norm = None                       # the script does not clip
 
     def __init__(self, net, opt, imgs, msks, lbl_msk=None, labels='lbl_msk', warmup=3):
+        from .models import xbd
         what = "GraphedXbdUnetStep"
         if labels not in ops.XBD_UNET_LABELS:
             raise ValueError("%s: labels %r is not one of %s" % (what, labels, sorted(ops.XBD_UNET_LABELS)))
@@ -698,46 +703,16 @@ class GraphedXbdUnetStep(GraphedXbdStep):
             a.tensor("lbl_msk", lbl_msk, torch.uint8, (B, H, W), "[%d, %d, %d] like imgs" % (B, H, W))
         a.placed()
         self.labels, self.parts = labels, None
-        GraphedTrainStep.__init__(self, net, opt, imgs, lbl_msk if labels == 'lbl_msk' else None, msks, warmup=warmup)
-
-    def _set_inputs(self, imgs, lbl_msk, msks):
-        from .models import xbd
-        self.a, self.lab = imgs.clone(), msks.clone()
-        self.lbl = lbl_msk.clone() if lbl_msk is not None else None
         self._w = xbd.unet_weights_dev(imgs.device)        # made here: no host-to-device copy inside the capture
+        self._build(net, opt, (imgs, msks, lbl_msk if labels == 'lbl_msk' else None), warmup)
 
-    def _copy_inputs(self, imgs, msks, lbl_msk=None):
-        self.a.copy_(imgs, non_blocking=True)
-        self.lab.copy_(msks, non_blocking=True)            # bytes to bytes
-        if self.lbl is not None and lbl_msk is not None:
-            self.lbl.copy_(lbl_msk, non_blocking=True)
+    def __call__(self, imgs=None, msks=None, lbl_msk=None):
+        return super().__call__(imgs, msks, lbl_msk)
 
     def _eager_body(self, include_opt):
         from .models import xbd
-        self.net.zero_grad()
-        logits = self.net(self.a)
-        self.logits = logits.detach()
-        loss, self.parts = xbd.unet_loss(logits, self.lab, self.lbl, self.labels, want_parts=True)
-        loss.backward()
-        if include_opt:
-            self.opt.step()
-        return loss.detach()
-
-    def _body(self, include_opt):
-        """the one-graph step at engine level: the kernels of `_eager_body` without what autograd adds around them (the fill of
-        the upstream gradient and the copies at its boundary).  DAHITRA_GRAPH_AUTOGRAD=1 switches back to the autograd step."""
-        if os.environ.get("DAHITRA_GRAPH_AUTOGRAD") == "1":
-            return self._eager_body(include_opt)
-        net = self.net
-        logits = self._forward_split()
-        bwd = net._engine.take_backward()
-        self.logits = logits
-        loss, dl = self._loss_and_grad(logits)
-        net._arena.grad.zero_()
-        net._engine.backward(dl, bwd)
-        net._bind_grad_views()           # the optimizer skips parameters without a .grad, as torch does
-        if include_opt:
-            self.opt.step()
+        self.logits, loss, self.parts = xbd.unet_eager_step(self.net, self.opt, self.a, self.lab, self.lbl, self.labels,
+                                                            update=include_opt)
         return loss
 
     def _loss_and_grad(self, logits):
@@ -746,12 +721,3 @@ class GraphedXbdUnetStep(GraphedXbdStep):
         lo = logits.float().contiguous()
         loss, self.parts, sums = ops.xbd_unet_loss_fwd(lo, self.lab, self.lbl, self.labels, self._w, 1.0, 8.0, xbd.UNET_CE_SCALE)
         return loss, ops.xbd_unet_loss_bwd(lo, self.lab, self.lbl, self.labels, sums, self._w, None, 1.0, 8.0, xbd.UNET_CE_SCALE)
-
-    def _update(self):
-        """mean over the ranks, then the hand-rolled AdamW: the script does not clip"""
-        if self.world > 1:
-            _, grad = self.net.flat_params()
-            if getattr(self, "_inv_world", None) is None:
-                self._inv_world = torch.tensor([1.0 / self.world], device=grad.device)
-            ops.scale_into(grad, self._inv_world, grad)
-        self.opt.step()

@@ -277,6 +277,16 @@ def _eval_step(model, batch, class_counts, thr, select):
                       lambda step: step._generation == model._arena.generation and step.class_counts is class_counts)
 
 
+def _next_rows(rows, n, count, row_shape, dtype, device):
+    """The rows [n, n + count) of an epoch's device buffer [*, *row_shape], made by the first call (rows=None) and doubled, on the
+    device, when it is full: an iterator does not say how long it is.  Returns (the buffer, the view of those rows)."""
+    if rows is None:
+        rows = torch.zeros((max(64, count),) + row_shape, dtype=dtype, device=device)
+    if n + count > rows.shape[0]:
+        rows = torch.cat([rows, torch.zeros((max(rows.shape[0], count),) + row_shape, dtype=dtype, device=device)])
+    return rows, rows[n:n + count]
+
+
 def _epoch(what, model, batches, row_shape, accumulator, replay, eager):
     """The epoch loop of validate and validate_sweep.  The first batch fixes the shape and the device; accumulator(device) gives
     the int64 class accumulator (kept on the model: a recorded step holds its address), zeroed here; every image gets one int64
@@ -290,17 +300,15 @@ def _epoch(what, model, batches, row_shape, accumulator, replay, eager):
             imgs, msk, lbl = batch['img'], batch['msk'], batch['lbl_msk']
             _device_u8("validation", imgs)
             B = imgs.shape[0]
-            if rows is None:
+            if first is None:
                 dev, first = imgs.device, tuple(imgs.shape)
                 acc = accumulator(dev)
                 acc.zero_()
-                rows = torch.zeros((max(64, B),) + row_shape, dtype=torch.int64, device=dev)
-            if n + B > rows.shape[0]:            # an iterator does not say how long it is: the buffer doubles, on the device
-                rows = torch.cat([rows, torch.zeros((max(rows.shape[0], B),) + row_shape, dtype=torch.int64, device=dev)])
+            rows, mine = _next_rows(rows, n, B, row_shape, torch.int64, dev)
             if replay is not None and tuple(imgs.shape) == first:
-                rows[n:n + B].copy_(replay(batch, acc), non_blocking=True)
+                mine.copy_(replay(batch, acc), non_blocking=True)
             else:
-                eager(model(imgs).float(), msk, lbl, rows[n:n + B], acc)
+                eager(model(imgs).float(), msk, lbl, mine, acc)
             n += B
     if rows is None:
         raise ValueError("%s: no batches" % what)
@@ -527,6 +535,19 @@ def unet_val_batches(pipe, batch_size=16, crop=256):
         yield pipe.make_batch(ind, crop, [[512, 512, 0, 0, 0, 0, 0, crop, crop]] * len(ind), train=False)
 
 
+def unet_eager_step(model, optimizer, imgs, msks, lbl_msk, labels, update=True):
+    """The script's step through autograd (train_unettransformer.py:436-481): zero_grad, forward, unet_loss, backward and --
+    with `update` -- optimizer.step(), no clip.  Returns (logits, loss, parts), detached.  What train_epoch_unet runs for a batch
+    without a recorded step, and GraphedXbdUnetStep's `_eager_body`."""
+    model.zero_grad()
+    logits = model(imgs)
+    loss, parts = unet_loss(logits, msks, lbl_msk, labels, want_parts=True)
+    loss.backward()
+    if update:
+        optimizer.step()
+    return logits.detach(), loss.detach(), parts
+
+
 def _unet_train_step(model, optimizer, first, labels, graph):
     """run(batch) -> (loss, parts) device tensors for the batches of one epoch: batches of the first batch's shape replay the
     model's recorded GraphedXbdUnetStep (kept on the model per shape, label mode, optimizer and device), any other shape -- a
@@ -534,11 +555,7 @@ def _unet_train_step(model, optimizer, first, labels, graph):
     _device_u8("training", first['img'], first['msk'])
 
     def eager(batch):
-        model.zero_grad()
-        loss, parts = unet_loss(model(batch['img']), batch['msk'], batch['lbl_msk'], labels, want_parts=True)
-        loss.backward()
-        optimizer.step()
-        return loss.detach(), parts
+        return unet_eager_step(model, optimizer, batch['img'], batch['msk'], batch['lbl_msk'], labels)[1:]
     if not graph:
         return eager
     from ..graph import GraphedXbdUnetStep
@@ -578,13 +595,9 @@ def train_epoch_unet(current_epoch, model, optimizer, scheduler, batches, labels
         if run is None:
             run = _unet_train_step(model, optimizer, batch, labels, graph)
         loss, parts = run(batch)
-        n = len(sizes)
-        if rows is None:
-            rows = torch.zeros(64, 9, dtype=torch.float32, device=loss.device)
-        if n == rows.shape[0]:                # an iterator does not say how long it is: the buffer doubles, on the device
-            rows = torch.cat([rows, torch.zeros_like(rows)])
-        rows[n, 0:1].copy_(loss.reshape(1), non_blocking=True)
-        rows[n, 1:].copy_(parts, non_blocking=True)
+        rows, row = _next_rows(rows, len(sizes), 1, (9,), torch.float32, loss.device)
+        row[0, 0:1].copy_(loss.reshape(1), non_blocking=True)
+        row[0, 1:].copy_(parts, non_blocking=True)
         sizes.append(int(batch['img'].shape[0]))
     if rows is None:
         raise ValueError("train_epoch_unet: no batches")

@@ -19,6 +19,8 @@ import functools
 import math
 import os
 import random
+import socket
+import sys
 
 import numpy as np
 import pytest
@@ -288,3 +290,123 @@ def test_train_epoch_unet_meters_are_the_means_of_the_steps(capsys):
     assert line == ["epoch: 0; lr 0.0000600; Loss {:.4f}; loss2 {:.4f}; Dice {:.4f}".format(meters['loss'], meters['loss2'],
                                                                                             meters['dice'])]
     assert len(net.__dict__['_xbd_unet_steps']) == 1                   # the recorded step is kept on the model
+
+
+# ---- two data-parallel ranks and the held inputs, at the smallest shape this file runs the net at ---------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def batch_64(n, seed=13):
+    """n pairs of 64 x 64 on the host: imgs [n, 6, 64, 64], the loader's uint8 msks [n, 5, 64, 64] and a label plane 0 .. 4"""
+    a, b, lab = O.synthetic_batch(n, 64, seed=seed, n_class=5)
+    return torch.cat([a, b], 1), O.xbd_masks(lab).to(torch.uint8), lab[:, 0].to(torch.uint8)
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _unet_rank(rank, world, port, overlap, steps, out):
+    """one gloo rank on cuda:0 (as tests/test_parallel_gpu.py::_worker): DAHITRA_OVERLAP=0 is one graph + one all-reduce + the
+    update, DAHITRA_OVERLAP=1 two graphs around the all-reduce of the arena tail"""
+    os.environ.update(RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      DAHITRA_OVERLAP=overlap)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import torch.distributed as dist
+    from dahitra_amd import parallel
+    from dahitra_amd.graph import GraphedXbdUnetStep
+    from dahitra_amd.models import xbd
+    parallel.init_from_env("gloo")
+    torch.cuda.set_device(0)
+    net = make().train() if rank == 0 else xbd.BASE_Transformer_UNet(with_decoder_pos=None, compute_dtype="fp32").cuda().train()
+    net._ensure_arena(torch.device("cuda", 0))
+    parallel.broadcast_params_(net)                          # rank 1 keeps its random init: the broadcast must fix it
+    x6, msk, _ = batch_64(2 * world)
+    lo, hi = parallel.shard_batch(2 * world, rank, world)
+    x6, msk = x6[lo:hi].cuda(), msk[lo:hi].cuda()
+    opt = xbd.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-6, capturable=True)
+    step = GraphedXbdUnetStep(net, opt, x6, msk, None, labels='damage')
+    assert step.exchange
+    if overlap == "0":
+        assert step.split_off is None
+    else:
+        assert step.split_off is not None and 0 < step.split_off < net._arena.n_active
+    for _ in range(steps):
+        step(x6, msk)
+    torch.cuda.synchronize()
+    torch.save({k: v.cpu() for k, v in net.state_dict().items()}, out % rank)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@functools.lru_cache(None)
+def two_replica_emulation(steps=2):
+    """the single-process emulation of two ranks, made once for both forms: per-shard gradients of two replicas, the sum of the
+    two arenas scaled by 1 / 2, NO clip, xbd.AdamW.step() on every replica -> replica 0's state on the host"""
+    from dahitra_amd import ops
+    from dahitra_amd.models import xbd
+    x6, msk, _ = batch_64(4)
+    nets = [make().train() for _ in range(2)]
+    opts = [xbd.AdamW(n.parameters(), lr=1e-3, weight_decay=1e-6) for n in nets]
+    for _ in range(steps):
+        for r, net in enumerate(nets):
+            net.zero_grad()
+            sl = slice(2 * r, 2 * r + 2)
+            xbd.unet_loss(net(x6[sl].cuda()), msk[sl].cuda(), None, 'damage').backward()
+        total = nets[0].flat_params()[1] + nets[1].flat_params()[1]
+        for net, opt in zip(nets, opts):
+            g = net.flat_params()[1]
+            g.copy_(total)
+            ops.scale_into(g, torch.tensor([0.5], device=g.device), g)
+            opt.step()
+    return {k: v.cpu() for k, v in nets[0].state_dict().items()}
+
+
+@pytest.mark.parametrize("overlap", ["0", "1"])
+def test_two_ranks_of_the_unet_step_match_the_single_process_emulation(tmp_path, overlap):
+    """GraphedXbdUnetStep(labels='damage') on two gloo ranks, two steps, in the serial and in the overlapped form: both ranks end
+    with equal parameters, within 2e-5 of the emulation (the bound tests/test_parallel_gpu.py holds the graphed xBD step to: the
+    replay uses the device-side Adam bias corrections, the emulation the host-side ones)"""
+    import torch.multiprocessing as mp
+    out = str(tmp_path / "rank%d.pt")
+    mp.start_processes(_unet_rank, args=(2, _free_port(), overlap, 2, out), nprocs=2, join=True, start_method="spawn")
+    sd0, sd1 = torch.load(out % 0), torch.load(out % 1)
+    ref = two_replica_emulation()
+    worst = 0.0
+    for k, v in sd0.items():
+        if not v.dtype.is_floating_point or "running_" in k or "num_batches" in k:
+            continue                                   # BatchNorm buffers are per replica
+        assert torch.equal(v, sd1[k]), k               # same reduced gradient, same update on both ranks
+        worst = max(worst, float((v - ref[k]).abs().max()))
+    print("two ranks, DAHITRA_OVERLAP=%s: worst distance from the emulation %.3e" % (overlap, worst))
+    assert worst <= 2e-5, worst
+
+
+@pytest.mark.parametrize("labels", ["damage", "lbl_msk"])
+def test_a_replay_on_the_held_inputs_equals_a_replay_given_them(labels):
+    """two steps recorded on nets in the same state: one is handed (imgs, msks, lbl_msk) at every call, the other replays on what
+    it holds.  Three replays, at the 1e-5 of graph against eager.  An lbl_msk handed to a 'damage' step is ignored."""
+    from dahitra_amd.graph import GraphedXbdUnetStep
+    from dahitra_amd.models import xbd
+    x6, msk, lbl = (t.cuda() for t in batch_64(2))
+    steps = []
+    for _ in range(2):
+        net = make().train()
+        opt = xbd.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-6, capturable=True)
+        steps.append(GraphedXbdUnetStep(net, opt, x6, msk, lbl, labels=labels))
+    given, held = steps
+    worst = 0.0
+    for it in range(3):
+        lg, lh = float(given(x6.clone(), msk.clone(), lbl.clone())), float(held())
+        pg, ph = given.parts.cpu().numpy(), held.parts.cpu().numpy()
+        worst = max(worst, abs(lg - lh) / abs(lh), float(np.max(np.abs(pg[:7] - ph[:7]) / np.abs(ph[:7]))))
+        assert abs(lg - lh) <= 1e-5 * abs(lh), (it, lg, lh)
+        assert pg[7] == ph[7] == 0 and np.all(np.abs(pg[:7] - ph[:7]) <= 1e-5 * np.abs(ph[:7])), (it, pg, ph)
+    print("held inputs, labels=%s: worst relative difference %.3e" % (labels, worst))
+    for s in steps:
+        assert (s.lbl is None) if labels == 'damage' else (s.lbl.dtype == torch.uint8 and torch.equal(s.lbl, lbl))
