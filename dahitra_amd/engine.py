@@ -133,9 +133,6 @@ class Engine:
         # all layers of a fused decoder stack in one launch per direction (csrc/decoder_fused.hip DecArgs::depth): the stack is
         # a per-pixel-row function, so nothing synchronises between its layers but a workgroup's own re-staging of the weights
         self.fuse_dec_stack = os.environ.get("DAHITRA_NO_DEC_STACK", "0") != "1"
-        # the three levels' small kernels on streams of their own between the shared launches (_run_staged)
-        self.level_streams = os.environ.get("DAHITRA_LEVEL_STREAMS", "0") == "1"
-        self._lstreams = []
         # class-head data gradient gated for the classifier's BatchNorm (mask + BN-backward sums in its epilogue).  Measured
         # neutral (8020 vs 8027 pairs/s: the reduction pass it removes costs what the extra read of y costs the head kernel):
         # off by default, DAHITRA_GATED_HEAD=1 turns it on.
@@ -144,10 +141,6 @@ class Engine:
         # 16-byte-per-pixel dlogits (one MFMA per 16 pixels x 16 channels) -- 3 x 134 MB less at the bench size
         # (DAHITRA_NO_FUSED_HEAD_BN=1: the three-kernel path)
         self.fused_head_bn = os.environ.get("DAHITRA_NO_FUSED_HEAD_BN", "0") != "1"
-        # a second stream for the classifier's weight gradient, next to the low-occupancy token-side backward (bf16 training).
-        # Measured: the launch does overlap the encoder's backward in the graph (rocprofv3 trace: 120 us next to encoder_bwd /
-        # encoder_wgrad / tok_bwd instead of 63 us alone), but those kernels slow down by 28 us and the forked graph costs more
-        # than the rest: 7950 vs 8010 pairs/s over five interleaved 150-step runs.  Off by default (DAHITRA_SIDE_STREAM=1).
         # bf16: the data gradient of classifier.0 goes straight to the coarse |A - B| maps (the 32 x 256 x 256 gradient of the
         # bilinear-upsampled map is never written or re-read): DAHITRA_NO_FUSED_UP4_BWD=1 restores the two-kernel path
         self.fused_up4_bwd = os.environ.get("DAHITRA_NO_FUSED_UP4_BWD", "0") != "1"
@@ -158,7 +151,6 @@ class Engine:
         # run at >= 512 workgroups).  OFF by default; DAHITRA_FUSED_UP4_FWD=1 turns the convolution's form on (the weight
         # gradient then materialises the map itself).  DESIGN.md section 6e.
         self.fused_up4_fwd = os.environ.get("DAHITRA_FUSED_UP4_FWD", "0") == "1"
-        self.use_side = os.environ.get("DAHITRA_SIDE_STREAM", "0") == "1"
         # Residual blocks keep two tensors out of HBM that had one reader each.  (1) The BatchNorm output of a shortcut with a
         # downsample: the bn_apply of bn2 / bn3 forms it from the shortcut conv's output while it loads its residual
         # (ops.BnResidual, dh_bn_apply_res_affine) -- one launch and one write + read of the tensor less.  (2) The masked copy
@@ -169,10 +161,6 @@ class Engine:
         # selections of the same roundings: results keep their bits.  DAHITRA_BLOCK_COPIES=1 restores both tensors (one switch,
         # for tests).  Measured: DESIGN.md section 6i, "Residual blocks without their single-reader tensors".
         self.block_copies = os.environ.get("DAHITRA_BLOCK_COPIES", "0") == "1"
-        self.pack_side = os.environ.get("DAHITRA_PACK_SIDE", "0") == "1"
-        self._pack_stream = None
-        self.side = None
-        self._deferred_wgrad = None
         self.shapes = {k: s for k, s, _ in state_spec(net_G)}
         self.p = {}        # key -> fp32 parameter / buffer tensors (device)
         self.g = {}        # key -> fp32 gradient views
@@ -197,23 +185,10 @@ class Engine:
         if plan is None:
             plan = self._plans[self.need_grad] = self._build_plan()
         pack, self.pk, self.xstack, self.wstack = plan
-        # the per-step re-pack (one launch, 37 - 42 us of strided gathers) next to the stem, which reads the OIHW weights itself:
-        # a side stream forked here and joined after the stem (_pack_join) -- in the recorded step two parallel branches
-        if self.pack_side and self.training and self.direct_stem and self.dtype == torch.bfloat16 and ops.PROFILE is None:
-            if self._pack_stream is None:
-                self._pack_stream = ops.SideStream(self.p["resnet.conv1.weight"].device)
-            with self._pack_stream.fork():
-                pack.run()
-        else:
-            pack.run()
+        pack.run()
         key = "resnet.conv1.weight"
         if not (self.direct_stem and self.dtype == torch.bfloat16):      # the direct stem kernel reads the OIHW weights itself
             self.pk[key] = Packed(ops.stem_pack_weight(self.p[key], self.dtype), None)
-
-    def _pack_join(self):
-        """the current stream waits for the re-pack issued on the side stream (no-op otherwise): before the first packed weight is read"""
-        if self._pack_stream is not None:
-            self._pack_stream.join()
 
     def _build_plan(self):
         ck = ops.chunk_channels(self.dtype)
@@ -313,8 +288,7 @@ class Engine:
                        w_frag=self.pk[wkey].dgrad_frag if stride == 1 else None)
         return Gated(*r) if gate is not None else r
 
-    def conv_bn(self, x, wkey, bnkey, ks, stride, pad, groups, relu, residual=None, dilation=1, lazy=False, side_wgrad=False,
-                lazy_res=False):
+    def conv_bn(self, x, wkey, bnkey, ks, stride, pad, groups, relu, residual=None, dilation=1, lazy=False, lazy_res=False):
         """conv + BatchNorm (+ residual) (+ ReLU).  x may be an ops.BnInput (the previous layer's lazy output).
         lazy=True (train mode, ReLU, no residual; the ONLY consumer must be a 3x3 stride-1 convolution and its weight
         gradient): the normalised activation is never written -- the call returns an ops.BnInput (pre-BN conv output +
@@ -391,14 +365,7 @@ class Engine:
                 r = ops.bn_bwd(dout, out if relu else None, y, mean, invstd, gamma, self.g[bnkey + ".weight"],
                                self.g[bnkey + ".bias"], groups, accumulate=True, want_dres=wd, bits=relu_bits)
                 dy, dres = r if wd else (r, None)
-            if side_wgrad and self.side is not None:
-                # Deferred to the side stream: nothing until the batched split-K reduce needs this weight gradient.  It is
-                # launched (run_deferred_wgrad) when the main stream reaches the token encoder's backward -- one workgroup per
-                # image, 3/4 of the CUs idle for ~150 us; forked right here it only competed with the data gradient below.
-                self._deferred_wgrad = (x, dy, wkey, ks, stride, pad, dilation)
-            else:
-                ops.conv2d_wgrad(x, dy, self.g[wkey], ks, stride, pad, accumulate=True, use_tr=self.use_tr,
-                                 dilation=dilation)
+            ops.conv2d_wgrad(x, dy, self.g[wkey], ks, stride, pad, accumulate=True, use_tr=self.use_tr, dilation=dilation)
             if through_up4 is not None:
                 return ops.conv3x3_dgrad_through_up4(dy, self.pk[wkey].dgrad, *through_up4), dres
             if split and need_dx:
@@ -959,8 +926,6 @@ class Engine:
     def forward(self, x1, x2, training, need_grad):
         ops.set_f32_mma_mode(self.mma_fwd)        # library state per host thread: every entry point sets it
         self.training, self.need_grad = training, need_grad
-        if need_grad and self.use_side and self.side is None and self.dtype == torch.bfloat16:
-            self.side = ops.SideStream(x1.device)
         self._pack_all()
         if self.cfg["kind"] == "bit":
             logits, bwd = self._bit(x1, x2)
@@ -991,56 +956,40 @@ class Engine:
         bwd, self._bwd = self._bwd, None
         return bwd
 
-    def backward(self, dlogits_nchw, bwd=None):
+    def _begin_backward(self, device):
+        """what every backward pass opens with: the MMA mode, the grad plan's packed weights, the weight-gradient batch"""
         ops.set_f32_mma_mode(self.mma_bwd)
-        if bwd is None:
-            bwd, self._bwd = self._bwd, None
-        if bwd is None:
-            raise RuntimeError("dahitra_amd: backward called without a grad-enabled forward")
         plan = self._plans.get(True)
         if plan is not None:       # a no-grad forward in between switched self.pk to the forward-only packed weights
             self.pk, self.xstack, self.wstack = plan[1], plan[2], plan[3]
         if self._wgrad_plan is None:
-            self._wgrad_plan = ops.WgradPlan(dlogits_nchw.device, batch=True)
+            self._wgrad_plan = ops.WgradPlan(device, batch=True)
+
+    def backward(self, dlogits_nchw, bwd=None):
+        if bwd is None:
+            bwd, self._bwd = self._bwd, None
+        if bwd is None:
+            raise RuntimeError("dahitra_amd: backward called without a grad-enabled forward")
+        self._begin_backward(dlogits_nchw.device)
         with self._wgrad_plan as plan:      # the conv layers' split-K reduces: one launch at the end of the pass
             bwd(dlogits_nchw)
-            self._side_join()
             plan.run()
 
     # A backward pass in TWO parts (data-parallel overlap, dahitra_amd/graph.py): after backward_first() every gradient
     # from resnet.layer3 to the end of the arena is final (its split-K reduces have run) and can be all-reduced while
     # backward_second() computes the stem / layer1 / layer2 gradients.
     def backward_first(self, dlogits_nchw, bwd):
-        ops.set_f32_mma_mode(self.mma_bwd)
         split = getattr(bwd, "split", None)
         if split is None:
             raise RuntimeError("dahitra_amd: this net's backward has no split point")
-        plan = self._plans.get(True)
-        if plan is not None:
-            self.pk, self.xstack, self.wstack = plan[1], plan[2], plan[3]
-        if self._wgrad_plan is None:
-            self._wgrad_plan = ops.WgradPlan(dlogits_nchw.device, batch=True)
+        self._begin_backward(dlogits_nchw.device)
         self._wgrad_plan.__enter__()
         try:
             self._split_state = (split[1], split[0](dlogits_nchw))
-            self._side_join()
             self._wgrad_plan.run()
         except BaseException:
             self._wgrad_plan.__exit__(*sys.exc_info())      # abort: what the failed pass recorded must not be launched
             raise
-
-    def run_deferred_wgrad(self):
-        d, self._deferred_wgrad = self._deferred_wgrad, None
-        if d is None:
-            return
-        x, dy, wkey, ks, stride, pad, dilation = d
-        with self.side.fork(x.y if isinstance(x, ops.BnInput) else (x.a if isinstance(x, ops.Up4Input) else x), dy):
-            ops.conv2d_wgrad(x, dy, self.g[wkey], ks, stride, pad, accumulate=True, use_tr=self.use_tr, dilation=dilation)
-
-    def _side_join(self):
-        if self.side is not None:
-            self.run_deferred_wgrad()
-            self.side.join()
 
     def backward_second(self):
         ops.set_f32_mma_mode(self.mma_bwd)
@@ -1105,7 +1054,6 @@ class Engine:
         B = x1.shape[0]
         S2 = 2 * B
         xp, xarg, xshape, b_stem = self.stem(x1, x2, 2, pool=True)
-        self._pack_join()
         if cfg.get("backbone") == "resnet50":
             l1, b_l1 = self.res50_layer(xp, 1, 1, 1, 1, 2)
             l2, b_l2 = self.res50_layer(l1, 2, 2, 1, 1, 2)
@@ -1138,7 +1086,7 @@ class Engine:
             upd = ops.Up4Input(dec4[:B].contiguous(), dec4[B:].contiguous())
         else:
             upd = ops.absdiff_upsample4(dec4[:B], dec4[B:])
-        h, b_c0 = self.conv_bn(upd, k0, "classifier.1", 3, 1, 1, 1, True, lazy=True, side_wgrad=True)
+        h, b_c0 = self.conv_bn(upd, k0, "classifier.1", 3, 1, 1, 1, True, lazy=True)
         logits, b_out = self._head_out(h, "classifier.3.weight", "classifier.3.bias")
         if not self.need_grad:
             return logits, None
@@ -1156,8 +1104,6 @@ class Engine:
                 dec_g = torch.empty_like(dec4)
                 ops.absdiff_upsample4_bwd_into(dec4[:B], dec4[B:], dupd, dec_g[:B], dec_g[B:])
             dfeat = b_dec(dec_g.view(S2 * hw, DIM))                    # also fills dtok
-            if self.side is not None:
-                self.run_deferred_wgrad()            # the classifier's weight gradient, next to the encoder's backward
             dtok_cat = b_enc(dtok)
             dfeat4 = dfeat.view(S2, fh, fw, DIM)
             ops.tokenizer_bwd(feat, wa, tsaved, dtok_cat, dfeat4, self.g["conv_a.weight"], self.g["pos_embedding"],
@@ -1192,38 +1138,20 @@ class Engine:
         backward: the `bwd` it returns).  They run in rounds inside one ops.EncoderBatch: the launches they reach are only
         RECORDED, and after each round the recorded ones go out together -- the levels are independent, an encoder stack
         occupies 2 x batch workgroups, the decoder stacks of the 16 x 16 and 32 x 32 levels a fraction of the chip.
-        Between two such launches every level issues its OWN small kernels (1x1 squeeze, tokenizer, cross-attention operand
-        preparation and its gradients, positional adds, channel copies: 138 launches under 8 us in the DAHiTra step, most of
-        them a few dozen workgroups): with `level_streams` each level's segment goes to a stream of its own, forked from and
-        joined into the main stream around the round -- in the recorded step they are parallel branches of the graph and run
-        side by side instead of one after the other.
         ew=True (the `_level` generators, which pause after them): the levels' positional adds, channel concatenations and token
         differences (and their gradients) are recorded as well and go out as one job-table launch per round (ops.EwBatch).
         Returns the generators' return values."""
         vals = {}
-        streams = None
-        if self.level_streams and len(gens) > 1 and ops.PROFILE is None:
-            dev = torch.cuda.current_device()
-            while len(self._lstreams) < len(gens):
-                self._lstreams.append(ops.SideStream(torch.device("cuda", dev)))
-            streams = self._lstreams
-        with ops.EncoderBatch(decoder=True, ew=ew and streams is None) as eb:
-            live = list(enumerate(gens))
+        with ops.EncoderBatch(decoder=True, ew=ew) as eb:
+            live = list(gens)
             while live:
                 paused = []
-                for i, g in live:
+                for g in live:
                     try:
-                        if streams is not None:
-                            with streams[i].fork():
-                                next(g)
-                        else:
-                            next(g)
-                        paused.append((i, g))
+                        next(g)
+                        paused.append(g)
                     except StopIteration as e:
                         vals[id(g)] = e.value
-                if streams is not None:
-                    for st in streams:
-                        st.join()
                 eb.launch()          # what the levels recorded in this round: one launch per kernel family
                 live = paused
         return [vals[id(g)] for g in gens]
@@ -1354,7 +1282,6 @@ class Engine:
     def _unet(self, x1, x2):
         B = x1.shape[0]
         s2, b_stem = self.stem(x1, x2, 2)                      # [2B,128,128,64] (post-ReLU tap)
-        self._pack_join()
         p4, arg4 = ops.maxpool(s2, want_arg=True)
         s4, b_l1 = self.res_layer(p4, 1, 1, 2)                 # 64x64x64
         s8, b_l2 = self.res_layer(s4, 2, 2, 2)                 # 32x32x128

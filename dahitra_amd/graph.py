@@ -25,8 +25,6 @@ undone (parameters, BN buffers and optimizer state are restored), so the first g
 How launches become a graph is written once, `_Recorded._capture`, for the train steps (GraphedTrainStep and the two xBD steps
 that derive from it) and for the recorded evaluation steps (`_RecordedEval`).  A train step is its hooks: `_forward_split`,
 `_loss_and_grad`, `_eager_body` and `_update`, the class attributes INPUTS and ENGINE_LEVEL, and `max_norm`."""
-import os
-
 import torch
 import torch.distributed as dist
 
@@ -129,7 +127,7 @@ class GraphedTrainStep(_Recorded):
             self.loss = self._capture([net], dev, warm, [counted(self._split_first), counted(self._second)], warmup)[0]
             # graph 2 replays beside RCCL's kernels and must hold none
             self.persist_bn_launches = tuple(counts)
-            if self.persist_bn_launches[1] and os.environ.get("DAHITRA_OVERLAP_PERSIST_BN") != "1":
+            if self.persist_bn_launches[1]:
                 raise RuntimeError("dahitra_amd: %d persistent BatchNorm launches were recorded into the graph that overlaps the "
                                    "gradient all-reduce" % self.persist_bn_launches[1])
         else:
@@ -186,8 +184,8 @@ class GraphedTrainStep(_Recorded):
 
     def _body(self, include_opt):
         """the one-graph step: `_engine_pass` with the whole backward for an ENGINE_LEVEL class, the autograd step
-        `_eager_body` otherwise (DAHITRA_GRAPH_AUTOGRAD=1: A/B switch of an ENGINE_LEVEL class back to it)"""
-        if not self.ENGINE_LEVEL or os.environ.get("DAHITRA_GRAPH_AUTOGRAD") == "1":
+        `_eager_body` otherwise"""
+        if not self.ENGINE_LEVEL:
             return self._eager_body(include_opt)
         loss = self._engine_pass(self.net._engine.backward)
         if include_opt:
@@ -223,9 +221,6 @@ class GraphedTrainStep(_Recorded):
     def _second(self):
         """graph 2 (layer2 / layer1 / stem backward) replays WHILE the all-reduce of the arena tail runs on RCCL's stream: its
         BatchNorm backward must not be the persistent one-launch form, whose device-wide barrier needs every CU"""
-        if os.environ.get("DAHITRA_OVERLAP_PERSIST_BN") == "1":      # EXPERIMENT (one rank only): what the two-pass BatchNorm of graph 2 costs
-            self.net._engine.backward_second()
-            return
         with ops.no_persist_bn():
             self.net._engine.backward_second()
 

@@ -311,43 +311,6 @@ class WgradPlan:
 _WGRAD_PLAN = None
 
 
-class SideStream:
-    """A second HIP stream for launches that nothing downstream of the current kernel chain waits for (a weight gradient
-    next to the low-occupancy token-side backward kernels).  fork(): the side stream waits for everything enqueued so far
-    on the current stream; launches inside `with side:` go to it; join(): the current stream waits for the side stream.
-    Works under HIP-graph capture (the fork / join become graph dependencies).  Tensors handed to side launches are kept
-    alive until the join (the caching allocator must not give their memory to a later main-stream launch)."""
-
-    def __init__(self, device):
-        self.stream, self.keep, self.active, self._ctx = torch.cuda.Stream(device=device), [], False, None
-
-    def fork(self, *tensors):
-        global _PERSIST_BLOCK
-        self.stream.wait_stream(torch.cuda.current_stream())
-        self.keep += [t for t in tensors if t is not None]
-        if not self.active:
-            _PERSIST_BLOCK += 1       # until the join: no device-wide-barrier kernels next to the side stream's launches
-        self.active = True
-        return self
-
-    def __enter__(self):
-        self._ctx = torch.cuda.stream(self.stream)
-        self._ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        self._ctx.__exit__(*exc)
-        self._ctx = None
-        return False
-
-    def join(self):
-        global _PERSIST_BLOCK
-        if self.active:
-            torch.cuda.current_stream().wait_stream(self.stream)
-            self.keep, self.active = [], False
-            _PERSIST_BLOCK -= 1
-
-
 # ---- convolution / linear ------------------------------------------------------------------------
 PROFILE = None       # set to {} by bench.py to collect (events, algorithmic flops, algorithmic bytes) per launch
 REPLAY = None        # set to {"key": class, "calls": []} by bench.py for ONE eager step: the C calls of that kernel class as
@@ -973,14 +936,14 @@ _BN_SYNC = {}
 BN_BWD_PERSIST = os.environ.get("DAHITRA_NO_PERSIST_BN", "0") != "1"      # True: where faster; "force": wherever supported (tests)
 if os.environ.get("DAHITRA_PERSIST_BN_FORCE", "0") == "1":
     BN_BWD_PERSIST = "force"
-_PERSIST_BLOCK = 0          # > 0: inside no_persist_bn() -- another stream may run beside the launches made here
+_PERSIST_BLOCK = 0          # > 0: inside no_persist_bn(), its only writer -- another stream may run beside the launches made here
 BN_PERSIST_LAUNCHES = 0     # persistent launches issued (or recorded into a graph) by this process: what tests assert the guard on
 
 
 class no_persist_bn:
     """`with ops.no_persist_bn():` BatchNorm backward takes the two-pass kernels.  The persistent form (dh_bn_bwd_persist)
     holds a device-wide barrier across 256 one-per-CU workgroups: it must not be launched where a kernel of another
-    stream -- the RCCL all-reduce of the overlapped data-parallel step, a side-stream weight gradient -- may hold CUs."""
+    stream -- the RCCL all-reduce of the overlapped data-parallel step -- may hold CUs."""
 
     def __enter__(self):
         global _PERSIST_BLOCK

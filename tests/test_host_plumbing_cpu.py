@@ -188,7 +188,7 @@ def test_staged_levels_advance_in_rounds_and_launch_between_them(monkeypatch):
 
     monkeypatch.setattr(ops, "EncoderBatch", FakeBatch)
     import types
-    host = types.SimpleNamespace(level_streams=False, _lstreams=[])          # the two attributes the method reads
+    host = types.SimpleNamespace()          # the method reads no attribute of its host
     out = engine.Engine._run_staged(host, [level("a", 1), level("b", 3), level("c", 0)])
     assert out == ["A", "B", "C"]
     assert log == [("open", True), ("a", 0), ("b", 0), "launch", ("b", 1), "launch", ("b", 2), "launch", "launch", "close"]
