@@ -48,6 +48,18 @@ one launch per batch as well (dh_xbd_augment_warp_u8), with `draw_unet_params` f
     differ by one in a byte).  Without `colour=True` the operations are drawn, reported as `skipped` and not applied.
   * Not built: clahe (OpenCV's 8-bit Lab tables) and imgaug's elastic transform, each drawn by under 2 % of the samples.  Both
     draw functions draw them, so the `random` stream stands where the script's does, and report them as `skipped`.
+
+The set the scripts train on comes from the same resident pipeline.  Both scan every post-disaster label for the classes it
+holds, cut their one folder 90 / 10 with sklearn's train_test_split and train on an index list in which files with damage repeat
+(train.py:397-429, train_unettransformer.py:499-522).  `class_table` / `file_classes` read that scan off the resident labels in
+one launch (ops.xbd_class_table, dh_xbd_class_table_u8); `split_indices`, `train_indices` and `unet_train_indices` are the split
+and the two lists on the host; `trainset` / `unet_trainset` do a script's lines in one call; and `indices=` / `drop_last=` of
+`batches`, `unet_batches` and models/xbd.unet_val_batches run an epoch over such a list, a repeated index reading the same
+resident source again:
+
+    train_idxs, val_idxs = pipe.unet_trainset(seed)
+    for batch in pipe.unet_batches(16, 256, random.Random(seed + 321), indices=train_idxs, drop_last=True): ...
+    for batch in xbd.unet_val_batches(pipe, 16, 256, indices=val_idxs): ...
 """
 import collections
 import ctypes
@@ -55,6 +67,7 @@ import functools
 import glob
 import math
 import os
+import random
 
 import numpy as np
 import torch
@@ -750,6 +763,93 @@ def unet_colour_reference_u8(img6_u8, colour):
     return out
 
 
+# ---- the scripts' training set: the 90 / 10 split and the oversampled index lists (train.py:397-429, ----
+# ---- train_unettransformer.py:499-522) ----
+
+def split_indices(n, test_size=0.1, seed=0):
+    """(train_idxs0, val_idxs), int64 arrays: what sklearn.model_selection.train_test_split(np.arange(n), test_size=test_size,
+    random_state=seed) returns, restated on numpy so that the product does not import sklearn: n_test = ceil(test_size * n),
+    perm = np.random.RandomState(seed).permutation(n), validation = perm[:n_test], training = perm[n_test:].  Equal to sklearn
+    on a committed fixture (tests/golden/xbd_split.json, written by tools/make_xbd_split_golden.py).  test_size is a fraction
+    inside (0, 1), as the scripts pass it (sklearn also takes a count; this does not).  ValueError where sklearn raises one: a
+    test_size outside (0, 1), n < 1, or a split that leaves no training sample (n = 1 is one)."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("split_indices: n %r is no positive integer" % (n,))
+    if isinstance(test_size, bool) or not isinstance(test_size, (float, np.floating)) or not 0 < test_size < 1:
+        raise ValueError("split_indices: test_size %r is no fraction inside (0, 1)" % (test_size,))
+    n_test = int(math.ceil(test_size * n))
+    if n - n_test < 1:
+        raise ValueError("split_indices: with n = %d and test_size = %r the training set is empty" % (n, test_size))
+    perm = np.random.RandomState(seed).permutation(int(n)).astype(np.int64)
+    return perm[n_test:], perm[:n_test]
+
+
+def _class_rows(file_classes, who):
+    fc = np.asarray(file_classes)
+    if fc.ndim != 2 or fc.shape[1] != 4 or fc.dtype != np.bool_:
+        raise ValueError("%s: file_classes is a bool array [n, 4] (GpuXbdPipeline.file_classes), got %s %s" % (who, fc.shape, fc.dtype))
+    return fc
+
+
+def _index_list(idxs, rows, who):
+    idxs = [int(i) for i in idxs]
+    if any(not 0 <= i < rows for i in idxs):
+        raise ValueError("%s: an index of train_idxs0 lies outside the %d rows of file_classes" % (who, rows))
+    return idxs
+
+
+def unet_train_indices(file_classes, train_idxs0):
+    """train_idxs of xBD_code/train_unettransformer.py:513-520, an int64 array: every index of train_idxs0 once, once more if
+    the file holds any of classes 2 to 4 (file_classes[i, 1:].max()), once more if it holds class 4 (file_classes[i, 3]), in
+    the order of train_idxs0.  file_classes: the bool [n, 4] array of GpuXbdPipeline.file_classes.  It draws nothing."""
+    fc = _class_rows(file_classes, "unet_train_indices")
+    out = []
+    for i in _index_list(train_idxs0, len(fc), "unet_train_indices"):
+        out += [i] * (1 + int(fc[i, 1:].any()) + int(fc[i, 3]))
+    return np.asarray(out, dtype=np.int64)
+
+
+def train_indices(file_classes, train_idxs0, rng, files=None):
+    """(train_idxs, non_zero_bldg, non_zero_dmg) of xBD_code/train.py:414-425 (train_loc.py and train_GAN.py use the same
+    lines): in the order of train_idxs0, an index is taken if its file holds any building -- a file without one is dropped --
+    and taken (again) if `rng.random() > 0.5` and the file holds any of classes 2 to 4.  The draw is made for EVERY index,
+    whether or not the file has damage (`and` evaluates it first), so afterwards `rng` (a random.Random, or the `random` module)
+    stands len(train_idxs0) calls of random() further.  The two counters are the script's.
+    files: None -- row i of file_classes is file i, the set the script MEANT.  With the list of the files' paths -- the script
+    AS EXECUTED: train.py:405-406 appends a file's row a second time when its path contains 'AOI', so file_classes[i] there is
+    the row of an earlier file for every i behind the first such path; `files` rebuilds that doubled table and indexes it as the
+    script does.  The two are the same list when no path contains 'AOI'."""
+    fc = _class_rows(file_classes, "train_indices")
+    if files is not None:
+        files = [str(f) for f in files]
+        if len(files) != len(fc):
+            raise ValueError("train_indices: %d files for %d rows of file_classes" % (len(files), len(fc)))
+        fc = np.repeat(fc, [2 if 'AOI' in f else 1 for f in files], axis=0)
+    out, non_zero_bldg, non_zero_dmg = [], 0, 0
+    for i in _index_list(train_idxs0, len(fc), "train_indices"):
+        if fc[i].any():
+            out.append(i)
+            non_zero_bldg += 1
+        if rng.random() > 0.5 and fc[i, 1:].any():
+            out.append(i)
+            non_zero_dmg += 1
+    return np.asarray(out, dtype=np.int64), non_zero_bldg, non_zero_dmg
+
+
+def epoch_order(n, indices):
+    """the source indices of an epoch over n samples as a fresh list: every sample once (indices None), or `indices`, which may
+    repeat; ValueError for an empty list or an index outside the samples"""
+    if indices is None:
+        return list(range(n))
+    order = [int(i) for i in indices]
+    if not order:
+        raise ValueError("indices: an epoch over no sample")
+    outside = [i for i in order if not 0 <= i < n]
+    if outside:
+        raise ValueError("indices: %d lies outside the %d samples" % (outside[0], n))
+    return order
+
+
 class GpuXbdPipeline:
     def __init__(self, pre_u8, post_u8, pre_mask_u8, post_label_u8, files=None):
         """pre_u8, post_u8: [n_src, H, W, 3] uint8 device tensors; pre_mask_u8 (0 / 255) and post_label_u8 (0 .. 4):
@@ -766,6 +866,7 @@ class GpuXbdPipeline:
         self.unet_skipped = collections.Counter()      # unet_batches: the drawn operations of the last epoch that are not built
         self.unet_applied = collections.Counter()      # ... and, with colour=True, the colour operations that were applied
         self._colour_ws = None
+        self._class_table = None
 
     @classmethod
     def from_image_dir(cls, images_dir, device='cuda:0', files=None):
@@ -796,6 +897,46 @@ class GpuXbdPipeline:
 
     def __len__(self):
         return self.pre.shape[0]
+
+    def class_table(self):
+        """[len(self), 6] int64 host array, read-only: how many pixels of every resident post-disaster label equal 0, 1, 2, 3, 4
+        or lie above 4 (ops.XBD_CLASS_COLUMNS) -- ops.xbd_class_table on the resident stack, one launch and one device-to-host
+        read.  Kept on the pipeline: a second call returns the same array without a launch (the sources do not change)."""
+        if self._class_table is None:
+            table = ops.xbd_class_table(self.post_label).cpu().numpy().astype(np.int64)
+            table.setflags(write=False)
+            self._class_table = table
+        return self._class_table
+
+    def file_classes(self):
+        """the bool [len(self), 4] array the training scripts call file_classes (train.py:397-407,
+        train_unettransformer.py:499-506): fl[c - 1] = c in msk1 for c = 1 .. 4, here class_table()[:, 1:5] > 0 -- no label
+        is opened or copied back.  (train.py's table holds the rows of 'AOI' paths twice; train_indices' `files` restates
+        that.)"""
+        return self.class_table()[:, 1:5] > 0
+
+    def unet_trainset(self, seed=0):
+        """(train_idxs, val_idxs) of xBD_code/train_unettransformer.py:499-520 from this one folder: file_classes from the
+        resident labels, split_indices(len(self), 0.1, seed), and unet_train_indices on the training part -- train_idxs is
+        already oversampled and repeats indices; val_idxs is the held-out tenth.  Feed them to unet_batches(..., indices=
+        train_idxs, drop_last=True) and models.xbd.unet_val_batches(self, ..., indices=val_idxs).  No image is copied.  (The
+        script then seeds `random` and numpy with seed + 321: the epochs' rng is the caller's.)"""
+        train_idxs0, val_idxs = split_indices(len(self), 0.1, seed)
+        return unet_train_indices(self.file_classes(), train_idxs0), val_idxs
+
+    def trainset(self, seed=0, rng=None):
+        """(train_idxs, val_idxs, rng) of xBD_code/train.py:397-429 from this one folder, the script as executed:
+        file_classes from the resident labels, split_indices(len(self), 0.1, seed), then train_indices with `files=self.files`
+        -- so the doubled rows of paths that contain 'AOI' (train.py:405-406) are reproduced; call train_indices(
+        self.file_classes(), train_idxs0, rng) for the set the script meant.  rng defaults to random.Random(seed + 321), the
+        state the script's random.seed(seed + 321) leaves, and is returned so that the caller's epochs go on drawing from it as
+        the script's loader does.  Prints the script's counts line: non_zero_bldg non_zero_dmg len(train_idxs) len(val_idxs)."""
+        if rng is None:
+            rng = random.Random(seed + 321)
+        train_idxs0, val_idxs = split_indices(len(self), 0.1, seed)
+        train_idxs, non_zero_bldg, non_zero_dmg = train_indices(self.file_classes(), train_idxs0, rng, self.files)
+        print(non_zero_bldg, non_zero_dmg, len(train_idxs), len(val_idxs))
+        return train_idxs, val_idxs, rng
 
     def make_batch(self, indices, crop, params=None, train=True, jitter=None, dilate=0):
         """indices: source samples of the batch; params: one row per sample in PARAM_FIELDS order (draw_train_params), or None
@@ -870,7 +1011,7 @@ class GpuXbdPipeline:
             msk = ops.xbd_msk_dilate(msk, dilate)
         return {'img': img, 'msk': msk, 'lbl_msk': lbl, 'fn': [self.files[int(i)] for i in indices]}
 
-    def batches(self, batch_size, crop, train=True, rng=None, jitter_gen=None, dilate=0):
+    def batches(self, batch_size, crop, train=True, rng=None, jitter_gen=None, dilate=0, indices=None, drop_last=False):
         """one epoch.  train: `rng` (a random.Random) shuffles the samples, then every sample draws its parameters with
         draw_train_params, in batch order (the reference's DataLoader shuffles with torch's generator and draws in its worker
         processes: the order of the samples is this loader's own, a sample's draws are the reference's).  Otherwise the
@@ -879,19 +1020,27 @@ class GpuXbdPipeline:
         jitter_gen: a torch.Generator; every training sample whose draw_train_params flag is set then draws its ColorJitter
         parameters from it (draw_jitter_params, pre then post, in sample order) and gets them applied.  None: no ColorJitter
         and no draw from any torch generator.
-        dilate: make_batch's, for every batch of a training epoch (0: off; ValueError with train=False).  It draws nothing."""
+        dilate: make_batch's, for every batch of a training epoch (0: off; ValueError with train=False).  It draws nothing.
+        indices: None -- every sample once -- or the epoch's source indices, which may repeat (trainset / unet_trainset's
+        oversampled train_idxs, or val_idxs): a training epoch shuffles a copy of the list with `rng`, a validation epoch takes
+        it in the order given.  A repeated index reads the same resident source again; nothing is copied.  ValueError, before
+        any launch, for an empty list or an index outside the samples.
+        drop_last: stop in front of a batch shorter than batch_size, as the scripts' DataLoader(drop_last=True): the epoch then
+        has len(indices) // batch_size batches, their steps_per_epoch."""
         _, H, W, _ = self.pre.shape
         if dilate and not train:
             raise ValueError("dilate: the dilated masks are training targets; the reference's ValData does not dilate (train=False)")
         if not train and not crop == H == W:
             raise ValueError("a validation epoch takes whole images: crop %d is not the %dx%d image" % (crop, H, W))
-        order = list(range(len(self)))
+        order = epoch_order(len(self), indices)
         if train:
             if rng is None:
                 raise ValueError("a training epoch draws from `rng` (a random.Random)")
             rng.shuffle(order)
         for s in range(0, len(order), batch_size):
             ind = order[s:s + batch_size]
+            if drop_last and len(ind) < batch_size:
+                break
             if not train:
                 yield self.make_batch(ind, crop, None, train)
                 continue
@@ -957,23 +1106,27 @@ class GpuXbdPipeline:
             msk = ops.xbd_msk_dilate(msk, dilate)
         return {'img': img, 'msk': msk, 'lbl_msk': self._zero_lbl, 'fn': [self.files[int(i)] for i in indices]}
 
-    def unet_batches(self, batch_size, crop, rng, dilate=5, colour=False, np_rng=None):
+    def unet_batches(self, batch_size, crop, rng, dilate=5, colour=False, np_rng=None, indices=None, drop_last=False):
         """one training epoch of xBD_code/train_unettransformer.py's loader: `rng` (a random.Random) shuffles the samples, then
         every sample draws with draw_unet_params, in batch order (the sample order is this loader's own, as in `batches`; a
         sample's draws are the script's).  Yields make_unet_batch's dicts.  `self.unet_skipped` counts, over the epoch, the
         drawn operations that are not applied (collections.Counter of draw_unet_params' names).
         colour=True draws with draw_unet_colour instead -- the same stream -- and applies the colour operations
         (make_unet_batch's `colour`); `self.unet_applied` counts them under the same names.  np_rng: the np.random.RandomState
-        gauss_noise draws from (the script draws from numpy's global legacy generator); without one gauss_noise stays skipped."""
+        gauss_noise draws from (the script draws from numpy's global legacy generator); without one gauss_noise stays skipped.
+        indices, drop_last: as in `batches` -- the script's epoch is unet_batches(16, 256, rng, indices=train_idxs,
+        drop_last=True) with unet_trainset's train_idxs."""
         if rng is None:
             raise ValueError("a training epoch draws from `rng` (a random.Random)")
         _, H, W, _ = self.pre.shape
-        order = list(range(len(self)))
+        order = epoch_order(len(self), indices)
         rng.shuffle(order)
         self.unet_skipped = collections.Counter()
         self.unet_applied = collections.Counter()
         for s in range(0, len(order), batch_size):
             ind = order[s:s + batch_size]
+            if drop_last and len(ind) < batch_size:
+                break
             rows, colours = [], []
             for _ in ind:
                 if colour:

@@ -8,7 +8,8 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
     unet_loss(out, msks, lbl_msk, labels)             xBD_code/train_unettransformer.py:438-456 (five ComboLoss terms + 8 * the
         class-weighted cross-entropy of the logits masked by lbl_msk > 0; uint8 masks, one pass; labels='damage' derives the label)
     unet_scheduler(optimizer)                         train_unettransformer.py:536      (MultiStepLR, gamma 0.6)
-    unet_val_batches(pipe, batch_size, crop)          train_unettransformer.py:288-352  (ValData: the fixed crop at (512, 512))
+    unet_val_batches(pipe, batch_size, crop, indices) train_unettransformer.py:288-352  (ValData: the fixed crop at (512, 512);
+        indices: the val_idxs of pipe.unet_trainset(), the tenth the script holds out of its one folder)
     train_epoch_unet(current_epoch, model, optimizer, scheduler, batches)   train_unettransformer.py:421-486 (no clip; the meters
         Loss / loss2 / loss3 / Dice from ONE host read per epoch; `seg_loss`, `ce_loss` and `scaler` are not arguments here)
     clip_grad_norm_(parameters, max_norm)             torch.nn.utils.clip_grad_norm_ as called at train.py:373
@@ -526,12 +527,17 @@ def unet_scheduler(optimizer):
     return torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=list(UNET_MILESTONES), gamma=UNET_GAMMA)
 
 
-def unet_val_batches(pipe, batch_size=16, crop=256):
+def unet_val_batches(pipe, batch_size=16, crop=256, indices=None):
     """The script's ValData (lines 288-352) from a GpuXbdPipeline: the samples in order, the fixed crop at x0 = y0 = 512, no
     augmentation, ValData's masks (train=False) -- what validate / evaluate_val take.  The script's val_batch_size is 16 and its
-    DataLoader keeps the ragged last batch."""
-    for s in range(0, len(pipe), batch_size):
-        ind = list(range(s, min(s + batch_size, len(pipe))))
+    DataLoader keeps the ragged last batch.
+    indices: None -- every sample -- or the source indices to validate on, in the order given: the `val_idxs` of
+    pipe.unet_trainset(), the tenth the script holds out of the one folder it trains on.  ValueError, before any launch, for an
+    empty list or an index outside the samples."""
+    from ..datasets.xbd_pipeline import epoch_order
+    order = epoch_order(len(pipe), indices)
+    for s in range(0, len(order), batch_size):
+        ind = order[s:s + batch_size]
         yield pipe.make_batch(ind, crop, [[512, 512, 0, 0, 0, 0, 0, crop, crop]] * len(ind), train=False)
 
 

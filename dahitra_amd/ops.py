@@ -2506,6 +2506,27 @@ def xbd_msk_dilate(msk_u8, k=5, out=None):
     return out
 
 
+# ---- xBD class table: the bytes of every class in every resident label (csrc/xbd_classes.hip) ----------------
+XBD_CLASS_COLUMNS = ("class0", "class1", "class2", "class3", "class4", "above4")
+
+
+def xbd_class_table(labels_u8, out=None):
+    """How many bytes of every label equal 0, 1, 2, 3, 4 or lie above 4, in one pass on the device (dh_xbd_class_table_u8).
+    labels_u8 [n, H, W] uint8, contiguous -- GpuXbdPipeline's post_label stack, or a slice of it along the first axis: no
+    alignment is asked -- -> int32 [n, 6], columns XBD_CLASS_COLUMNS; a row sums to H * W.  The training scripts' file_classes
+    (fl[c - 1] = c in msk1) is table[:, 1:5] > 0.  A memset node and one launch; integer adds only, so the table is exact and the
+    same bits on every call.  out: an [n, 6] int32 buffer to write into; every word of it is overwritten.
+    ValueError, before any launch, for a wrong rank or dtype, n == 0 or an empty image, H * W > 2^31 - 1, tensors on different
+    devices or non-contiguous storage; HipLibraryError for CPU tensors (there is no CPU path)."""
+    a = _Args("xbd_class_table", cpu_error=True)
+    n, H, W = a.tensor("labels_u8", labels_u8, torch.uint8, lambda t: t.dim() == 3 and t.numel() > 0 and t.shape[1] * t.shape[2] < 2 ** 31,
+                       "[n, H, W], not empty, H * W <= 2^31 - 1").shape
+    out = a.out(out, torch.int32, (n, len(XBD_CLASS_COLUMNS)))
+    a.placed()
+    _call("dh_xbd_class_table_u8", P(labels_u8), n, H * W, P(out), S())
+    return out
+
+
 XBD_WARP_TILE = (32, 32)         # (TH, TW) of dh_xbd_augment_warp_u8's output tile: dh_xbd_augment_warp_tile_h / _tile_w
 XBD_WARP_PARAM_WORDS = 12        # x0, y0, vflip, rot, sx, sy, warp, chan, dR, dG, dB, 0
 

@@ -997,6 +997,21 @@ int dh_xbd_fill_holes_ws_bytes(int N, int H, int W, long* bytes);
 int dh_xbd_fill_holes_u8(const unsigned char* src, int N, int H, int W, int background, unsigned char* dst, void* ws,
                          long ws_bytes, void* stream);
 
+/* ---- xBD class table: the bytes of every class in every resident label (csrc/xbd_classes.hip) --------------------------------
+ * dh_xbd_class_table_u8: labels [n][hw] uint8, contiguous (the pipeline's post_label stack, or a slice of it: no alignment is
+ * asked of the pointer or of hw) -> counts [n][6] int32: columns 0 .. 4 the number of bytes of file f equal to 0 .. 4, column 5
+ * the number above 4; a row sums to hw.  `file_classes` of xBD_code/train.py:397-407 and train_unettransformer.py:499-506
+ * (fl[c - 1] = c in msk1) is counts[:, 1:5] > 0.  All 6 n words are written whatever they held: a memset node on the stream
+ * clears them, then one launch adds.  A workgroup counts dh_xbd_class_table_chunk() bytes of one file: the bytes in front of the
+ * first 16-byte aligned address and behind the last whole piece one by one, the body with 16-byte loads; counts are kept in
+ * 32-bit registers (never in packed narrow lanes), summed across the wave and then across the workgroup through LDS, and reach
+ * memory as at most one integer atomic per class and workgroup.  Integer adds only: exact, and the same bits on every call.
+ * Nothing outside labels is read and labels is not written.
+ * Refused (nothing is written, non-zero, dh_last_error begins with xbd_class_table): a null pointer, n < 1, hw < 1,
+ * hw > 2^31 - 1. */
+int dh_xbd_class_table_chunk(void);
+int dh_xbd_class_table_u8(const unsigned char* labels, long n, long hw, int* counts, void* stream);
+
 /* ---- the change-detection evaluator's picture (models/evaluator.py:118-131; csrc/cd_visual.hip) ------------------------------
  * dh_cd_eval_vis_u8: A, B [N][3][H][W] fp32 (as the net receives them), logits [N][C][H][W] fp32, label [N][H][W] int64 ->
  * out [4 * rows * H][cols * W][3] uint8 RGB, cols = min(8, N), rows = ceil(N / cols) (make_grid, padding 0): four bands of
