@@ -15,7 +15,6 @@ namespace {
 constexpr int VC_THREADS = 256;
 constexpr int VC_WAVES = VC_THREADS / 64;
 constexpr int VC_MAX_WORKGROUPS = 512;      // over the whole batch: two workgroups per CU, the rest is the grid-stride loop
-constexpr int VC_NCOUNT = 15;               // 3 image counters, then (tp, fn, fp) of each of the 4 classes
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -49,27 +48,30 @@ __global__ __launch_bounds__(VC_THREADS) void xbd_val_clear_kernel(unsigned long
     if (i < n) image_counts[i] = 0;
 }
 
-// grid (gx, B): image blockIdx.y, groups of 4 pixels strided over gx workgroups
+// grid (gx, B): image blockIdx.y, groups of 4 pixels strided over gx workgroups.  ND: the damage classes -- logits [B][ND + 1][HW],
+// counters 3 + 3 ND (4: train.py; 3: train_adapt.py, whose net merges destroyed into class 3)
+template <int ND>
 __global__ __launch_bounds__(VC_THREADS) void xbd_val_count_kernel(const float* __restrict__ logits,
                                                                    const unsigned char* __restrict__ msk0, long msk0_stride,
                                                                    const unsigned char* __restrict__ lbl, int W, long HW,
                                                                    float thr, int select,
                                                                    unsigned long long* __restrict__ image_counts,
                                                                    unsigned long long* __restrict__ class_counts) {
-    __shared__ unsigned red[VC_WAVES][VC_NCOUNT];
+    constexpr int NCOUNT = 3 + 3 * ND;
+    __shared__ unsigned red[VC_WAVES][NCOUNT];
     const int j = blockIdx.y;
-    const float* lg = logits + (long)j * 5 * HW;
+    const float* lg = logits + (long)j * (ND + 1) * HW;
     const unsigned char* m0 = msk0 + (long)j * msk0_stride;
     const unsigned char* lb = lbl + (long)j * HW;
     // plane c starts at lg + c * HW: with HW % 4 != 0 the planes are aligned differently, so each one decides for itself
-    bool vl[5];
+    bool vl[ND + 1];
 #pragma unroll
-    for (int c = 0; c < 5; ++c) vl[c] = (reinterpret_cast<uintptr_t>(lg + c * HW) & 15) == 0;
+    for (int c = 0; c < ND + 1; ++c) vl[c] = (reinterpret_cast<uintptr_t>(lg + c * HW) & 15) == 0;
     const bool vm = (reinterpret_cast<uintptr_t>(m0) & 3) == 0, vb = (reinterpret_cast<uintptr_t>(lb) & 3) == 0;
 
-    unsigned cnt[VC_NCOUNT];
+    unsigned cnt[NCOUNT];
 #pragma unroll
-    for (int i = 0; i < VC_NCOUNT; ++i) cnt[i] = 0;
+    for (int i = 0; i < NCOUNT; ++i) cnt[i] = 0;
 
     const long groups = (HW + 3) >> 2;
 #pragma unroll 2
@@ -77,10 +79,10 @@ __global__ __launch_bounds__(VC_THREADS) void xbd_val_count_kernel(const float* 
         const long p0 = g << 2;
         const int n = HW - p0 >= 4 ? 4 : (int)(HW - p0);
         const bool full = n == 4;
-        float x[5][4];
+        float x[ND + 1][4];
         unsigned gt[4], tg[4];
 #pragma unroll
-        for (int c = 0; c < 5; ++c) load4(lg + c * HW + p0, full && vl[c], n, x[c]);
+        for (int c = 0; c < ND + 1; ++c) load4(lg + c * HW + p0, full && vl[c], n, x[c]);
         load4(m0 + p0, full && vm, n, gt);
         load4(lb + p0, full && vb, n, tg);
         int row = 0, col = 0;
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(VC_THREADS) void xbd_val_count_kernel(const float* 
                 float best = sigmoidf_(x[1][k]);
                 unsigned arg = 0;
 #pragma unroll
-                for (int c = 2; c < 5; ++c) {
+                for (int c = 2; c < ND + 1; ++c) {
                     const float s = sigmoidf_(x[c][k]);
                     if (s > best) { best = s; arg = c - 1; }
                 }
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(VC_THREADS) void xbd_val_count_kernel(const float* 
                 if (sel) {
                     const unsigned t = tg[k];
 #pragma unroll
-                    for (unsigned c = 0; c < 4; ++c) {
+                    for (unsigned c = 0; c < (unsigned)ND; ++c) {
                         cnt[3 + 3 * c] += pred == c && t == c;
                         cnt[4 + 3 * c] += pred != c && t == c;
                         cnt[5 + 3 * c] += pred == c && t != c;
@@ -127,12 +129,12 @@ __global__ __launch_bounds__(VC_THREADS) void xbd_val_count_kernel(const float* 
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-    for (int i = 0; i < VC_NCOUNT; ++i) {
+    for (int i = 0; i < NCOUNT; ++i) {
         const unsigned s = wave_sum_u32(cnt[i]);
         if (lane == 0) red[wave][i] = s;
     }
     __syncthreads();
-    if (threadIdx.x < VC_NCOUNT) {
+    if (threadIdx.x < NCOUNT) {
         unsigned s = 0;
 #pragma unroll
         for (int w = 0; w < VC_WAVES; ++w) s += red[w][threadIdx.x];
@@ -269,9 +271,10 @@ __global__ __launch_bounds__(VC_THREADS) void xbd_val_sweep_kernel(const float* 
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
-extern "C" int dh_xbd_val_count(const float* logits, const unsigned char* msk0, long msk0_image_stride,
-                                const unsigned char* lbl, int B, int H, int W, float thr, int select, long long* image_counts,
-                                long long* class_counts, void* stream) {
+namespace {
+template <int ND>
+int xbd_val_count_impl(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl, int B, int H,
+                       int W, float thr, int select, long long* image_counts, long long* class_counts, void* stream) {
     DH_REQUIRE(logits && msk0 && lbl && image_counts && class_counts, "xbd_val_count: null pointer");
     DH_REQUIRE(B >= 1 && B <= 65535, "xbd_val_count: B=%d must be in 1..65535", B);
     DH_REQUIRE(H >= 1 && W >= 1, "xbd_val_count: empty image %dx%d", H, W);
@@ -293,11 +296,29 @@ extern "C" int dh_xbd_val_count(const float* logits, const unsigned char* msk0, 
     int gx = dh_cdiv((HW + 3) / 4, VC_THREADS);
     const int cap = VC_MAX_WORKGROUPS / B > 0 ? VC_MAX_WORKGROUPS / B : 1;
     if (gx > cap) gx = cap;
-    hipLaunchKernelGGL(xbd_val_count_kernel, dim3(gx, B), dim3(VC_THREADS), 0, ST(stream), logits, msk0, msk0_image_stride, lbl, W,
+    hipLaunchKernelGGL(xbd_val_count_kernel<ND>, dim3(gx, B), dim3(VC_THREADS), 0, ST(stream), logits, msk0, msk0_image_stride, lbl, W,
                        HW, thr, select, reinterpret_cast<unsigned long long*>(image_counts),
                        reinterpret_cast<unsigned long long*>(class_counts));
     DH_CHECK_LAUNCH("xbd_val_count");
     return 0;
+}
+}  // namespace
+
+extern "C" int dh_xbd_val_count(const float* logits, const unsigned char* msk0, long msk0_image_stride,
+                                const unsigned char* lbl, int B, int H, int W, float thr, int select, long long* image_counts,
+                                long long* class_counts, void* stream) {
+    return xbd_val_count_impl<4>(logits, msk0, msk0_image_stride, lbl, B, H, W, thr, select, image_counts, class_counts, stream);
+}
+
+// dh_xbd_val_count for logits [B][n_damage + 1][H][W] and class_counts [n_damage][3]: n_damage 4 is that call, 3 the pass of
+// xBD_code/train_adapt.py:262-280 (three damage classes, lbl 0 .. 2)
+extern "C" int dh_xbd_val_count_n(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl,
+                                  int n_damage, int B, int H, int W, float thr, int select, long long* image_counts,
+                                  long long* class_counts, void* stream) {
+    DH_REQUIRE(n_damage == 3 || n_damage == 4, "xbd_val_count: n_damage=%d is neither 3 nor 4", n_damage);
+    if (n_damage == 3)
+        return xbd_val_count_impl<3>(logits, msk0, msk0_image_stride, lbl, B, H, W, thr, select, image_counts, class_counts, stream);
+    return xbd_val_count_impl<4>(logits, msk0, msk0_image_stride, lbl, B, H, W, thr, select, image_counts, class_counts, stream);
 }
 
 extern "C" int dh_xbd_val_sweep(const float* logits, const unsigned char* msk0, long msk0_image_stride,

@@ -836,6 +836,40 @@ def train_indices(file_classes, train_idxs0, rng, files=None):
     return np.asarray(out, dtype=np.int64), non_zero_bldg, non_zero_dmg
 
 
+def adapt_files(names):
+    """the name filter of xBD_code/train_adapt.py:75 on a list of file names or paths, order kept: a name stays if it contains
+    '_pre_disaster.png' and 'hurricane-michael' or 'AOI' -- xBD's hurricane-michael tiles plus the Ida-BD (AOI) tiles.  What the
+    caller applies to `files` before GpuXbdPipeline.from_image_dir(..., files=...)."""
+    return [f for f in names if ('_pre_disaster.png' in f) and (('hurricane-michael' in f) or ('AOI' in f))]
+
+
+def adapt_train_indices(class_table, files, seed=0):
+    """(train_idxs, val_idxs, n_xbd, n_train_aoi) of xBD_code/train_adapt.py:369-391 from a class table [n, 6] (GpuXbdPipeline.
+    class_table) and the n file names: a file is kept if the sum of its non-zero label bytes, sum(c * table[:, c]), exceeds 500;
+    the kept files are split by name into 'AOI' and the rest; split_indices(len(aoi), 0.15, seed) splits the AOI files;
+    train_idxs = the rest, then the training AOI files, val_idxs = the held-out AOI files -- all as row indices of the table,
+    int64 arrays.  ValueError if column 5 is non-zero (the sum of a byte above 4 cannot be read from the table), if the names do
+    not match the rows, or where split_indices refuses the AOI files (none, or one)."""
+    table = np.asarray(class_table)
+    if table.ndim != 2 or table.shape[1] != 6 or table.dtype.kind not in "iu":
+        raise ValueError("adapt_train_indices: class_table is an integer array [n, 6], got %s %s" % (table.shape, table.dtype))
+    files = [str(f) for f in files]
+    if len(files) != len(table):
+        raise ValueError("adapt_train_indices: %d files for %d rows of class_table" % (len(files), len(table)))
+    if table[:, 5].any():
+        raise ValueError("adapt_train_indices: %d files hold label bytes above 4; their sum is not in the class table"
+                         % int((table[:, 5] != 0).sum()))
+    sums = (table[:, :5].astype(np.int64) * np.arange(5, dtype=np.int64)[None, :]).sum(axis=1)
+    xbd_files, aoi_files = [], []
+    for i, fn in enumerate(files):
+        if sums[i] > 500:
+            (aoi_files if 'AOI' in fn else xbd_files).append(i)
+    tr, va = split_indices(len(aoi_files), 0.15, seed)
+    train_aoi = [aoi_files[x] for x in tr]
+    return (np.asarray(xbd_files + train_aoi, dtype=np.int64), np.asarray([aoi_files[x] for x in va], dtype=np.int64),
+            len(xbd_files), len(train_aoi))
+
+
 def epoch_order(n, indices):
     """the source indices of an epoch over n samples as a fresh list: every sample once (indices None), or `indices`, which may
     repeat; ValueError for an empty list or an index outside the samples"""
@@ -1051,6 +1085,85 @@ class GpuXbdPipeline:
                 jitter.append((draw_jitter_params(jitter_gen), draw_jitter_params(jitter_gen))
                               if flag and jitter_gen is not None else None)
             yield self.make_batch(ind, crop, params, train, jitter if jitter_gen is not None else None, dilate)
+
+    def adapt_trainset(self, seed=0):
+        """(train_idxs, val_idxs) of xBD_code/train_adapt.py:72-78, 369-391 from this one folder (adapt_train_indices on the
+        resident class table and self.files): the files whose non-zero label bytes sum above 500, the AOI ones split 85 / 15 with
+        split_indices(len(aoi), 0.15, seed); train_idxs = the other files, then the training AOI files; val_idxs = the held-out
+        AOI files.  Indices into this pipeline: feed them to adapt_batches(..., indices=train_idxs, drop_last=True) and
+        adapt_batches(..., train=False, indices=val_idxs).  The name filter of line 75 is adapt_files(), applied by the caller
+        to `files` before the pipeline is built.  Prints the script's two count lines.  Host code on the class table: no image
+        is copied, no label is opened.  (The script then seeds `random` and numpy with seed + 321: the epochs' rng is the
+        caller's.)"""
+        train_idxs, val_idxs, n_xbd, n_train_aoi = adapt_train_indices(self.class_table(), self.files, seed)
+        print(n_xbd)
+        print(n_train_aoi, len(train_idxs))
+        return train_idxs, val_idxs
+
+    def make_adapt_batch(self, indices, crop, origins=None, train=True):
+        """A batch of xBD_code/train_adapt.py's TrainData (lines 97-184; train=True) or ValData (196-245), the Ida-BD adaptation
+        of the FOUR-output net, in ONE launch (ops.xbd_adapt_batch, dh_xbd_adapt_batch_u8).  indices: the source samples;
+        origins: one (x0, y0) per sample, the corner of its crop x crop window, or None for (0, 0) -- the script's crop is the
+        whole 1024 tile, where (0, 0) is the only origin.  Returns {'img': fp32 [n, 6, crop, crop] = x / 127 - 1, 'msk': uint8
+        [n, 4, crop, crop], 'lbl_msk': uint8 [n, crop, crop], 'fn'}.  The mask planes are a pure function of the post label
+        byte l: m1 = (l == 1), m2 = (l == 2), m3 = (l in (3, 4)) -- destroyed merged with class 3 --, and m0 = m1 | m2 | m3 for a
+        training batch, whose pre-disaster mask is NOT read (line 165 clears channel 0, line 172 sets the union), or
+        pre_mask > 127 for a validation batch; lbl_msk = argmax(m1, m2, m3), 0 .. 2.  A label byte above 4 sets no plane.  The
+        script's priority lines 170-171 (m1 cleared where m2 or m3 is set, m3 where m2 is) cannot fire on planes cut from one
+        byte, which equals at most one of 1, 2 and 3 / 4; they would matter behind a dilation, which the script has commented
+        out.  The training augmentation of lines 115-146 sits inside a string literal: it is not executed and not built.
+        ValueError for a crop that does not fit, origins that do not match the samples or leave the image, or indices outside
+        the samples."""
+        n = len(indices)
+        _, H, W, _ = self.pre.shape
+        if isinstance(crop, bool) or not isinstance(crop, (int, np.integer)) or not 1 <= crop <= min(H, W):
+            raise ValueError("crop: %r does not fit the %dx%d images" % (crop, H, W))
+        crop = int(crop)
+        if n == 0 or any(not 0 <= int(i) < len(self) for i in indices):
+            raise ValueError("indices %r outside the %d samples" % (list(indices), len(self)))
+        dev = self.pre.device
+        org = None
+        if origins is not None:
+            rows = [tuple(int(v) for v in o) for o in origins]
+            if len(rows) != n or any(len(o) != 2 for o in rows):
+                raise ValueError("origins: %d rows for %d samples, each (x0, y0)" % (len(rows), n))
+            if any(not (0 <= x0 <= W - crop and 0 <= y0 <= H - crop) for x0, y0 in rows):
+                raise ValueError("origins: a %dx%d window at one of %r leaves the %dx%d image" % (crop, crop, rows, H, W))
+            org = torch.as_tensor(rows, dtype=torch.int32).reshape(n, 2).to(dev)
+        idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int32).to(dev)
+        img, msk, lbl = ops.xbd_adapt_batch(self.pre, self.post, self.pre_mask, self.post_label, idx, org, crop, train)
+        return {'img': img, 'msk': msk, 'lbl_msk': lbl, 'fn': [self.files[int(i)] for i in indices]}
+
+    def adapt_batches(self, batch_size, crop, train=True, rng=None, indices=None, drop_last=False):
+        """one epoch of xBD_code/train_adapt.py's loader, make_adapt_batch's dicts.  train: `rng` (a random.Random) shuffles the
+        samples (the sample order is this loader's own, as in `batches`), then every sample draws x0 = rng.randint(0, W - crop)
+        and y0 = rng.randint(0, H - crop), in that order: the two draws of lines 108-109, consumed even at the script's crop of
+        the whole tile, where both are 0 -- a shared `rng` stays in step with the script.  Nothing else is drawn.  Otherwise
+        (ValData) the samples in order, whole images: `crop` must be the (square) image size, ValueError otherwise.
+        indices, drop_last: as in `batches` -- the script's epochs are adapt_batches(1, 1024, True, rng, train_idxs,
+        drop_last=True) and adapt_batches(1, 1024, False, indices=val_idxs) with adapt_trainset's lists."""
+        _, H, W, _ = self.pre.shape
+        if not train and not crop == H == W:
+            raise ValueError("a validation epoch takes whole images: crop %d is not the %dx%d image" % (crop, H, W))
+        if not 1 <= crop <= min(H, W):
+            raise ValueError("crop: %r does not fit the %dx%d images" % (crop, H, W))
+        order = epoch_order(len(self), indices)
+        if train:
+            if rng is None:
+                raise ValueError("a training epoch draws from `rng` (a random.Random)")
+            rng.shuffle(order)
+        for s in range(0, len(order), batch_size):
+            ind = order[s:s + batch_size]
+            if drop_last and len(ind) < batch_size:
+                break
+            origins = None
+            if train:
+                origins = []
+                for _ in ind:
+                    x0 = rng.randint(0, W - crop)
+                    y0 = rng.randint(0, H - crop)
+                    origins.append((x0, y0))
+            yield self.make_adapt_batch(ind, crop, origins, train)
 
     def make_unet_batch(self, indices, crop, rows, dilate=5, colour=None):
         """A training batch of xBD_code/train_unettransformer.py's TrainData, the script that trains DAHiTra proper: rows is one

@@ -22,7 +22,7 @@ DAHITRA_OVERLAP=auto (default) takes this form only where the all-reduce it hide
 the update).  The warm-up steps torch needs before capture are
 undone (parameters, BN buffers and optimizer state are restored), so the first graphed step is step 1.
 
-How launches become a graph is written once, `_Recorded._capture`, for the train steps (GraphedTrainStep and the two xBD steps
+How launches become a graph is written once, `_Recorded._capture`, for the train steps (GraphedTrainStep and the three xBD steps
 that derive from it) and for the recorded evaluation steps (`_RecordedEval`).  A train step is its hooks: `_forward_split`,
 `_loss_and_grad`, `_eager_body` and `_update`, the class attributes INPUTS and ENGINE_LEVEL, and `max_norm`."""
 import torch
@@ -435,6 +435,7 @@ class GraphedTileStep(_RecordedEval):
 
 class _RecordedXbdBatch(_RecordedEval):
     """The static batch of the two validation steps: imgs, channel 0 of msk and lbl_msk, checked and copied by every call"""
+    classes = 4          # damage classes: a four-dimensional msk has classes + 1 channels
 
     def _hold(self, imgs, msk, lbl_msk):
         self._check(imgs, msk, lbl_msk, tuple(imgs.shape))
@@ -453,8 +454,9 @@ class _RecordedXbdBatch(_RecordedEval):
         B, _, H, W = want
         if imgs.dim() != 4 or imgs.shape[1] != 6 or tuple(imgs.shape) != tuple(want):
             raise ValueError("%s: imgs %s, the step holds [%d, 6, %d, %d]" % (name, tuple(imgs.shape), B, H, W))
-        if tuple(msk.shape) not in ((B, 5, H, W), (B, H, W)):
-            raise ValueError("%s: msk %s is neither [%d, 5, %d, %d] nor its channel 0" % (name, tuple(msk.shape), B, H, W))
+        C = self.classes + 1
+        if tuple(msk.shape) not in ((B, C, H, W), (B, H, W)):
+            raise ValueError("%s: msk %s is neither [%d, %d, %d, %d] nor its channel 0" % (name, tuple(msk.shape), B, C, H, W))
         if tuple(lbl_msk.shape) != (B, H, W):
             raise ValueError("%s: lbl_msk %s, the step holds [%d, %d, %d]" % (name, tuple(lbl_msk.shape), B, H, W))
 
@@ -481,9 +483,14 @@ class GraphedXbdEvalStep(_RecordedXbdBatch):
 
     msk is the loader's [B, 5, H, W] mask or its channel 0 ([B, H, W]); only channel 0 is kept.  The shapes are static and
     CHECKED: a batch of another shape (the ragged last one of an epoch) raises ValueError and goes through the eager path
-    (models/xbd.validate does that); nothing is broadcast.  The parameters are read when the graph replays."""
+    (models/xbd.validate does that); nothing is broadcast.  The parameters are read when the graph replays.
+    classes: the damage classes, 4 (default) or 3 -- the four-output net of xBD_code/train_adapt.py, whose pass
+    (lines 262-280) counts three: msk is then [B, 4, H, W] and class_counts [3, 3] (ops.xbd_val_count's `classes`)."""
 
-    def __init__(self, net, imgs, msk, lbl_msk, class_counts, thr=0.3, select='reference', warmup=2):
+    def __init__(self, net, imgs, msk, lbl_msk, class_counts, thr=0.3, select='reference', warmup=2, classes=4):
+        if classes not in ops.XBD_VAL_CLASSES:
+            raise ValueError("GraphedXbdEvalStep: classes %r is not one of %s" % (classes, list(ops.XBD_VAL_CLASSES)))
+        self.classes = classes
         self.net, self.class_counts, self.thr, self.select = net, class_counts, float(thr), select
         self._hold(imgs, msk, lbl_msk)
         self.image_counts = torch.zeros(imgs.shape[0], 3, dtype=torch.int64, device=imgs.device)
@@ -493,7 +500,7 @@ class GraphedXbdEvalStep(_RecordedXbdBatch):
         with torch.no_grad():
             logits = self.net(self.imgs)
         logits = logits.float()
-        ops.xbd_val_count(logits, self.msk0, self.lbl, self.image_counts, self.class_counts, self.thr, self.select)
+        ops.xbd_val_count(logits, self.msk0, self.lbl, self.image_counts, self.class_counts, self.thr, self.select, self.classes)
         return logits
 
 
@@ -716,3 +723,53 @@ class GraphedXbdUnetStep(GraphedXbdStep):
         lo = logits.float().contiguous()
         loss, self.parts, sums = ops.xbd_unet_loss_fwd(lo, self.lab, self.lbl, self.labels, self._w, 1.0, 8.0, xbd.UNET_CE_SCALE)
         return loss, ops.xbd_unet_loss_bwd(lo, self.lab, self.lbl, self.labels, sums, self._w, None, 1.0, 8.0, xbd.UNET_CE_SCALE)
+
+
+class GraphedXbdAdaptStep(GraphedXbdStep):
+    """The step of xBD_code/train_adapt.py:326-347, the Ida-BD adaptation of the FOUR-output DAHiTra, as one HIP graph: forward of
+    the 6-channel model, its loss (models/xbd.adapt_loss: four ComboLoss terms weighted 0.1, 0.8, 2, 8 plus 5 * the class-weighted
+    cross-entropy of the raw logits) at engine level, backward, clip_grad_norm_(0.999) (line 346) and the hand-rolled AdamW.
+    msks are the loader's uint8 bytes [B, 4, H, W] (GpuXbdPipeline.make_adapt_batch) and stay bytes.
+
+        step = GraphedXbdAdaptStep(net, xbd.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-7, capturable=True), imgs, msks)
+        loss = step(imgs, msks)          # step.parts: the static [6] tensor of ops.XBD_ADAPT_PARTS, valid after every replay
+
+    step() without arguments replays on the inputs the step holds.  With torch.distributed the parent's forms apply: the mean over
+    the ranks, then the clip over the complete arena, then the update.  A scheduler's learning rate reaches the replay through
+    opt.sync_hyper, as in the parent.  ValueError for a dtype or shape that does not fit, before anything is recorded."""
+    INPUTS = ("a", "lab")          # imgs, msks
+    ENGINE_LEVEL = True
+
+    def __init__(self, net, opt, imgs, msks, max_norm=0.999, warmup=3):
+        from .models import xbd
+        a = ops._Args("GraphedXbdAdaptStep", cpu_error=True)
+        B, _, H, W = a.tensor("imgs", imgs, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 6 and t.numel() > 0,
+                              "[B, 6, H, W], not empty").shape
+        a.tensor("msks", msks, torch.uint8, (B, 4, H, W), "[%d, 4, %d, %d] like imgs" % (B, H, W))
+        a.placed()
+        self.max_norm, self.parts = max_norm, None
+        self._w = xbd.adapt_weights_dev(imgs.device)        # made here: no host-to-device copy inside the capture
+        self._build(net, opt, (imgs, msks), warmup)
+
+    def __call__(self, imgs=None, msks=None):
+        return super().__call__(imgs, msks)
+
+    def _body(self, include_opt):
+        """the one-graph step: the engine-level pass, then (single process) the clip and the update"""
+        loss = self._engine_pass(self.net._engine.backward)
+        if include_opt:
+            self._update()
+        return loss
+
+    def _eager_body(self, include_opt):
+        from .models import xbd
+        self.logits, loss, self.parts = xbd.adapt_eager_step(self.net, self.opt, self.a, self.lab, self.max_norm,
+                                                             update=include_opt)
+        return loss
+
+    def _loss_and_grad(self, logits):
+        """the script's loss and its gradient at engine level: two launches forward, one backward, the masks read as bytes"""
+        from .models import xbd
+        lo = logits.float().contiguous()
+        loss, self.parts, sums = ops.xbd_adapt_loss_fwd(lo, self.lab, self._w, 1.0, 8.0, xbd.ADAPT_CE_SCALE)
+        return loss, ops.xbd_adapt_loss_bwd(lo, self.lab, sums, self._w, None, 1.0, 8.0, xbd.ADAPT_CE_SCALE)

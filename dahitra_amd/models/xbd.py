@@ -3,6 +3,7 @@
 Mirrored interfaces (same names, argument meaning, error behaviour):
     BASE_Transformer_UNet(input_nc, output_nc, ...)   xBD_code/zoo/model_transformer_encoding.py:242-449
         net(x) with ONE [B, 6, H, W] tensor (pre | post), logits [B, 5, H, W]; built at xBD_code/train.py:44-45
+        output_nc=4: the four-output net of xBD_code/train_adapt.py:37-38 (localisation, minor, major, destroyed merged with 3)
     ComboLoss(weights, per_image=False)               xBD_code/losses.py:95-126   (dice + focal on the sigmoid)
     xbd_loss(out, msks)                               xBD_code/train.py:348-353   (the five weighted channel losses)
     unet_loss(out, msks, lbl_msk, labels)             xBD_code/train_unettransformer.py:438-456 (five ComboLoss terms + 8 * the
@@ -12,6 +13,16 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
         indices: the val_idxs of pipe.unet_trainset(), the tenth the script holds out of its one folder)
     train_epoch_unet(current_epoch, model, optimizer, scheduler, batches)   train_unettransformer.py:421-486 (no clip; the meters
         Loss / loss2 / loss3 / Dice from ONE host read per epoch; `seg_loss`, `ce_loss` and `scaler` are not arguments here)
+    adapt_loss(out, msks)                             xBD_code/train_adapt.py:332-342 (four ComboLoss terms weighted 0.1, 0.8, 2, 8
+        + 5 * the class-weighted cross-entropy of the RAW logits; uint8 masks, the label derived from them in the kernel)
+    adapt_scheduler(optimizer)                        train_adapt.py:423                (MultiStepLR, gamma 0.6, no 17)
+    train_epoch_adapt(current_epoch, model, optimizer, scheduler, batches)   train_adapt.py:313-360 (WITH the clip of line 346;
+        the meters Loss / loss1 / loss2 / loss3 from ONE host read per epoch; line 359 as printed; line 331's print and the
+        unused GradScaler are not reproduced)
+    validate_adapt(model, batches) / evaluate_val_adapt(...)   train_adapt.py:248-310 (validate / evaluate_val with THREE damage
+        classes: f1 = 3 / sum(1 / (f1_sc + 1e-6)); the `best_score == 10000` train-score branch is not built)
+        the loader and the file set of that script are GpuXbdPipeline.make_adapt_batch / adapt_batches / adapt_trainset; the
+        sample order stays this loader's own, and the augmentation inside the script's string literal is not built
     clip_grad_norm_(parameters, max_norm)             torch.nn.utils.clip_grad_norm_ as called at train.py:373
     AdamW(params, lr, weight_decay)                   xBD_code/adamw.py:6-86      (hand-rolled; eps before bias correction)
     validate(model, data_loader)                      xBD_code/train.py:247-290   (dice of the localisation + harmonic F1)
@@ -33,7 +44,7 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
         damage class per building by vote, and the building-level confusion and F1 against the ground truth
     dilate / erode / opening / closing / fill_holes / clean_footprint   no counterpart: square-window morphology and hole
         filling of a footprint before its buildings are counted (scipy.ndimage's binary_* functions are the oracle)
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_unet_loss.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_ensemble.hip, csrc/xbd_visual.hip,
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_unet_loss.hip, csrc/xbd_adapt_loss.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_ensemble.hip, csrc/xbd_visual.hip,
 csrc/xbd_buildings.hip, csrc/xbd_morph.hip + the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
@@ -51,6 +62,11 @@ UNET_CE_WEIGHTS = (0.01, 0.10, 1.0, 0.80, 1.0)        # ... :563
 UNET_CE_SCALE = 8.0                                   # ... :456 (loss5 * 8)
 UNET_MILESTONES = (5, 11, 17, 23, 29, 33, 47, 50, 60, 70, 90, 110, 130, 150, 170, 180, 190)      # ... :536
 UNET_GAMMA = 0.6
+ADAPT_CHANNEL_WEIGHTS = (0.1, 0.8, 2.0, 8.0)          # xBD_code/train_adapt.py:336
+ADAPT_CE_WEIGHTS = (0.1, 0.5, 1.5, 1.5)               # ... :320
+ADAPT_CE_SCALE = 5.0                                  # ... :340 (ce_loss(...) * 5)
+ADAPT_MILESTONES = (5, 11, 23, 29, 33, 47, 50, 60, 70, 90, 110, 130, 150, 170, 180, 190)      # ... :423 (no 17 in this list)
+ADAPT_MAX_NORM = 0.999                                # ... :346
 _weights = {}
 
 
@@ -60,17 +76,18 @@ def BASE_Transformer_UNet(input_nc=3, output_nc=5, with_pos='learned', resnet_st
                           with_decoder_pos=None, with_decoder=True, compute_dtype=None):
     """Constructor of the xBD copy.  `dec_depth` is accepted and ignored exactly as the reference does (the per-level
     decoder depths 4/4/8/1 are hard-coded, model_transformer_encoding.py:318-334).  Default torch initialisation (the
-    xBD scripts never call init_weights)."""
-    if (input_nc, output_nc, with_pos, resnet_stages_num, token_len, enc_depth, dim_head, decoder_dim_head, backbone) != \
-            (3, 5, 'learned', 4, 4, 1, 64, 64, 'resnet18') or not (tokenizer and token_trans and with_decoder and
-                                                                  decoder_softmax):
-        raise NotImplementedError("only the configuration of xBD_code/train.py:44-45 is built "
-                                  "(input_nc=3, output_nc=5, token_len=4, with_pos='learned', resnet18)")
+    xBD scripts never call init_weights).  output_nc: 5 (train.py) or 4 (train_adapt.py: netspec's `..._c4` entries, the same
+    state but for the classifier's two shapes); anything else raises NotImplementedError."""
+    if (input_nc, with_pos, resnet_stages_num, token_len, enc_depth, dim_head, decoder_dim_head, backbone) != \
+            (3, 'learned', 4, 4, 1, 64, 64, 'resnet18') or output_nc not in (4, 5) or \
+            not (tokenizer and token_trans and with_decoder and decoder_softmax):
+        raise NotImplementedError("only the configurations of xBD_code/train.py:44-45 and train_adapt.py:37-38 are built "
+                                  "(input_nc=3, output_nc=5 or 4, token_len=4, with_pos='learned', resnet18)")
     if with_decoder_pos not in (None, 'learned'):
         raise NotImplementedError("with_decoder_pos must be None or 'learned'")
     print("using UNet Transformer !!!!")
-    return CDNet("xbd_unet_transformer" if with_decoder_pos == 'learned' else "xbd_unet_transformer_nodecpos",
-                 compute_dtype)
+    name = "xbd_unet_transformer" if output_nc == 5 else "xbd_unet_transformer_c4"
+    return CDNet(name if with_decoder_pos == 'learned' else name + "_nodecpos", compute_dtype)
 
 
 # ---- loss ------------------------------------------------------------------------------------------------
@@ -227,16 +244,20 @@ class AdamW(_ArenaAdamW):
 
 
 # ---- validation (xBD_code/train.py:247-307) ----------------------------------------------------------------
-def val_score(image_counts, class_counts, empty_score=1.0):
+def val_score(image_counts, class_counts, empty_score=1.0, classes=4):
     """The reference's score from the counts of ops.xbd_val_count, in its own float64 numpy expressions.
     image_counts: integers [n_images, 3] = |gt0|, |loc|, |gt0 & loc| per image; class_counts: integers [4, 3] = tp, fn, fp per
     class.  dice of an image = 2 |gt0 & loc| / (|gt0| + |loc|), `empty_score` when both are empty (utils.py:147-154);
     d0 = mean of the dices; f1_sc[c] = 2 tp / (2 tp + fp + fn), nan for 0 / 0 as numpy gives it; f1 = 4 / sum(1 / (f1_sc +
     1e-6)); score = 0.3 d0 + 0.7 f1 (train.py:281-288).  A class without a counted pixel makes the score nan, and
     `nan > best_score` is False: the reference's behaviour, kept.  Returns (score, {'dice', 'f1', 'f1_per_class'}).
-    The counts are additive: ranks that validate shards sum them before this call."""
+    The counts are additive: ranks that validate shards sum them before this call.
+    classes: the damage classes, 4 (default: all of the above) or 3 -- xBD_code/train_adapt.py:282-289 for its four-output net:
+    class_counts [3, 3] and f1 = 3 / sum(1 / (f1_sc + 1e-6)).  ValueError for another number."""
+    if classes not in ops.XBD_VAL_CLASSES:
+        raise ValueError("val_score: classes %r is not one of %s" % (classes, list(ops.XBD_VAL_CLASSES)))
     ic = np.asarray(image_counts.cpu() if torch.is_tensor(image_counts) else image_counts).astype(np.int64).reshape(-1, 3)
-    cc = np.asarray(class_counts.cpu() if torch.is_tensor(class_counts) else class_counts).astype(np.int64).reshape(4, 3)
+    cc = np.asarray(class_counts.cpu() if torch.is_tensor(class_counts) else class_counts).astype(np.int64).reshape(classes, 3)
     dices0 = []
     for gt0, loc, both in ic:
         im_sum = gt0 + loc
@@ -244,10 +265,10 @@ def val_score(image_counts, class_counts, empty_score=1.0):
     with np.errstate(divide='ignore', invalid='ignore'):
         d0 = np.mean(dices0) if dices0 else np.float64('nan')
         tp, fn, fp = (cc[:, k].astype(np.float64) for k in range(3))          # np.zeros((4,)) accumulators: float64
-        f1_sc = np.zeros((4,))
-        for c in range(4):
+        f1_sc = np.zeros((classes,))
+        for c in range(classes):
             f1_sc[c] = 2 * tp[c] / (2 * tp[c] + fp[c] + fn[c])
-        f1 = 4 / np.sum(1.0 / (f1_sc + 1e-6))
+        f1 = classes / np.sum(1.0 / (f1_sc + 1e-6))
         sc = 0.3 * d0 + 0.7 * f1
     return sc, {'dice': d0, 'f1': f1, 'f1_per_class': f1_sc}
 
@@ -269,12 +290,13 @@ def _kept_step(owner, slot, key, build, fresh):
     return step
 
 
-def _eval_step(model, batch, class_counts, thr, select):
+def _eval_step(model, batch, class_counts, thr, select, classes=4):
     """the model's recorded validation step for this batch shape, threshold, selection and device"""
     from ..graph import GraphedXbdEvalStep
     imgs = batch['img']
     return _kept_step(model, '_xbd_eval_steps', (tuple(imgs.shape), float(thr), select, str(imgs.device)),
-                      lambda: GraphedXbdEvalStep(model, imgs, batch['msk'], batch['lbl_msk'], class_counts, thr, select),
+                      lambda: GraphedXbdEvalStep(model, imgs, batch['msk'], batch['lbl_msk'], class_counts, thr, select,
+                                                 classes=classes),
                       lambda step: step._generation == model._arena.generation and step.class_counts is class_counts)
 
 
@@ -318,6 +340,26 @@ def _epoch(what, model, batches, row_shape, accumulator, replay, eager):
     return both[:cut].reshape((n,) + row_shape), both[cut:].reshape(tuple(acc.shape))
 
 
+def _val_counts(what, model, batches, thr, select, graph, classes):
+    """the epoch of validate (classes 4) and validate_adapt (3): (image_counts [n_images, 3], class_counts [classes, 3]) as numpy
+    integers, from ONE host read.  The class accumulator is kept on the model: a recorded step holds its address."""
+    if select not in ops.XBD_VAL_SELECT:
+        raise ValueError("%s: select %r is not one of %s" % (what, select, sorted(ops.XBD_VAL_SELECT)))
+
+    def accumulator(dev):
+        cc = model.__dict__.get('_xbd_val_class_counts')
+        if cc is None or cc.device != dev or cc.shape[0] != classes:
+            cc = model.__dict__['_xbd_val_class_counts'] = torch.zeros(classes, 3, dtype=torch.int64, device=dev)
+        return cc
+
+    def replay(batch, cc):
+        step = _eval_step(model, batch, cc, thr, select, classes)
+        step(batch['img'], batch['msk'], batch['lbl_msk'])
+        return step.image_counts
+    return _epoch(what, model, batches, (3,), accumulator, replay if graph else None,
+                  lambda logits, msk, lbl, rows, cc: ops.xbd_val_count(logits, msk, lbl, rows, cc, thr, select, classes))
+
+
 def validate(model, batches, thr=0.3, select='reference', graph=True, want_counts=False):
     """validate(model, data_loader) of xBD_code/train.py:247-290 on the device.  batches: dicts {'img' [B, 6, H, W] fp32,
     'msk' [B, 5, H, W], 'lbl_msk' [B, H, W]} as GpuXbdPipeline.batches(b, size, train=False) yields them (uint8; the
@@ -329,21 +371,7 @@ def validate(model, batches, thr=0.3, select='reference', graph=True, want_count
     by the first row of lbl_msk) or 'building' (pixels of msk[:, 0]), see ops.xbd_val_count.
     Prints the reference's `Val Score: ...` line and returns the score (with want_counts: score, parts, image_counts,
     class_counts as numpy integers)."""
-    if select not in ops.XBD_VAL_SELECT:
-        raise ValueError("validate: select %r is not one of %s" % (select, sorted(ops.XBD_VAL_SELECT)))
-
-    def accumulator(dev):
-        cc = model.__dict__.get('_xbd_val_class_counts')
-        if cc is None or cc.device != dev:
-            cc = model.__dict__['_xbd_val_class_counts'] = torch.zeros(4, 3, dtype=torch.int64, device=dev)
-        return cc
-
-    def replay(batch, cc):
-        step = _eval_step(model, batch, cc, thr, select)
-        step(batch['img'], batch['msk'], batch['lbl_msk'])
-        return step.image_counts
-    image_counts, cc = _epoch("validate", model, batches, (3,), accumulator, replay if graph else None,
-                              lambda logits, msk, lbl, rows, cc: ops.xbd_val_count(logits, msk, lbl, rows, cc, thr, select))
+    image_counts, cc = _val_counts("validate", model, batches, thr, select, graph, 4)
     sc, parts = val_score(image_counts, cc)
     f1_sc = parts['f1_per_class']
     print("Val Score: {}, Dice: {}, F1: {}, F1_0: {}, F1_1: {}, F1_2: {}, F1_3: {}".format(sc, parts['dice'], parts['f1'], f1_sc[0],
@@ -621,6 +649,160 @@ def train_epoch_unet(current_epoch, model, optimizer, scheduler, batches, labels
                                                                               meters['dice']))
     meters.update(lr=lr, steps=len(sizes), samples=int(w.sum()))
     return meters
+
+
+# ---- the adaptation script xBD_code/train_adapt.py: loss, step, epoch and validation of the FOUR-output net ---------------
+class _AdaptLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, msks, weights_dev, dice_w, focal_w, ce_w):
+        loss, parts, sums = ops.xbd_adapt_loss_fwd(logits, msks, weights_dev, dice_w, focal_w, ce_w)
+        ctx.save_for_backward(logits, msks, sums, weights_dev)
+        ctx.how = (dice_w, focal_w, ce_w)
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, dloss, _dparts):
+        logits, msks, sums, weights_dev = ctx.saved_tensors
+        up = dloss.detach().to(torch.float32).reshape(1).contiguous()
+        return (ops.xbd_adapt_loss_bwd(logits, msks, sums, weights_dev, up, *ctx.how),) + (None,) * 5
+
+
+def adapt_weights_dev(device, channel_weights=ADAPT_CHANNEL_WEIGHTS, ce_weights=ADAPT_CE_WEIGHTS):
+    """the 4 channel weights and the 4 class weights as ONE cached device tensor [8], the form ops.xbd_adapt_loss_fwd takes (no
+    host-to-device copy inside a HIP-graph capture).  ValueError unless both hold 4 numbers."""
+    key = (str(device), tuple(float(v) for v in channel_weights), tuple(float(v) for v in ce_weights))
+    if len(key[1]) != 4 or len(key[2]) != 4:
+        raise ValueError("adapt_loss: channel_weights %r and ce_weights %r must hold 4 numbers each" % (key[1], key[2]))
+    w = _weights.get(key)
+    if w is None:
+        w = _weights[key] = torch.tensor(key[1] + key[2], dtype=torch.float32, device=device)
+    return w
+
+
+def adapt_loss(out, msks, want_parts=False, channel_weights=ADAPT_CHANNEL_WEIGHTS, ce_weights=ADAPT_CE_WEIGHTS, dice=1.0,
+               focal=8.0, ce=ADAPT_CE_SCALE):
+    """The loss of train_adapt.py:332-342 in one pass over the pixels (ops.xbd_adapt_loss_fwd; one more for the gradient):
+        0.1 l0 + 0.8 l1 + 2 l2 + 8 l3 + 5 * CrossEntropyLoss(weight=[0.1, 0.5, 1.5, 1.5])(out, y)
+    with l_c = ComboLoss{dice 1, focal 8}(out[:, c], msks[:, c]) and y = the first maximum of (1 - m0, m1, m2, m3) -- the
+    script's msks[:, 0] = 1 - msks[:, 0]; argmax(msks, dim=1) -- derived inside the kernel from the mask bytes: msks is not
+    written.  out: logits [B, 4, H, W]; msks: uint8 [B, 4, H, W] AS THE LOADER YIELDS THEM (make_adapt_batch; no float copy is
+    made; another dtype is refused).  Unlike unet_loss the cross-entropy is taken of the raw logits, nothing is masked: it has
+    a gradient on every pixel.  want_parts: also return the device tensor parts [6] = ops.XBD_ADAPT_PARTS: the four channel
+    losses, the cross-entropy (before the factor 5), and 0.  No host synchronisation."""
+    if not (torch.is_tensor(out) and out.is_cuda):
+        raise _lib.HipLibraryError("dahitra_amd xBD loss runs on MI355X only (no CPU fallback)")
+    w = adapt_weights_dev(out.device, channel_weights, ce_weights)
+    loss, parts = _AdaptLoss.apply(out.float().contiguous(), msks.contiguous() if torch.is_tensor(msks) else msks, w,
+                                   float(dice), float(focal), float(ce))
+    return (loss, parts) if want_parts else loss
+
+
+def adapt_scheduler(optimizer):
+    """lr_scheduler.MultiStepLR(optimizer, milestones=[5, 11, 23, 29, 33, 47, 50, 60, ...], gamma=0.6) of train_adapt.py:423 --
+    unet_scheduler's list without the 17"""
+    return torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=list(ADAPT_MILESTONES), gamma=UNET_GAMMA)
+
+
+def adapt_eager_step(model, optimizer, imgs, msks, max_norm=ADAPT_MAX_NORM, update=True):
+    """The script's step through autograd (train_adapt.py:329-347): zero_grad, forward, adapt_loss, backward and -- with
+    `update` -- clip_grad_norm_(max_norm) and optimizer.step().  Returns (logits, loss, parts), detached.  What
+    train_epoch_adapt runs for a batch without a recorded step, and GraphedXbdAdaptStep's `_eager_body`."""
+    model.zero_grad()
+    logits = model(imgs)
+    loss, parts = adapt_loss(logits, msks, want_parts=True)
+    loss.backward()
+    if update:
+        clip_grad_norm_(model.parameters(), max_norm)
+        optimizer.step()
+    return logits.detach(), loss.detach(), parts
+
+
+def _adapt_train_step(model, optimizer, first, graph):
+    """_unet_train_step for the adaptation step: run(batch) -> (loss, parts); batches of the first batch's shape replay the model's
+    recorded GraphedXbdAdaptStep (kept on the model per shape, optimizer and device), any other shape and graph=False run eagerly"""
+    _device_u8("training", first['img'], first['msk'])
+
+    def eager(batch):
+        return adapt_eager_step(model, optimizer, batch['img'], batch['msk'])[1:]
+    if not graph:
+        return eager
+    from ..graph import GraphedXbdAdaptStep
+    imgs = first['img']
+    model._ensure_arena(imgs.device)
+    step = _kept_step(model, '_xbd_adapt_steps', (tuple(imgs.shape), id(optimizer), str(imgs.device)),
+                      lambda: GraphedXbdAdaptStep(model, optimizer, imgs, first['msk']),
+                      lambda step: step._generation == model._arena.generation and step.opt is optimizer)
+
+    def replay(batch):
+        if tuple(batch['img'].shape) != tuple(imgs.shape):
+            return eager(batch)
+        return step(batch['img'], batch['msk']), step.parts
+    return replay
+
+
+def train_epoch_adapt(current_epoch, model, optimizer, scheduler, batches, graph=True):
+    """train_epoch of xBD_code/train_adapt.py:313-360 on the device.  batches: dicts {'img' fp32 [B, 6, H, W], 'msk' uint8
+    [B, 4, H, W], ...} as GpuXbdPipeline.adapt_batches yields them.  Per batch: forward, adapt_loss, backward,
+    clip_grad_norm_(0.999) and the hand-rolled AdamW -- with graph=True one replay of a GraphedXbdAdaptStep (optimizer:
+    AdamW(..., capturable=True)).  Every step's loss and parts go into a row of a device buffer by asynchronous device copies;
+    the host reads ONCE, when the epoch is over, where the script reads four .item() values per step.  The meters are
+    AverageMeter's means, weighted by the batch size, as lines 349-352 feed them: Loss, loss1 (channel 1), loss2 (channel 2) and
+    loss3 (channel 3, the script's `lossesgan`).  Then scheduler.step(), and the script's closing line 359 as printed -- its
+    `loss2` is the meter of loss1 and its `Dice` the meter of loss3:
+        epoch: ..; lr ..; Loss ..; loss2 ..; Dice ..
+    Returns {'loss', 'loss1', 'loss2', 'loss3', 'loss0', 'ce', 'lr', 'steps', 'samples'}.
+    Not reproduced: the per-step print(out.shape, msks.shape) of line 331 and the GradScaler of line 430, which the script
+    never uses.  As in train_epoch_unet the scheduler moves by scheduler.step(), without the script's deprecated epoch argument
+    (with `step(current_epoch)` a milestone takes effect one epoch later), and the printed lr is
+    optimizer.param_groups[-1]['lr'], the rate the next epoch runs at."""
+    model.train()
+    run, rows, sizes = None, None, []
+    for batch in batches:
+        if run is None:
+            run = _adapt_train_step(model, optimizer, batch, graph)
+        loss, parts = run(batch)
+        rows, row = _next_rows(rows, len(sizes), 1, (7,), torch.float32, loss.device)
+        row[0, 0:1].copy_(loss.reshape(1), non_blocking=True)
+        row[0, 1:].copy_(parts, non_blocking=True)
+        sizes.append(int(batch['img'].shape[0]))
+    if rows is None:
+        raise ValueError("train_epoch_adapt: no batches")
+    host = rows[:len(sizes)].cpu().numpy().astype(np.float64)          # the epoch's one read
+    w = np.asarray(sizes, dtype=np.float64)
+    avg = lambda col: float((host[:, col] * w).sum() / w.sum())        # AverageMeter: sum(val * n) / sum(n)
+    meters = {'loss': avg(0), 'loss0': avg(1), 'loss1': avg(2), 'loss2': avg(3), 'loss3': avg(4), 'ce': avg(5)}
+    scheduler.step()
+    lr = optimizer.param_groups[-1]['lr']
+    print("epoch: {}; lr {:.7f}; Loss {:.4f}; loss2 {:.4f}; Dice {:.4f}".format(current_epoch, lr, meters['loss'], meters['loss1'],
+                                                                              meters['loss3']))
+    meters.update(lr=lr, steps=len(sizes), samples=int(w.sum()))
+    return meters
+
+
+def validate_adapt(model, batches, thr=0.3, select='reference', graph=True, want_counts=False):
+    """validate(model, data_loader, best_score) of xBD_code/train_adapt.py:248-294 on the device, for the four-output net.
+    batches: dicts {'img' [B, 6, H, W] fp32, 'msk' [B, 4, H, W], 'lbl_msk' [B, H, W]} as GpuXbdPipeline.adapt_batches(b, size,
+    train=False) yields them.  Everything is validate's -- one count kernel per batch (ops.xbd_val_count with classes=3), one
+    host read per epoch, a recorded GraphedXbdEvalStep per shape, the same `select` -- with THREE damage classes:
+    f1 = 3 / sum(1 / (f1_sc + 1e-6)), score = 0.3 d0 + 0.7 f1.  Prints the script's `Val Score: ... F1_2: ...` line and returns
+    the score (with want_counts: score, parts, image_counts, class_counts [3, 3] as numpy integers).  The script's
+    `best_score == 10000` branch ("Train Score" over a third of the loader) is not built."""
+    image_counts, cc = _val_counts("validate_adapt", model, batches, thr, select, graph, 3)
+    sc, parts = val_score(image_counts, cc, classes=3)
+    f1_sc = parts['f1_per_class']
+    print("Val Score: {}, Dice: {}, F1: {}, F1_0: {}, F1_1: {}, F1_2: {}".format(sc, parts['dice'], parts['f1'], f1_sc[0], f1_sc[1],
+                                                                                f1_sc[2]))
+    return (sc, parts, image_counts, cc) if want_counts else sc
+
+
+def evaluate_val_adapt(batches, best_score, model, optimizer, path, current_epoch, thr=0.3, select='reference', graph=True):
+    """evaluate_val of xBD_code/train_adapt.py:297-310: validate_adapt, and when the score beats `best_score` save the snapshot
+    {'epoch': current_epoch + 1, 'state_dict', 'best_score', 'optimizer'} to `path`.  A nan score beats nothing.  Prints the
+    `score: ... score_best: ...` line and returns the best score."""
+    model = model.eval()
+    d = validate_adapt(model, batches, thr=thr, select=select, graph=graph)
+    return _keep_best(d, best_score, model, optimizer, path, current_epoch)
 
 
 # ---- prediction (xBD_code/predict_test_cls.py:58-97) --------------------------------------------------------

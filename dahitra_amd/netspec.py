@@ -33,6 +33,12 @@ NET_CONFIGS = {
     "xbd_unet_transformer": dict(kind="xbd", n_class=5, token_len=4, enc_depth=1, decoder_pos=True, ctor_only=True),
     "xbd_unet_transformer_nodecpos": dict(kind="xbd", n_class=5, token_len=4, enc_depth=1, decoder_pos=False,
                                           ctor_only=True),
+    # the same model with FOUR outputs (localisation, minor, major, destroyed merged with class 3): the net of the Ida-BD
+    # adaptation script, built at xBD_code/train_adapt.py:37-38 with with_decoder_pos='learned'.  Only the classifier's two
+    # shapes differ from the five-class entries.
+    "xbd_unet_transformer_c4": dict(kind="xbd", n_class=4, token_len=4, enc_depth=1, decoder_pos=True, ctor_only=True),
+    "xbd_unet_transformer_c4_nodecpos": dict(kind="xbd", n_class=4, token_len=4, enc_depth=1, decoder_pos=False,
+                                             ctor_only=True),
 }
 RESNET50_BLOCKS = (3, 4, 6, 3)
 BIT_HEADS, BIT_DIM_HEAD = 8, 64

@@ -1948,29 +1948,116 @@ def xbd_unet_loss_bwd(logits, msk, lbl, labels, sums, weights_dev, upstream=None
     return dl
 
 
+# ---- loss of xBD_code/train_adapt.py's step (csrc/xbd_adapt_loss.hip) ----------------------------------------
+# lanes of one forward grid pass (dh_xbd_adapt_loss_grid_pass), as XBD_UNET_LOSS_PASS
+XBD_ADAPT_LOSS_PASS = 1024 * 256
+XBD_ADAPT_PARTS = ("loss0", "loss1", "loss2", "loss3", "ce", "zero")
+
+
+def _xbd_adapt_loss_args(what, logits, msk, weights_dev, extra=()):
+    """the tensors of xbd_adapt_loss_fwd / _bwd, refused before any launch: ValueError for a dtype or shape that does not fit and
+    for mixed devices, HipLibraryError when everything is on the CPU.  Returns B, H, W"""
+    a = _Args(what, cpu_error=True)
+    B, _, H, W = a.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 4 and t.numel() > 0,
+                          "[B, 4, H, W], not empty").shape
+    a.tensor("msk", msk, torch.uint8, (B, 4, H, W), "[%d, 4, %d, %d] like logits" % (B, H, W))
+    a.tensor("weights_dev", weights_dev, torch.float32, (8,), "[8]: 4 channel weights, 4 class weights")
+    for name, t, shape in extra:
+        if t is not None:
+            a.tensor(name, t, torch.float32, lambda t, n=math.prod(shape): t.numel() == n, str(list(shape)))
+    a.placed()
+    return B, H, W
+
+
+def xbd_adapt_loss_fwd(logits, msk, weights_dev, dice_weight=1.0, focal_weight=8.0, ce_weight=5.0):
+    """The loss of xBD_code/train_adapt.py:332-342 in one pass and a finalize launch (dh_xbd_adapt_loss_fwd): four weighted
+    ComboLoss{dice, focal} terms + ce_weight * the class-weighted cross-entropy of the RAW logits against y = the first maximum
+    of (1 - m0, m1, m2, m3), derived from the mask bytes in the kernel.  logits fp32 [B, 4, H, W]; msk uint8 [B, 4, H, W], the
+    loader's bytes; weights_dev fp32 [8] = the 4 channel weights, then the 4 class weights.  Returns (loss [], parts [6] =
+    XBD_ADAPT_PARTS, sums [18] for xbd_adapt_loss_bwd), all on the device; nothing is read by the host."""
+    B, H, W = _xbd_adapt_loss_args("xbd_adapt_loss_fwd", logits, msk, weights_dev)
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty(6, dtype=torch.float32, device=dev)
+    sums = torch.empty(18, dtype=torch.float32, device=dev)
+    ws = workspace(_ws_bytes("dh_xbd_adapt_loss_workspace_size"), dev)
+    _call("dh_xbd_adapt_loss_fwd", P(logits), P(msk), B, H * W, P(weights_dev), float(dice_weight), float(focal_weight),
+          float(ce_weight), P(sums), P(parts), P(loss), P(ws), ws.numel(), S())
+    return loss, parts, sums
+
+
+def xbd_adapt_loss_bwd(logits, msk, sums, weights_dev, upstream=None, dice_weight=1.0, focal_weight=8.0, ce_weight=5.0):
+    """dloss / dlogits of xbd_adapt_loss_fwd, one pass (dh_xbd_adapt_loss_bwd): fp32 [B, 4, H, W].  sums: the forward's third
+    result; upstream: a device scalar fp32 [1] that multiplies the gradient, or None for 1."""
+    if sums is None:
+        raise ValueError("xbd_adapt_loss_bwd: sums is None; it is xbd_adapt_loss_fwd's third result")
+    B, H, W = _xbd_adapt_loss_args("xbd_adapt_loss_bwd", logits, msk, weights_dev,
+                                   (("sums", sums, (18,)), ("upstream", upstream, (1,))))
+    dl = torch.empty_like(logits)
+    _call("dh_xbd_adapt_loss_bwd", P(logits), P(msk), P(sums), P(weights_dev), P(upstream), float(dice_weight),
+          float(focal_weight), float(ce_weight), B, H * W, P(dl), S())
+    return dl
+
+
+# ---- loader of xBD_code/train_adapt.py (csrc/xbd_adapt.hip) ------------------------------------------------------
+def xbd_adapt_batch(pre_u8, post_u8, pre_mask_u8, post_label_u8, idx, origins, crop, train=True):
+    """One batch of the adaptation script's TrainData / ValData in ONE launch (dh_xbd_adapt_batch_u8).  pre_u8, post_u8
+    [n_src, H, W, 3] and pre_mask_u8, post_label_u8 [n_src, H, W]: the resident uint8 sources; idx int32 [N]: the source of
+    every sample; origins int32 [N, 2] = (x0, y0) of every crop window, or None for (0, 0).  Returns (img fp32 [N, 6, crop, crop]
+    = x / 127 - 1, msk uint8 [N, 4, crop, crop], lbl uint8 [N, crop, crop]); the planes are stated at the entry's declaration.
+    train=False reads the pre mask for plane 0 (ValData).  ValueError for whatever does not fit, before the launch; the caller
+    range-checks idx and origins (they are device memory: the kernel clamps them into the sources)."""
+    a = _Args("xbd_adapt_batch")
+    n_src, H, W, _ = a.tensor("pre_u8", pre_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[3] == 3 and t.numel() > 0,
+                              "[n_src, H, W, 3], not empty").shape
+    a.tensor("post_u8", post_u8, torch.uint8, (n_src, H, W, 3))
+    a.tensor("pre_mask_u8", pre_mask_u8, torch.uint8, (n_src, H, W))
+    a.tensor("post_label_u8", post_label_u8, torch.uint8, (n_src, H, W))
+    N = a.tensor("idx", idx, torch.int32, lambda t: t.dim() == 1 and t.numel() > 0, "[N], not empty").shape[0]
+    if origins is not None:
+        a.tensor("origins", origins, torch.int32, (N, 2))
+    a.placed()
+    if isinstance(crop, bool) or not isinstance(crop, int) or not 1 <= crop <= min(H, W):
+        raise ValueError("xbd_adapt_batch: crop %r does not fit the %dx%d sources" % (crop, H, W))
+    dev = pre_u8.device
+    img = torch.empty(N, 6, crop, crop, dtype=torch.float32, device=dev)
+    msk = torch.empty(N, 4, crop, crop, dtype=torch.uint8, device=dev)
+    lbl = torch.empty(N, crop, crop, dtype=torch.uint8, device=dev)
+    _call("dh_xbd_adapt_batch_u8", P(pre_u8), P(post_u8), P(pre_mask_u8), P(post_label_u8), P(idx), P(origins), N, n_src, H, W,
+          crop, 0 if train else 1, P(img), P(msk), P(lbl), S())
+    return img, msk, lbl
+
+
 # ---- xBD validation count (csrc/xbd_eval.hip) -----------------------------------------------------------
 XBD_VAL_SELECT = {"reference": 0, "building": 1}
 
 
-def _xbd_val_args(what, logits, msk, lbl, select):
+XBD_VAL_CLASSES = (3, 4)          # damage classes: 4 (train.py's five-output net) or 3 (train_adapt.py's four-output net)
+
+
+def _xbd_val_args(what, logits, msk, lbl, select, classes=4):
     """the tensors of xbd_val_count / xbd_val_sweep: ValueError for shapes or dtypes that do not fit.  Returns the mask plane and
-    the labels as the kernel reads them (uint8), the plane's image stride in bytes, and B, H, W"""
+    the labels as the kernel reads them (uint8), the plane's image stride in bytes, and B, H, W.  classes: the damage classes;
+    logits and a four-dimensional msk have classes + 1 channels"""
     if select not in XBD_VAL_SELECT:
         raise ValueError("%s: select %r is not one of %s" % (what, select, sorted(XBD_VAL_SELECT)))
-    if logits.dim() != 4 or logits.shape[1] != 5:
-        raise ValueError("%s: logits %s are not [B, 5, H, W]" % (what, tuple(logits.shape),))
+    if classes not in XBD_VAL_CLASSES:
+        raise ValueError("%s: classes %r is not one of %s" % (what, classes, list(XBD_VAL_CLASSES)))
+    C = classes + 1
+    if logits.dim() != 4 or logits.shape[1] != C:
+        raise ValueError("%s: logits %s are not [B, %d, H, W]" % (what, tuple(logits.shape), C))
     if logits.dtype != torch.float32:
         raise ValueError("%s: logits are %s, the sigmoid is taken in float32" % (what, logits.dtype))
     B, _, H, W = logits.shape
     if B < 1 or H < 1 or W < 1:
         raise ValueError("%s: empty logits %s" % (what, tuple(logits.shape),))
     if msk.dim() == 4:
-        if tuple(msk.shape) != (B, 5, H, W):
+        if tuple(msk.shape) != (B, C, H, W):
             raise ValueError("%s: msk %s does not match logits %s" % (what, tuple(msk.shape), tuple(logits.shape)))
         msk = msk[:, 0]
     if tuple(msk.shape) != (B, H, W):
-        raise ValueError("%s: msk %s is neither [B, 5, H, W] nor [B, H, W] of logits %s"
-                         % (what, tuple(msk.shape), tuple(logits.shape)))
+        raise ValueError("%s: msk %s is neither [B, %d, H, W] nor [B, H, W] of logits %s"
+                         % (what, tuple(msk.shape), C, tuple(logits.shape)))
     if tuple(lbl.shape) != (B, H, W):
         raise ValueError("%s: lbl_msk %s is not [B, H, W] of logits %s" % (what, tuple(lbl.shape), tuple(logits.shape)))
     if select == "reference" and H != W:
@@ -1983,33 +2070,40 @@ def _xbd_val_args(what, logits, msk, lbl, select):
         msk = (msk != 0).to(torch.uint8)
     if lbl.dtype != torch.uint8:
         lbl = lbl.clamp(0, 255).to(torch.uint8)
-    # channel 0 of a contiguous [B, 5, H, W] mask: planes contiguous, images 5 * H * W bytes apart -- read without a copy
+    # channel 0 of a contiguous [B, C, H, W] mask: planes contiguous, images C * H * W bytes apart -- read without a copy
     if not (msk.stride(2) == 1 and msk.stride(1) == W and (B == 1 or msk.stride(0) >= H * W)):
         msk = msk.contiguous()
     stride = msk.stride(0) if B > 1 else H * W
     return msk, lbl, stride, B, H, W
 
 
-def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select="reference"):
+def xbd_val_count(logits, msk, lbl, image_counts, class_counts, thr=0.3, select="reference", classes=4):
     """The counts of the reference's validate() (xBD_code/train.py:258-279) for one batch, on the device, no host read.
     logits [B, 5, H, W] fp32; msk: the batch's mask [B, 5, H, W] (channel 0 is read in place) or its localisation plane
     [B, H, W] / msk[:, 0], uint8 as the device loader gives it; lbl [B, H, W] uint8 (classes 0 .. 3).  A long tensor (the
     reference's dtype) is converted once.  image_counts int64 [B, 3] = |gt0|, |loc|, |gt0 & loc| is written, class_counts int64
     [4, 3] = tp, fn, fp of each class is accumulated.  select: 'reference' (train.py:271-274: row r counts iff
-    lbl[j, 0, r] > 0; H == W) or 'building' (pixel p counts iff msk[j, 0, p] > 0).  ValueError for shapes or dtypes that do not
-    fit, before the call."""
-    msk, lbl, stride, B, H, W = _xbd_val_args("xbd_val_count", logits, msk, lbl, select)
+    lbl[j, 0, r] > 0; H == W) or 'building' (pixel p counts iff msk[j, 0, p] > 0).
+    classes: the damage classes, 4 (default: all of the above, dh_xbd_val_count) or 3 -- the pass of
+    xBD_code/train_adapt.py:262-280 for its four-output net (dh_xbd_val_count_n): logits and msk [B, 4, H, W], lbl 0 .. 2,
+    class_counts [3, 3].  ValueError for shapes or dtypes that do not fit, before the call."""
+    msk, lbl, stride, B, H, W = _xbd_val_args("xbd_val_count", logits, msk, lbl, select, classes)
     if tuple(image_counts.shape) != (B, 3) or image_counts.dtype != torch.int64:
         raise ValueError("xbd_val_count: image_counts %s %s is not int64 [%d, 3]" % (tuple(image_counts.shape), image_counts.dtype, B))
-    if tuple(class_counts.shape) != (4, 3) or class_counts.dtype != torch.int64:
-        raise ValueError("xbd_val_count: class_counts %s %s is not int64 [4, 3]" % (tuple(class_counts.shape), class_counts.dtype))
+    if tuple(class_counts.shape) != (classes, 3) or class_counts.dtype != torch.int64:
+        raise ValueError("xbd_val_count: class_counts %s %s is not int64 [%d, 3]" % (tuple(class_counts.shape), class_counts.dtype,
+                                                                                      classes))
     if not 0.0 < float(thr) < 1.0:
         raise ValueError("xbd_val_count: thr=%r must lie inside (0, 1)" % (thr,))
     for t in (logits, msk, lbl, image_counts, class_counts):
         if not t.is_cuda:
             raise _lib.HipLibraryError("xbd_val_count runs on MI355X only (no CPU fallback)")
-    _call("dh_xbd_val_count", P(logits.contiguous()), _vp(msk.data_ptr()), stride, P(lbl.contiguous()), B, H, W, float(thr),
-          XBD_VAL_SELECT[select], P(image_counts), P(class_counts), S())
+    if classes == 4:
+        _call("dh_xbd_val_count", P(logits.contiguous()), _vp(msk.data_ptr()), stride, P(lbl.contiguous()), B, H, W, float(thr),
+              XBD_VAL_SELECT[select], P(image_counts), P(class_counts), S())
+    else:
+        _call("dh_xbd_val_count_n", P(logits.contiguous()), _vp(msk.data_ptr()), stride, P(lbl.contiguous()), classes, B, H, W,
+              float(thr), XBD_VAL_SELECT[select], P(image_counts), P(class_counts), S())
 
 
 XBD_SWEEP_MAX = 64          # thresholds per call: they travel by value in the kernel's arguments

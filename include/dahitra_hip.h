@@ -811,6 +811,44 @@ int dh_xbd_unet_loss_bwd(const float* logits, const unsigned char* msk, const un
                          const float* sums, const float* weights_dev, const float* upstream_dev, float dice_weight,
                          float focal_weight, float ce_weight, int B, long HW, float* dlogits, void* stream);
 
+/* ---- loss of xBD_code/train_adapt.py's step (lines 332-342; csrc/xbd_adapt_loss.hip) ---------------------------------
+ * The four-output sibling of dh_xbd_unet_loss_*: loss = sum_c cw_c * ComboLoss{dice, focal}(logits[:, c], msk[:, c]) + ce_weight *
+ * CrossEntropyLoss(weight=w)(logits, y), in ONE pass over the pixels plus a finalize launch.  logits fp32 [B][4][HW]; msk uint8
+ * [B][4][HW] (bytes 0 / 1, the loader's), read in place.  y is derived from the mask bytes in the kernel: the FIRST maximum of
+ * (1 - m0, m1, m2, m3) as integers, torch.argmax after the script's msks[:, 0] = 1 - msks[:, 0].  The cross-entropy is taken of
+ * the raw logits, nothing is masked: every pixel has a cross-entropy gradient.  weights_dev: the 4 channel weights cw, then the 4
+ * class weights w.  The combo sums and channel losses are dh_combo_loss_fwd's float expressions; ce = (sum w_y nll) / (sum w_y)
+ * over all pixels (torch's weighted mean), nll = logsumexp(x) - x_y.  fwd writes loss_out [1], parts_out [6] = the four channel
+ * losses, ce, 0; sums_out [18] = [c][4] combo sums, sum w_y, sum w_y nll (what bwd reads).  Sums in fp64 through a fixed tree:
+ * deterministic.  The 4-pixel form (16-byte logit loads) runs where HW % 4 == 0 and the planes are aligned, the one-pixel form
+ * otherwise.  dh_xbd_adapt_loss_grid_pass: the lanes of one forward grid pass (pixels in the one-pixel form, quads in the other).
+ * bwd: dlogits [B][4][HW] = upstream * (cw_c * combo gradient + ce_weight * w_y / (sum w_y) * (softmax(x)_c - [c == y])),
+ * upstream_dev a device scalar or NULL for 1.  Refused (nothing is launched): a null pointer, an empty input, logits or dlogits
+ * that are not 4-byte aligned, a workspace smaller than dh_xbd_adapt_loss_workspace_size answers or not 8-byte aligned. */
+int dh_xbd_adapt_loss_workspace_size(long* bytes);
+int dh_xbd_adapt_loss_grid_pass(void);
+int dh_xbd_adapt_loss_fwd(const float* logits, const unsigned char* msk, int B, long HW, const float* weights_dev,
+                          float dice_weight, float focal_weight, float ce_weight, float* sums_out, float* parts_out,
+                          float* loss_out, void* workspace, long workspace_bytes, void* stream);
+int dh_xbd_adapt_loss_bwd(const float* logits, const unsigned char* msk, const float* sums, const float* weights_dev,
+                          const float* upstream_dev, float dice_weight, float focal_weight, float ce_weight, int B, long HW,
+                          float* dlogits, void* stream);
+
+/* ---- loader of xBD_code/train_adapt.py (TrainData lines 97-184, ValData 196-245; csrc/xbd_adapt.hip) -------------------
+ * One launch per batch.  pre, post [n_src][H][W][3] uint8, pre_mask and post_label [n_src][H][W] uint8, resident.  Output sample
+ * n takes source idx[n] and the S x S window at origins[n] = {x0, y0} (origins NULL: every window at (0, 0)); both are clamped
+ * into the sources, so nothing outside them is read whatever the tables hold.  out_img fp32 [N][6][S][S] =
+ * preprocess_inputs(concat(pre, post)) = x / 127 - 1; out_msk uint8 [N][4][S][S], 0 / 1, from the post label byte l:
+ * m1 = (l == 1), m2 = (l == 2), m3 = (l == 3 or l == 4), and m0 = m1 | m2 | m3 in mode 0 (TrainData: the pre mask is cleared and
+ * not read, pre_mask may be NULL) or pre_mask > 127 in mode 1 (ValData); out_lbl uint8 [N][S][S] = argmax(m1, m2, m3): 1 where
+ * l == 2, 2 where l is 3 or 4, else 0.  A label byte above 4 sets no plane.  16-byte image stores and dword mask stores where
+ * S % 4 == 0 and the outputs are aligned, byte stores otherwise; the same bytes either way.
+ * Refused (nothing is written): a null pointer other than origins (and pre_mask in mode 0), mode outside {0, 1}, N outside
+ * 1..65535, n_src < 1, S < 1, S > H, S > W, H * W >= 2^31. */
+int dh_xbd_adapt_batch_u8(const unsigned char* pre, const unsigned char* post, const unsigned char* pre_mask,
+                          const unsigned char* post_label, const int* idx, const int* origins, int N, int n_src, int H, int W,
+                          int S, int mode, float* out_img, unsigned char* out_msk, unsigned char* out_lbl, void* stream);
+
 /* ---- xBD validation count (xBD_code/train.py:258-279; csrc/xbd_eval.hip) -------------------------------
  * One pass over logits [B][5][H][W] fp32: s = sigmoid in fp32, loc = s[0] > thr (strict, in float32), pred = argmax(s[1:]) * loc
  * with the first maximum of the fp32 sigmoids winning.  msk0: image j's ground-truth localisation plane [H][W] (nonzero = set) at
@@ -821,6 +859,12 @@ int dh_xbd_unet_loss_bwd(const float* logits, const unsigned char* msk, const un
  * Refused (nothing is written): a null pointer, B < 1, thr outside (0, 1), select 0 with H != W, H * W >= 2^31. */
 int dh_xbd_val_count(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl, int B,
                      int H, int W, float thr, int select, long long* image_counts, long long* class_counts, void* stream);
+/* dh_xbd_val_count for n_damage damage classes: logits [B][n_damage + 1][H][W], lbl classes 0 .. n_damage - 1, class_counts
+ * [n_damage][3].  n_damage 4 is dh_xbd_val_count; 3 is the pass of xBD_code/train_adapt.py:262-280, whose net has four outputs
+ * (destroyed merged with class 3).  Refused besides what dh_xbd_val_count refuses: n_damage outside {3, 4}. */
+int dh_xbd_val_count_n(const float* logits, const unsigned char* msk0, long msk0_image_stride, const unsigned char* lbl,
+                       int n_damage, int B, int H, int W, float thr, int select, long long* image_counts,
+                       long long* class_counts, void* stream);
 /* The same pass for a whole grid of localisation thresholds: thr is a HOST pointer to T float32 values, 1 <= T <= 64, each
  * inside (0, 1), strictly ascending; they are read during the call and travel by value in the kernel's arguments (a recorded
  * graph owns its copy; there is no device table).  Per pixel: bin = the number of k with s0 > thr[k] (strict, float32), 0 .. T;

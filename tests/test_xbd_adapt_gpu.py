@@ -1,0 +1,639 @@
+"""xBD_code/train_adapt.py on the GPU: the kernels of csrc/xbd_adapt_loss.hip against the float64 restatement of
+tests/_xbd_adapt_cases.py and against the reference's own results (tests/golden/xbd_adapt_loss.npz), the loader's bytes
+(csrc/xbd_adapt.hip) and the three-class validation counts (dh_xbd_val_count_n) against the script's numpy, the four-class net
+against the five-class oracle by the slicing identity, and GraphedXbdAdaptStep / train_epoch_adapt against the eager step.
+
+The measure of the loss kernels is the reference's own float32 error, the rule of tests/test_xbd_unet_step_gpu.py: the distance
+of its float32 CPU results from its float64 ones on the fixture's two cases, the largest of the two per quantity
+(tools/make_adapt_loss_golden.py prints them, _xbd_adapt_cases.yardstick reads them from the fixture):
+    loss 2.38e-05, channel losses 2.70e-04, ce 1.43e-07 (relative), gradient 1.75e-06 of its maximum.
+A kernel result may lie twice as far from the float64 value.  loss and gradient take that bound as it stands; the five float32
+parts take it with the floor of the format's spacing, 2^-23 relative: max(measured, 2^-23), which lifts none of these figures
+(ce's 1.43e-07 lies just above 1.19e-07).  MEASURED_KERNEL below is what the kernels measured on the MI355X, for the record; no
+bound is derived from it.  On the fixture's own inputs the kernels sit where the reference's float32 sits (loss 2.375e-05
+against its 2.385e-05, gradient 1.73e-06 against 1.75e-06).  The inputs of the other shapes are the fixture's pixels, resampled
+(_xbd_adapt_cases.make_case)."""
+import functools
+import os
+import random
+import socket
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import _xbd_adapt_cases as C
+import _xbd_val_cases as V
+import cdnet_ref as O
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ULP = 2.0 ** -23
+GRAD_TOL = 6e-2        # tests/test_xbd_gpu.py: the fp32 gradient noise floor of these nets
+LOGIT_TOL = 2e-4       # ... its logit_tol; 5e-4 at 1024 x 1024
+LOGIT_TOL_1024 = 5e-4
+
+# the kernels' largest distance from float64 over test_kernel_matches_the_restatement's shapes and the fixture's cases, as measured
+MEASURED_KERNEL = {"loss": 2.42e-05, "channel": 2.70e-04, "ce": 4.01e-08, "grad": 1.81e-06}
+
+
+@pytest.fixture(scope="module")
+def golden(golden_dir):
+    return np.load(os.path.join(golden_dir, "xbd_adapt_loss.npz"))
+
+
+@pytest.fixture(scope="module")
+def bounds(golden):
+    y = C.yardstick(golden)
+    return {"loss": 2 * y["loss"], "grad": 2 * y["grad"], "channel": 2 * max(y["channel"], ULP), "ce": 2 * max(y["ce"], ULP)}
+
+
+def offset_view(t, dtype):
+    """a device copy of `t` that starts one element into its buffer: no plane is on its vector's boundary"""
+    flat = torch.zeros(t.numel() + 1, dtype=dtype, device=DEV)[1:]
+    flat.copy_(torch.as_tensor(t).reshape(-1))
+    return flat.view(tuple(t.shape))
+
+
+def kernel(logits, msk, upstream=1.0, unaligned=False):
+    """xbd.adapt_loss and its backward on the device -> (loss, parts [6], gradient) on the host"""
+    from dahitra_amd.models import xbd
+    if unaligned:
+        lg, dm = offset_view(logits, torch.float32), offset_view(msk, torch.uint8)
+        assert lg.data_ptr() % 16 == 4 and dm.data_ptr() % 4 == 1
+        lg.requires_grad_(True)
+    else:
+        lg, dm = torch.as_tensor(logits).cuda().requires_grad_(True), torch.as_tensor(msk).cuda()
+    loss, parts = xbd.adapt_loss(lg, dm, want_parts=True)
+    (loss * upstream).backward()
+    return float(loss.detach()), parts.cpu().numpy().astype(np.float64), lg.grad.cpu().numpy()
+
+
+def distances(got, ref):
+    loss, parts, grad = got
+    rel = lambda a, b: float(np.max(np.abs(np.asarray(a, dtype=np.float64) - b) / np.abs(b)))
+    return {"loss": rel(loss, ref["loss"]), "channel": rel(parts[:4], ref["parts"][:4]), "ce": rel(parts[4], ref["parts"][4]),
+            "grad": float(np.abs(grad.astype(np.float64) - ref["grad"]).max() / np.abs(ref["grad"]).max())}
+
+
+def check(what, got, ref, bounds):
+    d = distances(got, ref)
+    print("%s: %s" % (what, ", ".join("%s %.3e (bound %.3e)" % (k, v, bounds[k]) for k, v in d.items())))
+    assert got[1][5] == 0, what
+    for k, v in d.items():
+        assert v <= bounds[k], (what, k, v, bounds[k])
+
+
+def shapes():
+    """(B, H, W, saturated, unaligned): the fixture's shape (one pixel per lane), 1 x 4 x 8 x 12 (four), H * W % 4 == 0 on planes
+    that start off the vector's boundary (one again), and one shape past one grid pass per launch form"""
+    from dahitra_amd import ops
+    P = ops.XBD_ADAPT_LOSS_PASS
+    return tuple(s + (False,) for s in C.SHAPES) + ((2, 6, 10, False, True),
+                                                    (1, 1, P + 3, False, False),          # 3 pixels past one grid pass
+                                                    (1, 4, P + 1, False, False))          # one quad past one grid pass
+
+
+@functools.lru_cache(None)
+def shape_case(k):
+    """inputs (the fixture's pixels, resampled) and float64 reference of shape k, made once"""
+    B, H, W, sat, _ = shapes()[k]
+    golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "xbd_adapt_loss.npz"))
+    logits, msk = C.make_case(golden, B, H, W, sat, seed=60 + k)
+    return logits, msk, C.restate(logits.numpy(), msk.numpy())
+
+
+@pytest.mark.parametrize("k", range(5))
+def test_kernel_matches_the_restatement(k, bounds):
+    from dahitra_amd import _lib, ops
+    assert ops.XBD_ADAPT_LOSS_PASS == _lib.lib().dh_xbd_adapt_loss_grid_pass()
+    B, H, W, _, unaligned = shapes()[k]
+    assert k < 3 or B * H * W > ops.XBD_ADAPT_LOSS_PASS * (4 if H * W % 4 == 0 else 1)
+    logits, msk, ref = shape_case(k)
+    got = kernel(logits, msk, unaligned=unaligned)
+    check("%dx4x%dx%d%s" % (B, H, W, " unaligned" if unaligned else ""), got, ref, bounds)
+    if unaligned:          # the same inputs on aligned planes take the four-pixel form: held to the same reference
+        check("%dx4x%dx%d aligned" % (B, H, W), kernel(logits, msk), ref, bounds)
+
+
+def test_kernel_matches_the_reference_fixture(golden, bounds):
+    for name in C.CASES:
+        got = kernel(golden[name + "_logits"], golden[name + "_msk"])
+        check("fixture %s" % name, got, C.fixture_reference(golden, name), bounds)
+
+
+def test_two_calls_are_bit_equal():
+    for k in (0, 1):
+        logits, msk, _ = shape_case(k)
+        a, b = kernel(logits, msk), kernel(logits, msk)
+        assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+
+
+def test_upstream_gradient_scales_the_gradient(bounds):
+    logits, msk, _ = shape_case(0)
+    one, scaled = kernel(logits, msk), kernel(logits, msk, upstream=1.7)
+    assert scaled[0] == one[0]
+    assert float(np.abs(scaled[2] / 1.7 - one[2]).max()) <= 1e-6 * float(np.abs(one[2]).max())
+    check("upstream 1.7", scaled, C.restate(logits.numpy(), msk.numpy(), upstream=1.7), bounds)
+
+
+def test_the_mask_bytes_are_read_in_place_and_not_written():
+    """the script flips msks[:, 0] in place; the kernel derives the label from the bytes and leaves them alone"""
+    from dahitra_amd.models import xbd
+    logits, msk, _ = shape_case(1)
+    dm = msk.cuda()
+    keep = dm.clone()
+    xbd.adapt_loss(logits.cuda().requires_grad_(True), dm).backward()
+    assert torch.equal(dm, keep)
+
+
+def test_wrappers_refuse_on_the_device_what_the_kernel_cannot_read():
+    from dahitra_amd import _lib, ops
+    from dahitra_amd.models import xbd
+    logits, msk = (t.cuda() for t in shape_case(1)[:2])
+    w = xbd.adapt_weights_dev(logits.device)
+    with pytest.raises(ValueError, match="not contiguous"):
+        ops.xbd_adapt_loss_fwd(logits.permute(0, 1, 3, 2), msk.permute(0, 1, 3, 2), w)
+    with pytest.raises(ValueError, match="msk"):
+        xbd.adapt_loss(logits, msk.float())
+    with pytest.raises(ValueError, match="msk"):
+        xbd.adapt_loss(logits, msk.long())
+    with pytest.raises(ValueError, match="weights_dev"):
+        ops.xbd_adapt_loss_fwd(logits, msk, w.cpu())
+    with pytest.raises(ValueError, match="logits"):
+        ops.xbd_adapt_loss_fwd(torch.zeros(1, 5, 8, 12, device=DEV), msk, w)
+    # the C entry: null pointers, an empty input, a short workspace -- nothing is launched
+    L, P, S = _lib.lib(), ops.P, ops.S
+    sums, parts, loss = (torch.full((n,), -7.0, device=DEV) for n in (18, 6, 1))
+    ws = torch.empty(ops._ws_bytes("dh_xbd_adapt_loss_workspace_size"), dtype=torch.uint8, device=DEV)
+    good = dict(logits=P(logits), msk=P(msk), B=1, HW=96, w=P(w), d=1.0, f=8.0, c=5.0, sums=P(sums), parts=P(parts), loss=P(loss),
+                ws=P(ws), wsb=ws.numel())
+    order = ("logits", "msk", "B", "HW", "w", "d", "f", "c", "sums", "parts", "loss", "ws", "wsb")
+    for change in (dict(logits=P(None)), dict(msk=P(None)), dict(w=P(None)), dict(B=0), dict(HW=0), dict(sums=P(None)),
+                   dict(parts=P(None)), dict(loss=P(None)), dict(ws=P(None)), dict(wsb=ws.numel() - 1)):
+        args = dict(good, **change)
+        assert L.dh_xbd_adapt_loss_fwd(*[args[k] for k in order], S()) != 0, change
+        assert L.dh_last_error().decode().startswith("xbd_adapt_loss"), (change, L.dh_last_error())
+    dl = torch.full_like(logits, -7.0)
+    assert L.dh_xbd_adapt_loss_bwd(P(logits), P(msk), P(None), P(w), P(None), 1.0, 8.0, 5.0, 1, 96, P(dl), S()) != 0
+    assert L.dh_xbd_adapt_loss_bwd(P(logits), P(msk), P(sums), P(w), P(None), 1.0, 8.0, 5.0, 1, 96, P(None), S()) != 0
+    torch.cuda.synchronize()
+    assert (sums == -7).all() and (parts == -7).all() and (loss == -7).all() and (dl == -7).all()
+
+
+# ---- the loader ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sources():
+    """3 sources of 96 x 96: noise images, a pre mask with bytes on both sides of 127, labels 0 .. 4 and one byte of 9"""
+    rng = np.random.RandomState(17)
+    n, H, W = 3, 96, 96
+    pre = rng.randint(0, 256, (n, H, W, 3)).astype(np.uint8)
+    post = rng.randint(0, 256, (n, H, W, 3)).astype(np.uint8)
+    pre_mask = rng.choice(np.array([0, 1, 127, 128, 255], dtype=np.uint8), size=(n, H, W))
+    label = rng.randint(0, 5, (n, H, W)).astype(np.uint8)
+    label[:, 4, 6] = 9                   # inside every window the tests cut
+    label[2, 50, 40] = 255
+    return pre, post, pre_mask, label
+
+
+@pytest.fixture(scope="module")
+def pipe(sources):
+    from dahitra_amd.datasets.xbd_pipeline import GpuXbdPipeline
+    return GpuXbdPipeline(*(torch.from_numpy(a).to(DEV) for a in sources), files=["AOI_a", "michael_b", "AOI_c"])
+
+
+@pytest.mark.parametrize("train", [True, False])
+@pytest.mark.parametrize("crop,origins", [(7, [(3, 1), (1, 0), (89, 89)]),                # the byte form, odd origins
+                                          (64, [(0, 0), (5, 3), (32, 4)]),                # the dword form: aligned and odd sources
+                                          (96, None)])                                    # the whole tile, as the script takes it
+def test_make_adapt_batch_equals_the_scripts_bytes(pipe, sources, crop, origins, train):
+    indices = [2, 0, 2]                                                                   # a repeated index
+    b = pipe.make_adapt_batch(indices, crop, origins, train=train)
+    img, msk, lbl = C.batch_reference(*sources, indices, crop, origins, train)
+    assert b['img'].dtype == torch.float32 and b['msk'].dtype == torch.uint8 and b['lbl_msk'].dtype == torch.uint8
+    assert tuple(b['msk'].shape) == (3, 4, crop, crop) and b['fn'] == ["AOI_c", "AOI_a", "AOI_c"]
+    assert np.array_equal(b['img'].cpu().numpy(), img)                                    # x / 127 - 1: the same float32 bits
+    assert np.array_equal(b['msk'].cpu().numpy(), msk)
+    assert np.array_equal(b['lbl_msk'].cpu().numpy(), lbl)
+    x0, y0 = origins[0] if origins else (0, 0)
+    nine = msk[0, :, 4 - y0, 6 - x0]                                                      # sources[3][2, 4, 6] == 9
+    assert not nine[1:].any() and (not train or not nine[0]) and lbl[0, 4 - y0, 6 - x0] == 0      # a label byte of 9 sets no plane
+    assert lbl.max() == 2 and (msk[:, 0] != msk[:, 1:].max(1)).any() == (not train)
+
+
+def test_make_adapt_batch_refuses_what_does_not_fit(pipe):
+    with pytest.raises(ValueError, match="origins"):
+        pipe.make_adapt_batch([0, 1], 64, [(0, 0)])
+    with pytest.raises(ValueError, match="origins"):
+        pipe.make_adapt_batch([0], 64, [(33, 0)])
+    with pytest.raises(ValueError, match="crop"):
+        pipe.make_adapt_batch([0], 97)
+    with pytest.raises(ValueError, match="indices"):
+        pipe.make_adapt_batch([3], 64)
+    with pytest.raises(ValueError, match="whole images"):
+        next(pipe.adapt_batches(1, 64, train=False))
+    with pytest.raises(ValueError, match="rng"):
+        next(pipe.adapt_batches(1, 64, train=True))
+
+
+@pytest.mark.parametrize("crop", [96, 64])
+def test_adapt_batches_consumes_exactly_two_draws_per_training_sample(pipe, sources, crop):
+    """the draws of lines 108-109, x0 then y0, also at the whole tile where both are 0: the generator ends where a twin ends that
+    shuffles the same list and calls randint twice per sample"""
+    rng, twin = random.Random(5), random.Random(5)
+    got = list(pipe.adapt_batches(2, crop, True, rng, indices=[0, 1, 2, 1, 0]))
+    order = [0, 1, 2, 1, 0]
+    twin.shuffle(order)
+    origins = [(twin.randint(0, 96 - crop), twin.randint(0, 96 - crop)) for _ in order]
+    assert rng.getstate() == twin.getstate()
+    assert [len(b['fn']) for b in got] == [2, 2, 1]
+    want = C.batch_reference(*sources, order, crop, origins, True)
+    assert np.array_equal(torch.cat([b['img'] for b in got]).cpu().numpy(), want[0])
+    assert np.array_equal(torch.cat([b['msk'] for b in got]).cpu().numpy(), want[1])
+    assert len(list(pipe.adapt_batches(2, crop, True, random.Random(1), indices=[0, 1, 2], drop_last=True))) == 1
+    val = list(pipe.adapt_batches(2, 96, False, indices=[2, 0]))
+    assert len(val) == 1 and np.array_equal(val[0]['msk'].cpu().numpy(), C.batch_reference(*sources, [2, 0], 96, None, False)[1])
+
+
+def test_adapt_trainset_reads_the_resident_class_table(capsys):
+    from dahitra_amd.datasets.xbd_pipeline import GpuXbdPipeline, split_indices
+    rng = np.random.RandomState(2)
+    n = 9
+    label = np.zeros((n, 32, 32), dtype=np.uint8)
+    for i in range(n):
+        k = (0, 300, 126, 125, 400, 251, 900, 167, 600)[i]
+        label[i].reshape(-1)[:k] = 4 if k in (125, 126) else rng.randint(1, 5, k)          # 125 fours: exactly 500, dropped
+    names = ["AOI%d" % i if i % 3 else "hurricane-michael_%d" % i for i in range(n)]
+    z = torch.zeros(n, 32, 32, 3, dtype=torch.uint8, device=DEV)
+    p = GpuXbdPipeline(z, z, z[..., 0], torch.from_numpy(label).to(DEV), files=names)
+    train_idxs, val_idxs = p.adapt_trainset(seed=0)
+    want_train, want_val = C.trainset_literal(names, list(label), lambda m: split_indices(m, 0.15, 0))
+    assert [names[i] for i in train_idxs] == want_train and [names[i] for i in val_idxs] == want_val
+    assert 3 not in train_idxs and 3 not in val_idxs and 0 not in train_idxs
+    label[1, 0, 0] = 7
+    q = GpuXbdPipeline(z, z, z[..., 0], torch.from_numpy(label).to(DEV), files=names)
+    with pytest.raises(ValueError, match="above 4"):
+        q.adapt_trainset()
+
+
+# ---- validation ---------------------------------------------------------------------------------------------------------------
+SENTINEL = -7
+PREFILL = np.arange(9, dtype=np.int64).reshape(3, 3) * 1000 + 17
+
+
+def val_inputs(B, H, W, seed):
+    """tests/_xbd_val_cases.synthetic at max(H, W), its conditions checked, cut to four channels, H x W and labels 0 .. 2"""
+    S = max(H, W)
+    x, msk, lbl, planted = V.synthetic(B, S, seed)
+    V.check_synthetic(x, msk, lbl, planted)
+    return (np.ascontiguousarray(x[:, :4, :H, :W]), np.ascontiguousarray(msk[:, :4, :H, :W]),
+            np.ascontiguousarray(lbl[:, :H, :W] % 3))
+
+
+@pytest.mark.parametrize("B,H,W,select", [(2, 8, 8, "reference"), (3, 33, 33, "reference"), (2, 5, 12, "building")])
+def test_three_class_counts_equal_the_restatement(B, H, W, select):
+    from dahitra_amd import ops
+    x, msk, lbl = val_inputs(B, H, W, seed=B * 100 + H)
+    want_ic, want_cc = C.val_counts(x, msk[:, 0], lbl, select=select)
+    assert want_cc.sum() > 0 and (want_cc[:, :2].sum(1) > 0).all(), "every class is counted"
+    dx, dmsk, dlbl = (torch.from_numpy(a).to(DEV) for a in (x, msk, lbl))
+    for plane in (dmsk, dmsk[:, 0], dmsk[:, 0].contiguous()):
+        ic = torch.full((B, 3), SENTINEL, dtype=torch.int64, device=DEV)
+        cc = torch.from_numpy(PREFILL.copy()).to(DEV)
+        ops.xbd_val_count(dx, plane, dlbl, ic, cc, thr=V.THR, select=select, classes=3)
+        assert np.array_equal(ic.cpu().numpy(), want_ic), (select, ic.tolist(), want_ic.tolist())
+        assert np.array_equal(cc.cpu().numpy() - PREFILL, want_cc), (select, want_cc.tolist())
+    # the four-class entry on the same planes plus one: the existing symbol is what it was
+    x5 = np.concatenate([x, np.full_like(x[:, :1], -8.0)], axis=1)
+    ic4 = torch.zeros(B, 3, dtype=torch.int64, device=DEV)
+    cc4 = torch.zeros(4, 3, dtype=torch.int64, device=DEV)
+    ops.xbd_val_count(torch.from_numpy(x5).to(DEV), dmsk[:, 0], dlbl, ic4, cc4, thr=V.THR, select=select)
+    w_ic, w_cc = V.counts(x5, msk[:, 0], lbl, select=select)
+    assert np.array_equal(ic4.cpu().numpy(), w_ic) and np.array_equal(cc4.cpu().numpy(), w_cc)
+
+
+def test_val_count_n_refuses_other_class_counts():
+    from dahitra_amd import _lib, ops
+    L, P, S = _lib.lib(), ops.P, ops.S
+    x = torch.zeros(1, 4, 8, 8, device=DEV)
+    m = torch.ones(1, 8, 8, dtype=torch.uint8, device=DEV)
+    ic = torch.full((1, 3), SENTINEL, dtype=torch.int64, device=DEV)
+    cc = torch.zeros(3, 3, dtype=torch.int64, device=DEV)
+    for nd in (0, 2, 5):
+        assert L.dh_xbd_val_count_n(P(x), P(m), 64, P(m), nd, 1, 8, 8, 0.3, 0, P(ic), P(cc), S()) != 0
+        assert L.dh_last_error().decode().startswith("xbd_val_count")
+    assert L.dh_xbd_val_count_n(P(x), P(m), 64, P(m), 3, 1, 8, 8, float("nan"), 0, P(ic), P(cc), S()) != 0
+    torch.cuda.synchronize()
+    assert (ic == SENTINEL).all() and not cc.any()
+    assert L.dh_xbd_val_count_n(P(x), P(m), 64, P(m), 3, 1, 8, 8, 0.3, 0, P(ic), P(cc), S()) == 0
+    torch.cuda.synchronize()
+    assert ic.cpu().tolist() == [[64, 64, 64]]
+
+
+# ---- the net ------------------------------------------------------------------------------------------------------------------
+NAME5, NAME4 = "xbd_unet_transformer_nodecpos", "xbd_unet_transformer_c4_nodecpos"
+
+
+def sliced_state(name5):
+    """the five-class deterministic state with its classifier cut to rows 0 .. 3"""
+    sd = O.deterministic_state(name5)
+    sd["classifier.weight"] = sd["classifier.weight"][:4].clone()
+    sd["classifier.bias"] = sd["classifier.bias"][:4].clone()
+    return sd
+
+
+def make4(dtype="fp32", decoder_pos=False):
+    from dahitra_amd.models.xbd import BASE_Transformer_UNet
+    net = BASE_Transformer_UNet(input_nc=3, output_nc=4, token_len=4, resnet_stages_num=4, with_pos='learned',
+                                with_decoder_pos='learned' if decoder_pos else None, enc_depth=1, dec_depth=8,
+                                compute_dtype=dtype).cuda()
+    net.load_state_dict(sliced_state("xbd_unet_transformer" if decoder_pos else NAME5))
+    return net
+
+
+def adapt_masks(lab):
+    """TrainData's four planes from a label map [B, 1, H, W] or [B, H, W] of 0 .. 4, uint8"""
+    lab = lab.reshape(lab.shape[0], *lab.shape[-2:])
+    m1, m2, m3 = lab == 1, lab == 2, (lab == 3) | (lab == 4)
+    return torch.stack([m1 | m2 | m3, m1, m2, m3], dim=1).to(torch.uint8)
+
+
+def batch_64(n, seed=13):
+    a, b, lab = O.synthetic_batch(n, 64, seed=seed, n_class=5)
+    return torch.cat([a, b], 1), adapt_masks(lab)
+
+
+@functools.lru_cache(None)
+def oracle_64():
+    """the five-class oracle at 2 x 6 x 64 x 64 in train mode: its logits, and the gradients of sum(logits[:, :4] * R)"""
+    x6, _ = batch_64(2)
+    R = torch.randn(2, 4, 64, 64, generator=torch.Generator().manual_seed(29))
+    st = O.XbdTrainState(NAME5, O.deterministic_state(NAME5))
+    ref = O.forward(st.sd, NAME5, x6, None, training=True)
+    (ref[:, :4] * R).sum().backward()
+    grads = {"classifier.weight": st.sd["classifier.weight"].grad[:4].clone(), "classifier.bias": st.sd["classifier.bias"].grad[:4].clone(),
+             "resnet.layer1.0.conv1.weight": st.sd["resnet.layer1.0.conv1.weight"].grad.clone()}
+    return x6, R, ref.detach()[:, :4].clone(), grads
+
+
+@pytest.mark.parametrize("cdtype", ["fp32", "bf16x3"])
+def test_c4_net_equals_the_first_four_channels_of_the_five_class_oracle(cdtype):
+    """fp32: small = 4 with all four lanes real (nchw_to_nhwc piece, conv2d_wgrad(cout_real=4), colsum, head_dgrad3x3<float, 4>);
+    bf16x3: conv3x3_head, head_dlogits_pack and head_relu_bwd at four of eight"""
+    x6, R, want, grads = oracle_64()
+    net = make4(cdtype).train()
+    out = net(x6.cuda())
+    assert tuple(out.shape) == (2, 4, 64, 64)
+    err = float((out.detach().cpu() - want).abs().max()) / float(want.abs().max())
+    print("c4 %s: logits rel err %.3e" % (cdtype, err))
+    assert err <= LOGIT_TOL, err
+    (out * R.cuda()).sum().backward()
+    params = dict(net.named_parameters())
+    for k, w in grads.items():
+        e = float((params[k].grad.cpu() - w).abs().max())
+        print("c4 %s: grad %s err %.3e of max %.3e" % (cdtype, k, e, float(w.abs().max())))
+        assert e <= GRAD_TOL * float(w.abs().max()), (k, e, float(w.abs().max()))
+
+
+def test_c4_bf16_gradients_are_finite_and_a_loss_falls():
+    from dahitra_amd.models import xbd
+    x6, msk = (t.cuda() for t in batch_64(2))
+    net = make4("bf16").train()
+    opt = xbd.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-7)
+    hist = []
+    for it in range(6):
+        _, loss, _ = xbd.adapt_eager_step(net, opt, x6, msk)
+        if it == 0:
+            assert all(torch.isfinite(p.grad).all() for p in net.parameters() if p.grad is not None)
+        hist.append(float(loss))
+    assert hist[-1] < hist[0], hist
+
+
+def test_c4_decoder_pos_net_at_1024_equals_the_five_class_net():
+    """one eval forward of the script's own net (with_decoder_pos='learned', 1 x 6 x 1024 x 1024) against the first four channels
+    of the five-class net with the same weights, both on the device"""
+    from dahitra_amd.models.xbd import BASE_Transformer_UNet
+    a, b, _ = O.synthetic_batch(1, 1024, seed=11, n_class=5)
+    x6 = torch.cat([a, b], 1).cuda()
+    five = BASE_Transformer_UNet(output_nc=5, with_decoder_pos='learned').cuda()
+    five.load_state_dict(O.deterministic_state("xbd_unet_transformer"))
+    with torch.no_grad():
+        want = five.eval()(x6)[:, :4]
+        got = make4(decoder_pos=True).eval()(x6)
+    assert tuple(got.shape) == (1, 4, 1024, 1024)
+    err = float((got - want).abs().max()) / float(want.abs().max())
+    print("c4 decoder_pos 1024: rel err %.3e" % err)
+    assert err <= LOGIT_TOL_1024, err
+
+
+def test_load_snapshot_from_a_five_class_state_dict(tmp_path):
+    from dahitra_amd.models import xbd
+    from dahitra_amd.models.xbd import BASE_Transformer_UNet
+    path = str(tmp_path / "five")
+    torch.save({'epoch': 7, 'state_dict': {'module.' + k: v for k, v in O.deterministic_state(NAME5).items()}, 'best_score': 0.25}, path)
+    net = BASE_Transformer_UNet(output_nc=4)
+    own = {k: net.state_dict()[k].clone() for k in ("classifier.weight", "classifier.bias")}
+    assert xbd.load_snapshot(net, path) == (7, 0.25)
+    net = net.cuda().eval()
+    sd = net.state_dict()
+    assert all(torch.equal(sd[k].cpu(), v) for k, v in own.items())                    # classifier.*: its initial values
+    assert torch.equal(sd["conv_layer2_0.0.weight"].cpu(), O.deterministic_state(NAME5)["conv_layer2_0.0.weight"])
+    x6, _ = batch_64(1)
+    with torch.no_grad():
+        assert torch.isfinite(net(x6.cuda())).all()
+
+
+# ---- validation on the model ----------------------------------------------------------------------------------------------------
+def test_validate_adapt_prints_the_scripts_line_and_scores_three_classes(capsys):
+    from dahitra_amd.models import xbd
+    from dahitra_amd.datasets.xbd_pipeline import GpuXbdPipeline
+    rng = np.random.RandomState(4)
+    n, S = 3, 64
+    u8 = lambda *s: rng.randint(0, 256, s).astype(np.uint8)
+    label = np.kron(rng.randint(0, 5, (n, 8, 8)), np.ones((1, 8, 8))).astype(np.uint8)
+    p = GpuXbdPipeline(*(torch.from_numpy(a).to(DEV) for a in (u8(n, S, S, 3), u8(n, S, S, 3), ((label > 0) * 255).astype(np.uint8), label)))
+    net = make4().eval()
+    capsys.readouterr()
+    sc, parts, ic, cc = xbd.validate_adapt(net, p.adapt_batches(2, S, train=False), want_counts=True)
+    line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("Val Score")]
+    assert ic.shape == (3, 3) and cc.shape == (3, 3) and cc.sum() > 0
+    want, wparts = xbd.val_score(ic, cc, classes=3)
+    lit = C.val_score_literal(ic, cc)
+    assert (sc == want or (np.isnan(sc) and np.isnan(want))) and (lit[0] == want or np.isnan(want))
+    f = wparts['f1_per_class']
+    assert line == ["Val Score: {}, Dice: {}, F1: {}, F1_0: {}, F1_1: {}, F1_2: {}".format(want, wparts['dice'], wparts['f1'], f[0], f[1], f[2])]
+    # the eager path counts the same integers (a batch of 2 replayed, the ragged batch of 1 eager, against all eager)
+    _, _, ic_e, cc_e = xbd.validate_adapt(net, p.adapt_batches(2, S, train=False), graph=False, want_counts=True)
+    assert np.array_equal(ic, ic_e) and np.array_equal(cc, cc_e)
+    step = next(iter(net.__dict__['_xbd_eval_steps'].values()))
+    assert step.classes == 3 and tuple(step.class_counts.shape) == (3, 3)
+
+
+# ---- the step -----------------------------------------------------------------------------------------------------------------
+def test_hip_graph_adapt_step_equals_eager_step():
+    """three steps with a MultiStepLR whose milestone follows the first, WITH the clip: loss and parts at 1e-5, states at
+    1e-6 + 1e-5 max, the bounds of test_hip_graph_xbd_step_equals_eager_step"""
+    from dahitra_amd.graph import GraphedXbdAdaptStep
+    from dahitra_amd.models import xbd
+    x6, msk = (t.cuda() for t in batch_64(2))
+    eager = make4().train()
+    opt_e = xbd.AdamW(eager.parameters(), lr=1e-4, weight_decay=1e-7)
+    sch_e = torch.optim.lr_scheduler.MultiStepLR(opt_e, milestones=[1], gamma=0.6)
+    graphed = make4().train()
+    opt_g = xbd.AdamW(graphed.parameters(), lr=1e-4, weight_decay=1e-7, capturable=True)
+    sch_g = torch.optim.lr_scheduler.MultiStepLR(opt_g, milestones=[1], gamma=0.6)
+    step = GraphedXbdAdaptStep(graphed, opt_g, x6, msk)
+    assert step.lab.dtype == torch.uint8 and step.max_norm == 0.999
+    for it in range(3):
+        eager.zero_grad()
+        le, pe = xbd.adapt_loss(eager(x6), msk, want_parts=True)
+        le.backward()
+        norm = float(xbd.clip_grad_norm_(eager.parameters(), 0.999))
+        if it == 0:
+            print("total gradient norm of step one: %.3f" % norm)
+            assert norm > 0.999, norm                                  # the clip is active
+        opt_e.step()
+        sch_e.step()
+        lg = step(x6, msk)
+        sch_g.step()
+        assert abs(float(le) - float(lg)) <= 1e-5 * abs(float(le)), (it, float(le), float(lg))
+        pe, pg = pe.cpu().numpy(), step.parts.cpu().numpy()
+        assert pg.shape == (6,) and pg[5] == pe[5] == 0
+        assert np.all(np.abs(pe[:5] - pg[:5]) <= 1e-5 * np.abs(pe[:5])), (it, pe, pg)
+    assert opt_e.param_groups[0]["lr"] == opt_g.param_groups[0]["lr"] == pytest.approx(0.6e-4)
+    se, sg = eager.state_dict(), graphed.state_dict()
+    for k in se:
+        if se[k].dtype.is_floating_point:
+            assert float((se[k] - sg[k]).abs().max()) <= 1e-6 + 1e-5 * float(se[k].abs().max()), k
+    assert opt_g.step_count(graphed) == 3
+
+
+def test_a_replay_on_the_held_inputs_equals_a_replay_given_them():
+    from dahitra_amd.graph import GraphedXbdAdaptStep
+    from dahitra_amd.models import xbd
+    x6, msk = (t.cuda() for t in batch_64(2))
+    steps = []
+    for _ in range(2):
+        net = make4().train()
+        opt = xbd.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-7, capturable=True)
+        steps.append(GraphedXbdAdaptStep(net, opt, x6, msk))
+    given, held = steps
+    for it in range(3):
+        lg, lh = float(given(x6.clone(), msk.clone())), float(held())
+        pg, ph = given.parts.cpu().numpy(), held.parts.cpu().numpy()
+        assert abs(lg - lh) <= 1e-5 * abs(lh), (it, lg, lh)
+        assert np.all(np.abs(pg[:5] - ph[:5]) <= 1e-5 * np.abs(ph[:5])), (it, pg, ph)
+
+
+def test_train_epoch_adapt_meters_are_the_means_of_the_steps(pipe, capsys):
+    """three batches (2, 2, 1) of the synthetic pipeline at crop 64: the epoch's meters, from its one read, against an eager twin
+    whose values are read step by step; the ragged last batch runs eagerly inside the epoch"""
+    from dahitra_amd.models import xbd
+    batches = list(pipe.adapt_batches(2, 64, True, random.Random(0), indices=[0, 1, 2, 1, 0]))
+    assert [b['img'].shape[0] for b in batches] == [2, 2, 1]
+    net = make4().train()
+    opt = xbd.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-7, capturable=True)
+    sch = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=[1], gamma=0.6)
+    capsys.readouterr()
+    meters = xbd.train_epoch_adapt(0, net, opt, sch, batches)
+    line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("epoch: ")]
+    twin = make4().train()
+    opt_t = xbd.AdamW(twin.parameters(), lr=1e-4, weight_decay=1e-7)
+    rows = []
+    for b in batches:
+        _, loss, parts = xbd.adapt_eager_step(twin, opt_t, b['img'], b['msk'])
+        rows.append([loss.item()] + [v.item() for v in parts])
+    rows, w = np.asarray(rows, dtype=np.float64), np.array([2.0, 2.0, 1.0])
+    assert meters['steps'] == 3 and meters['samples'] == 5 and meters['lr'] == pytest.approx(0.6e-4)
+    for key, col in (('loss', 0), ('loss0', 1), ('loss1', 2), ('loss2', 3), ('loss3', 4), ('ce', 5)):
+        want = (rows[:, col] * w).sum() / w.sum()
+        assert abs(meters[key] - want) <= 1e-5 * abs(want), (key, meters[key], want)
+    assert line == ["epoch: 0; lr 0.0000600; Loss {:.4f}; loss2 {:.4f}; Dice {:.4f}".format(meters['loss'], meters['loss1'],
+                                                                                            meters['loss3'])]
+    assert len(net.__dict__['_xbd_adapt_steps']) == 1                   # the recorded step is kept on the model
+
+
+# ---- two data-parallel ranks ------------------------------------------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _adapt_rank(rank, world, port, overlap, steps, out):
+    """one gloo rank on cuda:0, as tests/test_xbd_unet_step_gpu.py::_unet_rank"""
+    os.environ.update(RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      DAHITRA_OVERLAP=overlap)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import torch.distributed as dist
+    from dahitra_amd import parallel
+    from dahitra_amd.graph import GraphedXbdAdaptStep
+    from dahitra_amd.models import xbd
+    parallel.init_from_env("gloo")
+    torch.cuda.set_device(0)
+    net = make4().train() if rank == 0 else xbd.BASE_Transformer_UNet(output_nc=4, compute_dtype="fp32").cuda().train()
+    net._ensure_arena(torch.device("cuda", 0))
+    parallel.broadcast_params_(net)                          # rank 1 keeps its random init: the broadcast must fix it
+    x6, msk = batch_64(2 * world)
+    lo, hi = parallel.shard_batch(2 * world, rank, world)
+    x6, msk = x6[lo:hi].cuda(), msk[lo:hi].cuda()
+    opt = xbd.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-7, capturable=True)
+    step = GraphedXbdAdaptStep(net, opt, x6, msk)
+    assert step.exchange and step.max_norm == 0.999
+    assert (step.split_off is None) == (overlap == "0")
+    for _ in range(steps):
+        step(x6, msk)
+    torch.cuda.synchronize()
+    torch.save({k: v.cpu() for k, v in net.state_dict().items()}, out % rank)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@functools.lru_cache(None)
+def two_replica_emulation(steps=2):
+    """the single-process emulation of two ranks: per-shard gradients of two replicas, the sum of the two arenas scaled by 1 / 2,
+    clip_grad_norm_(0.999) over the averaged arena, xbd.AdamW.step() on every replica -> replica 0's state on the host"""
+    from dahitra_amd import ops
+    from dahitra_amd.models import xbd
+    x6, msk = batch_64(4)
+    nets = [make4().train() for _ in range(2)]
+    opts = [xbd.AdamW(n.parameters(), lr=1e-3, weight_decay=1e-7) for n in nets]
+    for _ in range(steps):
+        for r, net in enumerate(nets):
+            net.zero_grad()
+            sl = slice(2 * r, 2 * r + 2)
+            xbd.adapt_loss(net(x6[sl].cuda()), msk[sl].cuda()).backward()
+        total = nets[0].flat_params()[1] + nets[1].flat_params()[1]
+        for net, opt in zip(nets, opts):
+            g = net.flat_params()[1]
+            g.copy_(total)
+            ops.scale_into(g, torch.tensor([0.5], device=g.device), g)
+            xbd.clip_grad_norm_(net.parameters(), 0.999)
+            opt.step()
+    return {k: v.cpu() for k, v in nets[0].state_dict().items()}
+
+
+@pytest.mark.parametrize("overlap", ["0", "1"])
+def test_two_ranks_of_the_adapt_step_match_the_single_process_emulation(tmp_path, overlap):
+    """GraphedXbdAdaptStep on two gloo ranks, two steps, in the serial and in the overlapped form, WITH the clip: both ranks end
+    with equal parameters, within the 2e-5 of tests/test_parallel_gpu.py of the emulation"""
+    import torch.multiprocessing as mp
+    out = str(tmp_path / "rank%d.pt")
+    mp.start_processes(_adapt_rank, args=(2, _free_port(), overlap, 2, out), nprocs=2, join=True, start_method="spawn")
+    sd0, sd1 = torch.load(out % 0), torch.load(out % 1)
+    ref = two_replica_emulation()
+    worst = 0.0
+    for k, v in sd0.items():
+        if not v.dtype.is_floating_point or "running_" in k or "num_batches" in k:
+            continue                                   # BatchNorm buffers are per replica
+        assert torch.equal(v, sd1[k]), k               # same reduced gradient, same update on both ranks
+        worst = max(worst, float((v - ref[k]).abs().max()))
+    print("two ranks, DAHITRA_OVERLAP=%s: worst distance from the emulation %.3e" % (overlap, worst))
+    assert worst <= 2e-5, worst
