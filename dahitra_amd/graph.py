@@ -674,7 +674,39 @@ class GraphedXbdStep(GraphedTrainStep):
         self.opt.step()
 
 
-class GraphedXbdUnetStep(GraphedXbdStep):
+class _GraphedXbdScriptStep(GraphedXbdStep):
+    """What the recorded steps of the two training scripts share: the check of imgs / msks (/ lbl_msk), the loss weights made
+    before the capture, `parts`, and the script's loss at engine level.  A subclass names its row of ops._XBD_LOSS_FORMS in
+    `_form` and gives `_eager_step(update)` -> (logits, loss, parts)."""
+    ENGINE_LEVEL = True
+    _form = None
+    lbl = labels = None                   # what the loss pair takes where the form has no lbl
+
+    def _build_script(self, what, net, opt, imgs, msks, lbl_msk, weights_dev, ce_scale, warmup):
+        channels = ops._XBD_LOSS_FORMS[self._form][0]
+        a = ops._Args(what, cpu_error=True)
+        B, _, H, W = a.tensor("imgs", imgs, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 6 and t.numel() > 0,
+                              "[B, 6, H, W], not empty").shape
+        a.tensor("msks", msks, torch.uint8, (B, channels, H, W), "[%d, %d, %d, %d] like imgs" % (B, channels, H, W))
+        if lbl_msk is not None:
+            a.tensor("lbl_msk", lbl_msk, torch.uint8, (B, H, W), "[%d, %d, %d] like imgs" % (B, H, W))
+        a.placed()
+        self.parts, self._ce_scale = None, ce_scale
+        self._w = weights_dev(imgs.device)        # made here: no host-to-device copy inside the capture
+        self._build(net, opt, (imgs, msks, lbl_msk), warmup)          # one per name of INPUTS: a step without "lbl" holds two
+
+    def _eager_body(self, include_opt):
+        self.logits, loss, self.parts = self._eager_step(include_opt)
+        return loss
+
+    def _loss_and_grad(self, logits):
+        """the script's loss and its gradient at engine level: two launches forward, one backward, the masks read as bytes"""
+        lo, label = logits.float().contiguous(), (self.lbl, self.labels)
+        loss, self.parts, sums = ops._xbd_loss_fwd(self._form, lo, self.lab, *label, self._w, 1.0, 8.0, self._ce_scale)
+        return loss, ops._xbd_loss_bwd(self._form, lo, self.lab, *label, sums, self._w, None, 1.0, 8.0, self._ce_scale)
+
+
+class GraphedXbdUnetStep(_GraphedXbdScriptStep):
     """The step of xBD_code/train_unettransformer.py:436-481, the script that trains DAHiTra proper, as one HIP graph: forward of
     the 6-channel model, its loss (models/xbd.unet_loss: five ComboLoss terms weighted 0.1, 0.1, 0.6, 0.3, 1 plus 8 * the
     class-weighted cross-entropy of the masked logits) at engine level, backward, NO gradient clip (commented out at line 480)
@@ -687,7 +719,7 @@ class GraphedXbdUnetStep(GraphedXbdStep):
     the kernel; lbl_msk is neither kept nor copied).  A scheduler's learning rate reaches the replay through opt.sync_hyper, as in
     the parent.  ValueError for a label mode, dtype or shape that does not fit, before anything is recorded."""
     INPUTS = ("a", "lab", "lbl")          # imgs, msks, lbl_msk (lbl is None under labels='damage')
-    ENGINE_LEVEL = True
+    _form = "unet"
     max_norm = None                       # the script does not clip
 
     def __init__(self, net, opt, imgs, msks, lbl_msk=None, labels='lbl_msk', warmup=3):
@@ -697,35 +729,19 @@ class GraphedXbdUnetStep(GraphedXbdStep):
             raise ValueError("%s: labels %r is not one of %s" % (what, labels, sorted(ops.XBD_UNET_LABELS)))
         if labels == 'lbl_msk' and lbl_msk is None:
             raise ValueError("%s: labels='lbl_msk' reads lbl_msk, which is None" % what)
-        a = ops._Args(what, cpu_error=True)
-        B, _, H, W = a.tensor("imgs", imgs, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 6 and t.numel() > 0,
-                              "[B, 6, H, W], not empty").shape
-        a.tensor("msks", msks, torch.uint8, (B, 5, H, W), "[%d, 5, %d, %d] like imgs" % (B, H, W))
-        if labels == 'lbl_msk':
-            a.tensor("lbl_msk", lbl_msk, torch.uint8, (B, H, W), "[%d, %d, %d] like imgs" % (B, H, W))
-        a.placed()
-        self.labels, self.parts = labels, None
-        self._w = xbd.unet_weights_dev(imgs.device)        # made here: no host-to-device copy inside the capture
-        self._build(net, opt, (imgs, msks, lbl_msk if labels == 'lbl_msk' else None), warmup)
+        self.labels = labels
+        self._build_script(what, net, opt, imgs, msks, lbl_msk if labels == 'lbl_msk' else None, xbd.unet_weights_dev,
+                           xbd.UNET_CE_SCALE, warmup)
 
     def __call__(self, imgs=None, msks=None, lbl_msk=None):
         return super().__call__(imgs, msks, lbl_msk)
 
-    def _eager_body(self, include_opt):
+    def _eager_step(self, update):
         from .models import xbd
-        self.logits, loss, self.parts = xbd.unet_eager_step(self.net, self.opt, self.a, self.lab, self.lbl, self.labels,
-                                                            update=include_opt)
-        return loss
-
-    def _loss_and_grad(self, logits):
-        """the script's loss and its gradient at engine level: two launches forward, one backward, the masks read as bytes"""
-        from .models import xbd
-        lo = logits.float().contiguous()
-        loss, self.parts, sums = ops.xbd_unet_loss_fwd(lo, self.lab, self.lbl, self.labels, self._w, 1.0, 8.0, xbd.UNET_CE_SCALE)
-        return loss, ops.xbd_unet_loss_bwd(lo, self.lab, self.lbl, self.labels, sums, self._w, None, 1.0, 8.0, xbd.UNET_CE_SCALE)
+        return xbd.unet_eager_step(self.net, self.opt, self.a, self.lab, self.lbl, self.labels, update=update)
 
 
-class GraphedXbdAdaptStep(GraphedXbdStep):
+class GraphedXbdAdaptStep(_GraphedXbdScriptStep):
     """The step of xBD_code/train_adapt.py:326-347, the Ida-BD adaptation of the FOUR-output DAHiTra, as one HIP graph: forward of
     the 6-channel model, its loss (models/xbd.adapt_loss: four ComboLoss terms weighted 0.1, 0.8, 2, 8 plus 5 * the class-weighted
     cross-entropy of the raw logits) at engine level, backward, clip_grad_norm_(0.999) (line 346) and the hand-rolled AdamW.
@@ -738,18 +754,12 @@ class GraphedXbdAdaptStep(GraphedXbdStep):
     the ranks, then the clip over the complete arena, then the update.  A scheduler's learning rate reaches the replay through
     opt.sync_hyper, as in the parent.  ValueError for a dtype or shape that does not fit, before anything is recorded."""
     INPUTS = ("a", "lab")          # imgs, msks
-    ENGINE_LEVEL = True
+    _form = "adapt"
 
     def __init__(self, net, opt, imgs, msks, max_norm=0.999, warmup=3):
         from .models import xbd
-        a = ops._Args("GraphedXbdAdaptStep", cpu_error=True)
-        B, _, H, W = a.tensor("imgs", imgs, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 6 and t.numel() > 0,
-                              "[B, 6, H, W], not empty").shape
-        a.tensor("msks", msks, torch.uint8, (B, 4, H, W), "[%d, 4, %d, %d] like imgs" % (B, H, W))
-        a.placed()
-        self.max_norm, self.parts = max_norm, None
-        self._w = xbd.adapt_weights_dev(imgs.device)        # made here: no host-to-device copy inside the capture
-        self._build(net, opt, (imgs, msks), warmup)
+        self.max_norm = max_norm
+        self._build_script("GraphedXbdAdaptStep", net, opt, imgs, msks, None, xbd.adapt_weights_dev, xbd.ADAPT_CE_SCALE, warmup)
 
     def __call__(self, imgs=None, msks=None):
         return super().__call__(imgs, msks)
@@ -761,15 +771,6 @@ class GraphedXbdAdaptStep(GraphedXbdStep):
             self._update()
         return loss
 
-    def _eager_body(self, include_opt):
+    def _eager_step(self, update):
         from .models import xbd
-        self.logits, loss, self.parts = xbd.adapt_eager_step(self.net, self.opt, self.a, self.lab, self.max_norm,
-                                                             update=include_opt)
-        return loss
-
-    def _loss_and_grad(self, logits):
-        """the script's loss and its gradient at engine level: two launches forward, one backward, the masks read as bytes"""
-        from .models import xbd
-        lo = logits.float().contiguous()
-        loss, self.parts, sums = ops.xbd_adapt_loss_fwd(lo, self.lab, self._w, 1.0, 8.0, xbd.ADAPT_CE_SCALE)
-        return loss, ops.xbd_adapt_loss_bwd(lo, self.lab, sums, self._w, None, 1.0, 8.0, xbd.ADAPT_CE_SCALE)
+        return xbd.adapt_eager_step(self.net, self.opt, self.a, self.lab, self.max_norm, update=update)

@@ -44,7 +44,7 @@ Mirrored interfaces (same names, argument meaning, error behaviour):
         damage class per building by vote, and the building-level confusion and F1 against the ground truth
     dilate / erode / opening / closing / fill_holes / clean_footprint   no counterpart: square-window morphology and hole
         filling of a footprint before its buildings are counted (scipy.ndimage's binary_* functions are the oracle)
-Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_unet_loss.hip, csrc/xbd_adapt_loss.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_ensemble.hip, csrc/xbd_visual.hip,
+Everything computes through libdahitra_hip.so (csrc/xbd_step.hip, csrc/xbd_script_loss.hip, csrc/xbd_eval.hip, csrc/xbd_predict.hip, csrc/xbd_ensemble.hip, csrc/xbd_visual.hip,
 csrc/xbd_buildings.hip, csrc/xbd_morph.hip + the shared model kernels); CPU tensors are refused.  val_score alone is host arithmetic: the reference's float64 numpy expressions on the integer counts."""
 import os
 
@@ -161,34 +161,39 @@ def xbd_loss(out, msks, channel_weights=CHANNEL_WEIGHTS, dice=1.0, focal=8.0, wa
     return (loss, channel) if want_channels else loss
 
 
-# ---- loss of xBD_code/train_unettransformer.py (lines 438-461, 562-564) --------------------------------------
-class _UnetLoss(torch.autograd.Function):
+# ---- losses of xBD_code/train_unettransformer.py (lines 438-461, 562-564) and xBD_code/train_adapt.py (lines 332-342) ----------
+class _ScriptLoss(torch.autograd.Function):
+    """both scripts' losses: `form` is the row of ops._XBD_LOSS_FORMS, lbl and labels are None where the form has no lbl"""
     @staticmethod
-    def forward(ctx, logits, msks, lbl, labels, weights_dev, dice_w, focal_w, ce_w):
-        loss, parts, sums = ops.xbd_unet_loss_fwd(logits, msks, lbl, labels, weights_dev, dice_w, focal_w, ce_w)
+    def forward(ctx, form, logits, msks, lbl, labels, weights_dev, dice_w, focal_w, ce_w):
+        loss, parts, sums = ops._xbd_loss_fwd(form, logits, msks, lbl, labels, weights_dev, dice_w, focal_w, ce_w)
         ctx.save_for_backward(logits, msks, lbl, sums, weights_dev)
-        ctx.how = (labels, dice_w, focal_w, ce_w)
+        ctx.how = (form, labels, dice_w, focal_w, ce_w)
         ctx.mark_non_differentiable(parts)
         return loss, parts
 
     @staticmethod
     def backward(ctx, dloss, _dparts):
         logits, msks, lbl, sums, weights_dev = ctx.saved_tensors
-        labels, dice_w, focal_w, ce_w = ctx.how
+        form, labels, dice_w, focal_w, ce_w = ctx.how
         up = dloss.detach().to(torch.float32).reshape(1).contiguous()
-        return (ops.xbd_unet_loss_bwd(logits, msks, lbl, labels, sums, weights_dev, up, dice_w, focal_w, ce_w),) + (None,) * 7
+        return (None, ops._xbd_loss_bwd(form, logits, msks, lbl, labels, sums, weights_dev, up, dice_w, focal_w, ce_w)) + (None,) * 7
+
+
+def _loss_weights_dev(what, device, n, channel_weights, ce_weights):
+    key = (str(device), tuple(float(v) for v in channel_weights), tuple(float(v) for v in ce_weights))
+    if len(key[1]) != n or len(key[2]) != n:
+        raise ValueError("%s: channel_weights %r and ce_weights %r must hold %d numbers each" % (what, key[1], key[2], n))
+    w = _weights.get(key)
+    if w is None:
+        w = _weights[key] = torch.tensor(key[1] + key[2], dtype=torch.float32, device=device)
+    return w
 
 
 def unet_weights_dev(device, channel_weights=UNET_CHANNEL_WEIGHTS, ce_weights=UNET_CE_WEIGHTS):
     """the 5 channel weights and the 5 class weights as ONE cached device tensor [10], the form ops.xbd_unet_loss_fwd takes (no
     host-to-device copy inside a HIP-graph capture).  ValueError unless both hold 5 numbers."""
-    key = (str(device), tuple(float(v) for v in channel_weights), tuple(float(v) for v in ce_weights))
-    if len(key[1]) != 5 or len(key[2]) != 5:
-        raise ValueError("unet_loss: channel_weights %r and ce_weights %r must hold 5 numbers each" % (key[1], key[2]))
-    w = _weights.get(key)
-    if w is None:
-        w = _weights[key] = torch.tensor(key[1] + key[2], dtype=torch.float32, device=device)
-    return w
+    return _loss_weights_dev("unet_loss", device, 5, channel_weights, ce_weights)
 
 
 def unet_loss(out, msks, lbl_msk=None, labels='lbl_msk', channel_weights=UNET_CHANNEL_WEIGHTS, ce_weights=UNET_CE_WEIGHTS,
@@ -210,8 +215,8 @@ def unet_loss(out, msks, lbl_msk=None, labels='lbl_msk', channel_weights=UNET_CH
     lbl = lbl_msk.contiguous() if torch.is_tensor(lbl_msk) and labels != 'damage' else None
     if labels == 'lbl_msk' and lbl is None:
         raise ValueError("unet_loss: labels='lbl_msk' reads lbl_msk, which is %r" % (lbl_msk,))
-    loss, parts = _UnetLoss.apply(out.float().contiguous(), msks.contiguous() if torch.is_tensor(msks) else msks, lbl, labels, w,
-                                  float(dice), float(focal), float(ce))
+    loss, parts = _ScriptLoss.apply("unet", out.float().contiguous(), msks.contiguous() if torch.is_tensor(msks) else msks, lbl,
+                                    labels, w, float(dice), float(focal), float(ce))
     return (loss, parts) if want_parts else loss
 
 
@@ -582,28 +587,64 @@ def unet_eager_step(model, optimizer, imgs, msks, lbl_msk, labels, update=True):
     return logits.detach(), loss.detach(), parts
 
 
-def _unet_train_step(model, optimizer, first, labels, graph):
-    """run(batch) -> (loss, parts) device tensors for the batches of one epoch: batches of the first batch's shape replay the
-    model's recorded GraphedXbdUnetStep (kept on the model per shape, label mode, optimizer and device), any other shape -- a
-    ragged last batch -- and graph=False take the eager step"""
+def _script_train_step(step_class, eager_step, slot, fields, extra, model, optimizer, first, graph):
+    """run(batch) -> (loss, parts) device tensors for the batches of one epoch of a training script: batches of the first batch's
+    shape replay the model's recorded step -- graph.<step_class>, kept in the model's `slot` per shape, `extra`, optimizer and
+    device -- any other shape -- a ragged last batch -- and graph=False take `eager_step`.  fields: the batch's entries that the
+    step takes, in its order; extra: what its constructor and the eager step take after them."""
     _device_u8("training", first['img'], first['msk'])
 
     def eager(batch):
-        return unet_eager_step(model, optimizer, batch['img'], batch['msk'], batch['lbl_msk'], labels)[1:]
+        return eager_step(model, optimizer, *(batch[f] for f in fields), *extra)[1:]
     if not graph:
         return eager
-    from ..graph import GraphedXbdUnetStep
+    from .. import graph as graphs
     imgs = first['img']
     model._ensure_arena(imgs.device)
-    step = _kept_step(model, '_xbd_unet_steps', (tuple(imgs.shape), labels, id(optimizer), str(imgs.device)),
-                      lambda: GraphedXbdUnetStep(model, optimizer, imgs, first['msk'], first['lbl_msk'], labels),
+    step = _kept_step(model, slot, (tuple(imgs.shape),) + extra + (id(optimizer), str(imgs.device)),
+                      lambda: getattr(graphs, step_class)(model, optimizer, *(first[f] for f in fields), *extra),
                       lambda step: step._generation == model._arena.generation and step.opt is optimizer)
 
     def replay(batch):
         if tuple(batch['img'].shape) != tuple(imgs.shape):
             return eager(batch)
-        return step(batch['img'], batch['msk'], batch['lbl_msk']), step.parts
+        return step(*(batch[f] for f in fields)), step.parts
     return replay
+
+
+def _unet_train_step(model, optimizer, first, labels, graph):
+    """_script_train_step of GraphedXbdUnetStep, kept per shape, label mode, optimizer and device"""
+    return _script_train_step('GraphedXbdUnetStep', unet_eager_step, '_xbd_unet_steps', ('img', 'msk', 'lbl_msk'), (labels,),
+                              model, optimizer, first, graph)
+
+
+def _train_epoch(what, current_epoch, model, optimizer, scheduler, batches, step_for, n_parts, columns, printed, check=None):
+    """The epoch of train_epoch_unet and train_epoch_adapt.  step_for(first batch) -> run(batch) -> (loss, parts [n_parts]); every
+    step's row [loss, parts...] goes into a device buffer, read ONCE when the epoch is over; check(rows), if given, may refuse
+    the epoch before the scheduler moves.  columns: meter name -> column of the row, AverageMeter's mean weighted by the batch
+    size; printed: the three meters of the script's closing line."""
+    model.train()
+    run, rows, sizes = None, None, []
+    for batch in batches:
+        if run is None:
+            run = step_for(batch)
+        loss, parts = run(batch)
+        rows, row = _next_rows(rows, len(sizes), 1, (1 + n_parts,), torch.float32, loss.device)
+        row[0, 0:1].copy_(loss.reshape(1), non_blocking=True)
+        row[0, 1:].copy_(parts, non_blocking=True)
+        sizes.append(int(batch['img'].shape[0]))
+    if rows is None:
+        raise ValueError("%s: no batches" % what)
+    host = rows[:len(sizes)].cpu().numpy().astype(np.float64)          # the epoch's one read
+    if check is not None:
+        check(host)
+    w = np.asarray(sizes, dtype=np.float64)
+    meters = {k: float((host[:, col] * w).sum() / w.sum()) for k, col in columns}        # AverageMeter: sum(val * n) / sum(n)
+    scheduler.step()
+    lr = optimizer.param_groups[-1]['lr']
+    print("epoch: {}; lr {:.7f}; Loss {:.4f}; loss2 {:.4f}; Dice {:.4f}".format(current_epoch, lr, *(meters[k] for k in printed)))
+    meters.update(lr=lr, steps=len(sizes), samples=int(w.sum()))
+    return meters
 
 
 def train_epoch_unet(current_epoch, model, optimizer, scheduler, batches, labels='lbl_msk', graph=True):
@@ -623,61 +664,22 @@ def train_epoch_unet(current_epoch, model, optimizer, scheduler, batches, labels
     a dynamic loss scale, skipped steps) are not reproduced: the net's compute_dtype decides the precision, nothing is scaled."""
     if labels not in ops.XBD_UNET_LABELS:
         raise ValueError("train_epoch_unet: labels %r is not one of %s" % (labels, sorted(ops.XBD_UNET_LABELS)))
-    model.train()
-    run, rows, sizes = None, None, []
-    for batch in batches:
-        if run is None:
-            run = _unet_train_step(model, optimizer, batch, labels, graph)
-        loss, parts = run(batch)
-        rows, row = _next_rows(rows, len(sizes), 1, (9,), torch.float32, loss.device)
-        row[0, 0:1].copy_(loss.reshape(1), non_blocking=True)
-        row[0, 1:].copy_(parts, non_blocking=True)
-        sizes.append(int(batch['img'].shape[0]))
-    if rows is None:
-        raise ValueError("train_epoch_unet: no batches")
-    host = rows[:len(sizes)].cpu().numpy().astype(np.float64)          # the epoch's one read
-    bad = int(host[:, 8].sum())
-    if bad:
-        raise IndexError("train_epoch_unet: %d label bytes above 4 in epoch %s (steps %s); CrossEntropyLoss has 5 classes"
-                         % (bad, current_epoch, np.nonzero(host[:, 8])[0].tolist()))
-    w = np.asarray(sizes, dtype=np.float64)
-    avg = lambda col: float((host[:, col] * w).sum() / w.sum())        # AverageMeter: sum(val * n) / sum(n)
-    meters = {'loss': avg(0), 'loss2': avg(3), 'loss3': avg(4), 'dice': avg(7), 'ce': avg(6)}
-    scheduler.step()
-    lr = optimizer.param_groups[-1]['lr']
-    print("epoch: {}; lr {:.7f}; Loss {:.4f}; loss2 {:.4f}; Dice {:.4f}".format(current_epoch, lr, meters['loss'], meters['loss2'],
-                                                                              meters['dice']))
-    meters.update(lr=lr, steps=len(sizes), samples=int(w.sum()))
-    return meters
+
+    def no_bad_labels(host):
+        bad = int(host[:, 8].sum())
+        if bad:
+            raise IndexError("train_epoch_unet: %d label bytes above 4 in epoch %s (steps %s); CrossEntropyLoss has 5 classes"
+                             % (bad, current_epoch, np.nonzero(host[:, 8])[0].tolist()))
+    return _train_epoch("train_epoch_unet", current_epoch, model, optimizer, scheduler, batches,
+                        lambda first: _unet_train_step(model, optimizer, first, labels, graph), len(ops.XBD_UNET_PARTS),
+                        (('loss', 0), ('loss2', 3), ('loss3', 4), ('dice', 7), ('ce', 6)), ('loss', 'loss2', 'dice'), no_bad_labels)
 
 
 # ---- the adaptation script xBD_code/train_adapt.py: loss, step, epoch and validation of the FOUR-output net ---------------
-class _AdaptLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, msks, weights_dev, dice_w, focal_w, ce_w):
-        loss, parts, sums = ops.xbd_adapt_loss_fwd(logits, msks, weights_dev, dice_w, focal_w, ce_w)
-        ctx.save_for_backward(logits, msks, sums, weights_dev)
-        ctx.how = (dice_w, focal_w, ce_w)
-        ctx.mark_non_differentiable(parts)
-        return loss, parts
-
-    @staticmethod
-    def backward(ctx, dloss, _dparts):
-        logits, msks, sums, weights_dev = ctx.saved_tensors
-        up = dloss.detach().to(torch.float32).reshape(1).contiguous()
-        return (ops.xbd_adapt_loss_bwd(logits, msks, sums, weights_dev, up, *ctx.how),) + (None,) * 5
-
-
 def adapt_weights_dev(device, channel_weights=ADAPT_CHANNEL_WEIGHTS, ce_weights=ADAPT_CE_WEIGHTS):
     """the 4 channel weights and the 4 class weights as ONE cached device tensor [8], the form ops.xbd_adapt_loss_fwd takes (no
     host-to-device copy inside a HIP-graph capture).  ValueError unless both hold 4 numbers."""
-    key = (str(device), tuple(float(v) for v in channel_weights), tuple(float(v) for v in ce_weights))
-    if len(key[1]) != 4 or len(key[2]) != 4:
-        raise ValueError("adapt_loss: channel_weights %r and ce_weights %r must hold 4 numbers each" % (key[1], key[2]))
-    w = _weights.get(key)
-    if w is None:
-        w = _weights[key] = torch.tensor(key[1] + key[2], dtype=torch.float32, device=device)
-    return w
+    return _loss_weights_dev("adapt_loss", device, 4, channel_weights, ce_weights)
 
 
 def adapt_loss(out, msks, want_parts=False, channel_weights=ADAPT_CHANNEL_WEIGHTS, ce_weights=ADAPT_CE_WEIGHTS, dice=1.0,
@@ -693,8 +695,8 @@ def adapt_loss(out, msks, want_parts=False, channel_weights=ADAPT_CHANNEL_WEIGHT
     if not (torch.is_tensor(out) and out.is_cuda):
         raise _lib.HipLibraryError("dahitra_amd xBD loss runs on MI355X only (no CPU fallback)")
     w = adapt_weights_dev(out.device, channel_weights, ce_weights)
-    loss, parts = _AdaptLoss.apply(out.float().contiguous(), msks.contiguous() if torch.is_tensor(msks) else msks, w,
-                                   float(dice), float(focal), float(ce))
+    loss, parts = _ScriptLoss.apply("adapt", out.float().contiguous(), msks.contiguous() if torch.is_tensor(msks) else msks, None,
+                                    None, w, float(dice), float(focal), float(ce))
     return (loss, parts) if want_parts else loss
 
 
@@ -719,26 +721,9 @@ def adapt_eager_step(model, optimizer, imgs, msks, max_norm=ADAPT_MAX_NORM, upda
 
 
 def _adapt_train_step(model, optimizer, first, graph):
-    """_unet_train_step for the adaptation step: run(batch) -> (loss, parts); batches of the first batch's shape replay the model's
-    recorded GraphedXbdAdaptStep (kept on the model per shape, optimizer and device), any other shape and graph=False run eagerly"""
-    _device_u8("training", first['img'], first['msk'])
-
-    def eager(batch):
-        return adapt_eager_step(model, optimizer, batch['img'], batch['msk'])[1:]
-    if not graph:
-        return eager
-    from ..graph import GraphedXbdAdaptStep
-    imgs = first['img']
-    model._ensure_arena(imgs.device)
-    step = _kept_step(model, '_xbd_adapt_steps', (tuple(imgs.shape), id(optimizer), str(imgs.device)),
-                      lambda: GraphedXbdAdaptStep(model, optimizer, imgs, first['msk']),
-                      lambda step: step._generation == model._arena.generation and step.opt is optimizer)
-
-    def replay(batch):
-        if tuple(batch['img'].shape) != tuple(imgs.shape):
-            return eager(batch)
-        return step(batch['img'], batch['msk']), step.parts
-    return replay
+    """_script_train_step of GraphedXbdAdaptStep, kept per shape, optimizer and device"""
+    return _script_train_step('GraphedXbdAdaptStep', adapt_eager_step, '_xbd_adapt_steps', ('img', 'msk'), (), model, optimizer,
+                              first, graph)
 
 
 def train_epoch_adapt(current_epoch, model, optimizer, scheduler, batches, graph=True):
@@ -756,28 +741,9 @@ def train_epoch_adapt(current_epoch, model, optimizer, scheduler, batches, graph
     never uses.  As in train_epoch_unet the scheduler moves by scheduler.step(), without the script's deprecated epoch argument
     (with `step(current_epoch)` a milestone takes effect one epoch later), and the printed lr is
     optimizer.param_groups[-1]['lr'], the rate the next epoch runs at."""
-    model.train()
-    run, rows, sizes = None, None, []
-    for batch in batches:
-        if run is None:
-            run = _adapt_train_step(model, optimizer, batch, graph)
-        loss, parts = run(batch)
-        rows, row = _next_rows(rows, len(sizes), 1, (7,), torch.float32, loss.device)
-        row[0, 0:1].copy_(loss.reshape(1), non_blocking=True)
-        row[0, 1:].copy_(parts, non_blocking=True)
-        sizes.append(int(batch['img'].shape[0]))
-    if rows is None:
-        raise ValueError("train_epoch_adapt: no batches")
-    host = rows[:len(sizes)].cpu().numpy().astype(np.float64)          # the epoch's one read
-    w = np.asarray(sizes, dtype=np.float64)
-    avg = lambda col: float((host[:, col] * w).sum() / w.sum())        # AverageMeter: sum(val * n) / sum(n)
-    meters = {'loss': avg(0), 'loss0': avg(1), 'loss1': avg(2), 'loss2': avg(3), 'loss3': avg(4), 'ce': avg(5)}
-    scheduler.step()
-    lr = optimizer.param_groups[-1]['lr']
-    print("epoch: {}; lr {:.7f}; Loss {:.4f}; loss2 {:.4f}; Dice {:.4f}".format(current_epoch, lr, meters['loss'], meters['loss1'],
-                                                                              meters['loss3']))
-    meters.update(lr=lr, steps=len(sizes), samples=int(w.sum()))
-    return meters
+    return _train_epoch("train_epoch_adapt", current_epoch, model, optimizer, scheduler, batches,
+                        lambda first: _adapt_train_step(model, optimizer, first, graph), len(ops.XBD_ADAPT_PARTS),
+                        (('loss', 0), ('loss0', 1), ('loss1', 2), ('loss2', 3), ('loss3', 4), ('ce', 5)), ('loss', 'loss1', 'loss3'))
 
 
 def validate_adapt(model, batches, thr=0.3, select='reference', graph=True, want_counts=False):

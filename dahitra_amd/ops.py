@@ -1887,33 +1887,72 @@ def adamw_xbd_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weig
           step, P(grad_scale_dev), S())
 
 
-# ---- loss of xBD_code/train_unettransformer.py's step (csrc/xbd_unet_loss.hip) ---------------------------
+# ---- losses of the two xBD training scripts (csrc/xbd_script_loss.hip) -------------------------------------------
 XBD_UNET_LABELS = {"lbl_msk": 0, "damage": 1}
 # lanes of one forward grid pass (dh_xbd_unet_loss_grid_pass): that many pixels where H * W is no multiple of 4 (one pixel per
 # lane), four times as many where it is; a batch beyond it is strided over
 XBD_UNET_LOSS_PASS = 1024 * 256
 XBD_UNET_PARTS = ("loss0", "loss1", "loss2", "loss3", "loss4", "ce", "dice", "bad_labels")
+# lanes of one forward grid pass (dh_xbd_adapt_loss_grid_pass), as XBD_UNET_LOSS_PASS
+XBD_ADAPT_LOSS_PASS = 1024 * 256
+XBD_ADAPT_PARTS = ("loss0", "loss1", "loss2", "loss3", "ce", "zero")
+
+# form -> channels, sums handed to the backward, parts, the entries' and refusals' prefix, whether the entries take lbl
+_XBD_LOSS_FORMS = {"unet": (5, 24, len(XBD_UNET_PARTS), "xbd_unet_loss", True),
+                   "adapt": (4, 18, len(XBD_ADAPT_PARTS), "xbd_adapt_loss", False)}
 
 
-def _xbd_unet_loss_args(what, logits, msk, lbl, labels, weights_dev, extra=()):
-    """the tensors of xbd_unet_loss_fwd / _bwd, refused before any launch: ValueError for a label mode, dtype or shape that does not
-    fit and for mixed devices, HipLibraryError when everything is on the CPU.  Returns label_mode, B, H, W"""
-    if labels not in XBD_UNET_LABELS:
-        raise ValueError("%s: labels %r is not one of %s" % (what, labels, sorted(XBD_UNET_LABELS)))
-    if labels == "lbl_msk" and lbl is None:
-        raise ValueError("%s: labels='lbl_msk' reads lbl, which is None" % what)
+def _xbd_loss_args(form, tail, logits, msk, lbl, labels, weights_dev, extra=()):
+    """the tensors of a form's loss _fwd / _bwd, refused before any launch: ValueError for a label mode, dtype or shape that does
+    not fit and for mixed devices, HipLibraryError when everything is on the CPU.  Returns the label arguments of the C entry
+    (lbl and label_mode, or none where the form has no lbl), B, H, W"""
+    C, _, _, prefix, has_lbl = _XBD_LOSS_FORMS[form]
+    what = prefix + tail
+    if has_lbl:
+        if labels not in XBD_UNET_LABELS:
+            raise ValueError("%s: labels %r is not one of %s" % (what, labels, sorted(XBD_UNET_LABELS)))
+        if labels == "lbl_msk" and lbl is None:
+            raise ValueError("%s: labels='lbl_msk' reads lbl, which is None" % what)
     a = _Args(what, cpu_error=True)
-    B, _, H, W = a.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 5 and t.numel() > 0,
-                          "[B, 5, H, W], not empty").shape
-    a.tensor("msk", msk, torch.uint8, (B, 5, H, W), "[%d, 5, %d, %d] like logits" % (B, H, W))
+    B, _, H, W = a.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == C and t.numel() > 0,
+                          "[B, %d, H, W], not empty" % C).shape
+    a.tensor("msk", msk, torch.uint8, (B, C, H, W), "[%d, %d, %d, %d] like logits" % (B, C, H, W))
     if lbl is not None:
         a.tensor("lbl", lbl, torch.uint8, (B, H, W), "[%d, %d, %d] like logits" % (B, H, W))
-    a.tensor("weights_dev", weights_dev, torch.float32, (10,), "[10]: 5 channel weights, 5 class weights")
+    a.tensor("weights_dev", weights_dev, torch.float32, (2 * C,), "[%d]: %d channel weights, %d class weights" % (2 * C, C, C))
     for name, t, shape in extra:
         if t is not None:
             a.tensor(name, t, torch.float32, lambda t, n=math.prod(shape): t.numel() == n, str(list(shape)))
     a.placed()
-    return XBD_UNET_LABELS[labels], B, H, W
+    if not has_lbl:
+        return (), B, H, W
+    mode = XBD_UNET_LABELS[labels]
+    return (P(lbl if mode == 0 else None), mode), B, H, W
+
+
+def _xbd_loss_fwd(form, logits, msk, lbl, labels, weights_dev, dice_weight, focal_weight, ce_weight):
+    _, n_sums, n_parts, prefix, _ = _XBD_LOSS_FORMS[form]
+    label_args, B, H, W = _xbd_loss_args(form, "_fwd", logits, msk, lbl, labels, weights_dev)
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty(n_parts, dtype=torch.float32, device=dev)
+    sums = torch.empty(n_sums, dtype=torch.float32, device=dev)
+    ws = workspace(_ws_bytes("dh_%s_workspace_size" % prefix), dev)
+    _call("dh_%s_fwd" % prefix, P(logits), P(msk), *label_args, B, H * W, P(weights_dev), float(dice_weight), float(focal_weight),
+          float(ce_weight), P(sums), P(parts), P(loss), P(ws), ws.numel(), S())
+    return loss, parts, sums
+
+
+def _xbd_loss_bwd(form, logits, msk, lbl, labels, sums, weights_dev, upstream, dice_weight, focal_weight, ce_weight):
+    _, n_sums, _, prefix, _ = _XBD_LOSS_FORMS[form]
+    if sums is None:
+        raise ValueError("%s_bwd: sums is None; it is %s_fwd's third result" % (prefix, prefix))
+    label_args, B, H, W = _xbd_loss_args(form, "_bwd", logits, msk, lbl, labels, weights_dev,
+                                         (("sums", sums, (n_sums,)), ("upstream", upstream, (1,))))
+    dl = torch.empty_like(logits)
+    _call("dh_%s_bwd" % prefix, P(logits), P(msk), *label_args, P(sums), P(weights_dev), P(upstream), float(dice_weight),
+          float(focal_weight), float(ce_weight), B, H * W, P(dl), S())
+    return dl
 
 
 def xbd_unet_loss_fwd(logits, msk, lbl, labels, weights_dev, dice_weight=1.0, focal_weight=8.0, ce_weight=8.0):
@@ -1923,50 +1962,13 @@ def xbd_unet_loss_fwd(logits, msk, lbl, labels, weights_dev, dice_weight=1.0, fo
     'damage': y = the first set channel among 1 .. 4 of msk (lbl is not read and may be None); weights_dev fp32 [10] = the 5
     channel weights, then the 5 class weights.  Returns (loss [], parts [8] = XBD_UNET_PARTS, sums [24] for xbd_unet_loss_bwd),
     all on the device; nothing is read by the host."""
-    mode, B, H, W = _xbd_unet_loss_args("xbd_unet_loss_fwd", logits, msk, lbl, labels, weights_dev)
-    dev = logits.device
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    parts = torch.empty(8, dtype=torch.float32, device=dev)
-    sums = torch.empty(24, dtype=torch.float32, device=dev)
-    need = _ws_bytes("dh_xbd_unet_loss_workspace_size")
-    ws = workspace(need, dev)
-    _call("dh_xbd_unet_loss_fwd", P(logits), P(msk), P(lbl if mode == 0 else None), mode, B, H * W, P(weights_dev),
-          float(dice_weight), float(focal_weight), float(ce_weight), P(sums), P(parts), P(loss), P(ws), ws.numel(), S())
-    return loss, parts, sums
+    return _xbd_loss_fwd("unet", logits, msk, lbl, labels, weights_dev, dice_weight, focal_weight, ce_weight)
 
 
 def xbd_unet_loss_bwd(logits, msk, lbl, labels, sums, weights_dev, upstream=None, dice_weight=1.0, focal_weight=8.0, ce_weight=8.0):
     """dloss / dlogits of xbd_unet_loss_fwd, one pass (dh_xbd_unet_loss_bwd): fp32 [B, 5, H, W].  sums: the forward's third result;
     upstream: a device scalar fp32 [1] that multiplies the gradient, or None for 1."""
-    if sums is None:
-        raise ValueError("xbd_unet_loss_bwd: sums is None; it is xbd_unet_loss_fwd's third result")
-    mode, B, H, W = _xbd_unet_loss_args("xbd_unet_loss_bwd", logits, msk, lbl, labels, weights_dev,
-                                        (("sums", sums, (24,)), ("upstream", upstream, (1,))))
-    dl = torch.empty_like(logits)
-    _call("dh_xbd_unet_loss_bwd", P(logits), P(msk), P(lbl if mode == 0 else None), mode, P(sums), P(weights_dev), P(upstream),
-          float(dice_weight), float(focal_weight), float(ce_weight), B, H * W, P(dl), S())
-    return dl
-
-
-# ---- loss of xBD_code/train_adapt.py's step (csrc/xbd_adapt_loss.hip) ----------------------------------------
-# lanes of one forward grid pass (dh_xbd_adapt_loss_grid_pass), as XBD_UNET_LOSS_PASS
-XBD_ADAPT_LOSS_PASS = 1024 * 256
-XBD_ADAPT_PARTS = ("loss0", "loss1", "loss2", "loss3", "ce", "zero")
-
-
-def _xbd_adapt_loss_args(what, logits, msk, weights_dev, extra=()):
-    """the tensors of xbd_adapt_loss_fwd / _bwd, refused before any launch: ValueError for a dtype or shape that does not fit and
-    for mixed devices, HipLibraryError when everything is on the CPU.  Returns B, H, W"""
-    a = _Args(what, cpu_error=True)
-    B, _, H, W = a.tensor("logits", logits, torch.float32, lambda t: t.dim() == 4 and t.shape[1] == 4 and t.numel() > 0,
-                          "[B, 4, H, W], not empty").shape
-    a.tensor("msk", msk, torch.uint8, (B, 4, H, W), "[%d, 4, %d, %d] like logits" % (B, H, W))
-    a.tensor("weights_dev", weights_dev, torch.float32, (8,), "[8]: 4 channel weights, 4 class weights")
-    for name, t, shape in extra:
-        if t is not None:
-            a.tensor(name, t, torch.float32, lambda t, n=math.prod(shape): t.numel() == n, str(list(shape)))
-    a.placed()
-    return B, H, W
+    return _xbd_loss_bwd("unet", logits, msk, lbl, labels, sums, weights_dev, upstream, dice_weight, focal_weight, ce_weight)
 
 
 def xbd_adapt_loss_fwd(logits, msk, weights_dev, dice_weight=1.0, focal_weight=8.0, ce_weight=5.0):
@@ -1975,28 +1977,13 @@ def xbd_adapt_loss_fwd(logits, msk, weights_dev, dice_weight=1.0, focal_weight=8
     of (1 - m0, m1, m2, m3), derived from the mask bytes in the kernel.  logits fp32 [B, 4, H, W]; msk uint8 [B, 4, H, W], the
     loader's bytes; weights_dev fp32 [8] = the 4 channel weights, then the 4 class weights.  Returns (loss [], parts [6] =
     XBD_ADAPT_PARTS, sums [18] for xbd_adapt_loss_bwd), all on the device; nothing is read by the host."""
-    B, H, W = _xbd_adapt_loss_args("xbd_adapt_loss_fwd", logits, msk, weights_dev)
-    dev = logits.device
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    parts = torch.empty(6, dtype=torch.float32, device=dev)
-    sums = torch.empty(18, dtype=torch.float32, device=dev)
-    ws = workspace(_ws_bytes("dh_xbd_adapt_loss_workspace_size"), dev)
-    _call("dh_xbd_adapt_loss_fwd", P(logits), P(msk), B, H * W, P(weights_dev), float(dice_weight), float(focal_weight),
-          float(ce_weight), P(sums), P(parts), P(loss), P(ws), ws.numel(), S())
-    return loss, parts, sums
+    return _xbd_loss_fwd("adapt", logits, msk, None, None, weights_dev, dice_weight, focal_weight, ce_weight)
 
 
 def xbd_adapt_loss_bwd(logits, msk, sums, weights_dev, upstream=None, dice_weight=1.0, focal_weight=8.0, ce_weight=5.0):
     """dloss / dlogits of xbd_adapt_loss_fwd, one pass (dh_xbd_adapt_loss_bwd): fp32 [B, 4, H, W].  sums: the forward's third
     result; upstream: a device scalar fp32 [1] that multiplies the gradient, or None for 1."""
-    if sums is None:
-        raise ValueError("xbd_adapt_loss_bwd: sums is None; it is xbd_adapt_loss_fwd's third result")
-    B, H, W = _xbd_adapt_loss_args("xbd_adapt_loss_bwd", logits, msk, weights_dev,
-                                   (("sums", sums, (18,)), ("upstream", upstream, (1,))))
-    dl = torch.empty_like(logits)
-    _call("dh_xbd_adapt_loss_bwd", P(logits), P(msk), P(sums), P(weights_dev), P(upstream), float(dice_weight),
-          float(focal_weight), float(ce_weight), B, H * W, P(dl), S())
-    return dl
+    return _xbd_loss_bwd("adapt", logits, msk, None, None, sums, weights_dev, upstream, dice_weight, focal_weight, ce_weight)
 
 
 # ---- loader of xBD_code/train_adapt.py (csrc/xbd_adapt.hip) ------------------------------------------------------

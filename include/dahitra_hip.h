@@ -787,7 +787,7 @@ int dh_adamw_xbd_step(float* param, const float* grad, float* exp_avg, float* ex
 int dh_adamw_xbd_step_graph(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float* hyper_dev,
                             int* step_dev, const float* grad_scale_dev, void* stream);
 
-/* ---- loss of xBD_code/train_unettransformer.py's step (lines 438-461; csrc/xbd_unet_loss.hip) -------------------
+/* ---- loss of xBD_code/train_unettransformer.py's step (lines 438-461; csrc/xbd_script_loss.hip) -----------------
  * loss = sum_c cw_c * ComboLoss{dice, focal}(logits[:, c], msk[:, c]) + ce_weight * CrossEntropyLoss(weight=w)(z, y) with
  * z = logits * (y > 0), in ONE pass over the pixels plus a finalize launch.  logits fp32 [B][5][HW]; msk uint8 [B][5][HW]
  * (bytes 0 / 1, the loader's); label_mode 0: y = lbl [B][HW] uint8; label_mode 1 ("damage"): y = the first set channel among
@@ -811,7 +811,7 @@ int dh_xbd_unet_loss_bwd(const float* logits, const unsigned char* msk, const un
                          const float* sums, const float* weights_dev, const float* upstream_dev, float dice_weight,
                          float focal_weight, float ce_weight, int B, long HW, float* dlogits, void* stream);
 
-/* ---- loss of xBD_code/train_adapt.py's step (lines 332-342; csrc/xbd_adapt_loss.hip) ---------------------------------
+/* ---- loss of xBD_code/train_adapt.py's step (lines 332-342; csrc/xbd_script_loss.hip) --------------------------------
  * The four-output sibling of dh_xbd_unet_loss_*: loss = sum_c cw_c * ComboLoss{dice, focal}(logits[:, c], msk[:, c]) + ce_weight *
  * CrossEntropyLoss(weight=w)(logits, y), in ONE pass over the pixels plus a finalize launch.  logits fp32 [B][4][HW]; msk uint8
  * [B][4][HW] (bytes 0 / 1, the loader's), read in place.  y is derived from the mask bytes in the kernel: the FIRST maximum of

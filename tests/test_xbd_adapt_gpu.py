@@ -1,4 +1,4 @@
-"""xBD_code/train_adapt.py on the GPU: the kernels of csrc/xbd_adapt_loss.hip against the float64 restatement of
+"""xBD_code/train_adapt.py on the GPU: the kernels of csrc/xbd_script_loss.hip against the float64 restatement of
 tests/_xbd_adapt_cases.py and against the reference's own results (tests/golden/xbd_adapt_loss.npz), the loader's bytes
 (csrc/xbd_adapt.hip) and the three-class validation counts (dh_xbd_val_count_n) against the script's numpy, the four-class net
 against the five-class oracle by the slicing identity, and GraphedXbdAdaptStep / train_epoch_adapt against the eager step.
@@ -24,12 +24,12 @@ import pytest
 import torch
 
 import _xbd_adapt_cases as C
+import _xbd_script_loss_checks as K
 import _xbd_val_cases as V
 import cdnet_ref as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ULP = 2.0 ** -23
 GRAD_TOL = 6e-2        # tests/test_xbd_gpu.py: the fp32 gradient noise floor of these nets
 LOGIT_TOL = 2e-4       # ... its logit_tol; 5e-4 at 1024 x 1024
 LOGIT_TOL_1024 = 5e-4
@@ -45,8 +45,7 @@ def golden(golden_dir):
 
 @pytest.fixture(scope="module")
 def bounds(golden):
-    y = C.yardstick(golden)
-    return {"loss": 2 * y["loss"], "grad": 2 * y["grad"], "channel": 2 * max(y["channel"], ULP), "ce": 2 * max(y["ce"], ULP)}
+    return K.bounds(C.yardstick(golden))
 
 
 def offset_view(t, dtype):
@@ -70,19 +69,9 @@ def kernel(logits, msk, upstream=1.0, unaligned=False):
     return float(loss.detach()), parts.cpu().numpy().astype(np.float64), lg.grad.cpu().numpy()
 
 
-def distances(got, ref):
-    loss, parts, grad = got
-    rel = lambda a, b: float(np.max(np.abs(np.asarray(a, dtype=np.float64) - b) / np.abs(b)))
-    return {"loss": rel(loss, ref["loss"]), "channel": rel(parts[:4], ref["parts"][:4]), "ce": rel(parts[4], ref["parts"][4]),
-            "grad": float(np.abs(grad.astype(np.float64) - ref["grad"]).max() / np.abs(ref["grad"]).max())}
-
-
 def check(what, got, ref, bounds):
-    d = distances(got, ref)
-    print("%s: %s" % (what, ", ".join("%s %.3e (bound %.3e)" % (k, v, bounds[k]) for k, v in d.items())))
-    assert got[1][5] == 0, what
-    for k, v in d.items():
-        assert v <= bounds[k], (what, k, v, bounds[k])
+    """four channel losses, cross-entropy and gradient under their bounds; the last of the six parts is 0"""
+    K.check(what, got, ref, bounds, 4, False, 0)
 
 
 def shapes():

@@ -1,4 +1,4 @@
-"""The step of xBD_code/train_unettransformer.py on the GPU: the kernels of csrc/xbd_unet_loss.hip against the float64 restatement of
+"""The step of xBD_code/train_unettransformer.py on the GPU: the kernels of csrc/xbd_script_loss.hip against the float64 restatement of
 tests/_xbd_unet_loss_cases.py and against the reference's own results (tests/golden/xbd_unet_loss.npz), the script as executed
 against the existing combo kernels, and GraphedXbdUnetStep / train_epoch_unet against the eager step.
 
@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 import torch
 
+import _xbd_script_loss_checks as K
 import _xbd_unet_loss_cases as C
 import cdnet_ref as O
 
@@ -43,9 +44,7 @@ def golden(golden_dir):
 
 @pytest.fixture(scope="module")
 def bounds(golden):
-    y = C.yardstick(golden)
-    return {"loss": 2 * y["loss"], "grad": 2 * y["grad"], "channel": 2 * max(y["channel"], ULP), "ce": 2 * max(y["ce"], ULP),
-            "dice": 2 * max(y["dice"], ULP)}
+    return K.bounds(C.yardstick(golden))
 
 
 def kernel(logits, msk, lbl, labels, upstream=1.0):
@@ -58,20 +57,9 @@ def kernel(logits, msk, lbl, labels, upstream=1.0):
     return float(loss), parts.cpu().numpy().astype(np.float64), lg.grad.cpu().numpy()
 
 
-def distances(got, ref):
-    loss, parts, grad = got
-    rel = lambda a, b: float(np.max(np.abs(np.asarray(a, dtype=np.float64) - b) / np.abs(b)))
-    return {"loss": rel(loss, ref["loss"]), "channel": rel(parts[:5], ref["parts"][:5]), "ce": rel(parts[5], ref["parts"][5]),
-            "dice": rel(parts[6], ref["parts"][6]),
-            "grad": float(np.abs(grad.astype(np.float64) - ref["grad"]).max() / np.abs(ref["grad"]).max())}
-
-
 def check(what, got, ref, bounds):
-    d = distances(got, ref)
-    print("%s: %s" % (what, ", ".join("%s %.3e (bound %.3e)" % (k, v, bounds[k]) for k, v in d.items())))
-    assert got[1][7] == ref["parts"][7], what
-    for k, v in d.items():
-        assert v <= bounds[k], (what, k, v, bounds[k])
+    """five channel losses, cross-entropy, Dice meter and gradient under their bounds; the count of bad labels exactly"""
+    K.check(what, got, ref, bounds, 5, True, ref["parts"][7])
 
 
 def shapes():
