@@ -150,14 +150,22 @@ def channel_weights_dev(device, channel_weights=CHANNEL_WEIGHTS):
     return w
 
 
-def xbd_loss(out, msks, channel_weights=CHANNEL_WEIGHTS, dice=1.0, focal=8.0, want_channels=False):
-    """train.py:348-353 in one pass: sum_c w_c * ComboLoss{dice:1, focal:8}(out[:, c], msks[:, c])"""
+def xbd_loss(out, msks, channel_weights=CHANNEL_WEIGHTS, dice=1.0, focal=8.0, want_channels=False, lovasz=0.0):
+    """train.py:348-353 in one pass: sum_c w_c * ComboLoss{dice:1, focal:8}(out[:, c], msks[:, c]).
+    lovasz: the weight of ComboLoss's 'lovasz' term in every channel's loss: a non-zero value adds
+    lovasz * sum_c w_c * lovasz_hinge(out[:, c], msks[:, c], per_image=False) (xbd_losses, dh_xbd_lovasz_fwd; nothing is
+    ignored); the channel losses of want_channels stay those of dice and focal.  0 launches what it always launched."""
     _check(out, msks)
     key = (str(out.device), tuple(float(v) for v in channel_weights))
     w = _weights.get(key)
     if w is None:                    # cached: no host-to-device copy inside a HIP-graph capture
         w = _weights[key] = torch.tensor(key[1], dtype=torch.float32, device=out.device)
-    loss, channel = _Combo.apply(out.float().contiguous(), msks.float().contiguous(), w, float(dice), float(focal))
+    logits = out.float().contiguous()
+    loss, channel = _Combo.apply(logits, msks.float().contiguous(), w, float(dice), float(focal))
+    if lovasz:
+        from .xbd_losses import _Lovasz
+        hinge, _ = _Lovasz.apply(logits, (msks if msks.dtype == torch.uint8 else msks.float()).contiguous(), "hinge", False, None, w)
+        loss = loss + float(lovasz) * hinge
     return (loss, channel) if want_channels else loss
 
 

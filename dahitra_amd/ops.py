@@ -1986,6 +1986,112 @@ def xbd_adapt_loss_bwd(logits, msk, sums, weights_dev, upstream=None, dice_weigh
     return _xbd_loss_bwd("adapt", logits, msk, None, None, sums, weights_dev, upstream, dice_weight, focal_weight, ce_weight)
 
 
+# ---- xBD losses: the Lovasz, Jaccard and BCE terms of ComboLoss (csrc/xbd_seg_losses.hip) ------------------------------
+XBD_LOVASZ_MODES = {"hinge": 0, "probas": 1, "sigmoid": 2}
+XBD_LOVASZ_TILE = 2048             # elements a workgroup takes per pass: dh_xbd_lovasz_tile
+XBD_LOVASZ_MAX_SEGMENTS = 256
+XBD_SEG_TERMS = ("jaccard", "bce", "mask_bceavg", "dice", "focal")
+_TARGET_KINDS = {torch.float32: 0, torch.uint8: 1}
+
+
+def _seg_loss_args(what, x, target, channel_weights_dev, extra=()):
+    """x fp32 [B, C, ...] and a target of its shape, fp32 or uint8; the optional fp32 tensors of `extra` = (name, tensor, numel).
+    ValueError for what does not fit, HipLibraryError when everything is on the CPU.  Returns (a, B, C, HW, target_kind)"""
+    a = _Args(what, cpu_error=True)
+    a.tensor("x", x, torch.float32, lambda t: t.dim() >= 3 and t.numel() > 0, "[B, C, ...], not empty")
+    B, C = x.shape[:2]
+    if not torch.is_tensor(target) or target.dtype not in _TARGET_KINDS:
+        raise ValueError("%s: target %s is neither a float32 nor a uint8 tensor" % (what, getattr(target, "dtype", type(target))))
+    a.tensor("target", target, target.dtype, tuple(x.shape), "%s like x" % list(x.shape))
+    if channel_weights_dev is not None:
+        a.tensor("channel_weights_dev", channel_weights_dev, torch.float32, (C,), "[%d]: a weight per channel" % C)
+    for name, t, numel in extra:
+        if t is not None:
+            a.tensor(name, t, torch.float32, lambda t, n=numel: t.numel() == n, "%d numbers" % numel)
+    a.placed()
+    return a, B, C, x.numel() // (B * C), _TARGET_KINDS[target.dtype]
+
+
+def _lovasz_call(what, x, target, mode, per_image, ignore, channel_weights_dev):
+    if mode not in XBD_LOVASZ_MODES and mode not in XBD_LOVASZ_MODES.values():
+        raise ValueError("%s: mode %r is not one of %s" % (what, mode, sorted(XBD_LOVASZ_MODES)))
+    ignore = -1 if ignore is None else int(ignore)
+    if not -1 <= ignore <= 255:
+        raise ValueError("%s: ignore=%r is neither None nor a byte" % (what, ignore))
+    a, B, C, HW, kind = _seg_loss_args(what, x, target, channel_weights_dev)
+    segments = B * C if per_image else C
+    if segments > XBD_LOVASZ_MAX_SEGMENTS or x.numel() > 1 << 30:
+        raise ValueError("%s: %d segments of %d elements; at most %d segments and 2^30 elements are sorted"
+                         % (what, segments, x.numel() // segments, XBD_LOVASZ_MAX_SEGMENTS))
+    ws = workspace(_ws_bytes("dh_xbd_lovasz_workspace_size", x.numel(), segments), x.device)
+    return (P(x), P(target), kind, B, C, HW, XBD_LOVASZ_MODES.get(mode, mode), int(bool(per_image)), ignore), ws
+
+
+def xbd_lovasz(x, target, mode, per_image=False, ignore=255, channel_weights_dev=None, bad_out=None):
+    """lovasz_hinge / lovasz_sigmoid of xBD_code/losses.py:129-225 for every channel, with the gradient (dh_xbd_lovasz_fwd).
+    x fp32 [B, C, H, W] (or [B, C, n]); target of its shape, fp32 or uint8 (the same bits either way).  mode 'hinge' (0): x are
+    logits; 'probas' (1): x are probabilities; 'sigmoid' (2): x are logits and the sigmoid is taken in the kernel.  per_image: a
+    channel's loss is the mean over its images (an image without a valid element counts 0) instead of one sort over the batch.
+    ignore: the target value that is dropped, or None.  Equal errors keep flat index order, so the gradient is defined.
+    Returns (loss [] = sum_c w_c channel_loss_c, channel_losses [C], dx like x = d loss / d x); w = channel_weights_dev or 1.
+    bad_out: an int32 [1] device tensor that receives the number of targets that are neither 0, 1 nor `ignore` (they are dropped).
+    No host read.  The only allocations are the three results and, when the current stream's ops.workspace is smaller than the
+    call needs, that workspace: a capture whose stream holds a workspace grown by a warm-up (ops.rekey_workspace, as
+    GraphedXbdStep does) records the call with nothing but its results in the graph's pool."""
+    args, ws = _lovasz_call("xbd_lovasz", x, target, mode, per_image, ignore, channel_weights_dev)
+    if bad_out is not None and not (torch.is_tensor(bad_out) and bad_out.dtype == torch.int32 and bad_out.numel() == 1
+                                    and bad_out.device == x.device):
+        raise ValueError("xbd_lovasz: bad_out is not an int32 [1] tensor beside x")
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    channel = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x)
+    _call("dh_xbd_lovasz_fwd", *args, P(channel_weights_dev), P(loss), P(channel), P(dx), P(bad_out), P(ws), ws.numel(), S())
+    return loss, channel, dx
+
+
+def xbd_lovasz_order(x, target, mode, per_image=False, ignore=255):
+    """The order xbd_lovasz sums in (dh_xbd_lovasz_order): int32 [n] flat indices into x, segment after segment (a segment is a
+    channel over the batch, c, or with per_image a plane, b * C + c), descending error inside a segment, equal errors in index
+    order, dropped elements last."""
+    args, ws = _lovasz_call("xbd_lovasz_order", x, target, mode, per_image, ignore, None)
+    order = torch.empty(x.numel(), dtype=torch.int32, device=x.device)
+    _call("dh_xbd_lovasz_order", *args, P(order), P(ws), ws.numel(), S())
+    return order
+
+
+def xbd_seg_terms_fwd(x, target, channel_weights_dev=None, jaccard=0.0, bce=0.0, mask_bceavg=0.0, dice=0.0, focal=0.0, probs=False):
+    """The jaccard, bce and mask_bceavg terms of ComboLoss (xBD_code/losses.py:36-45, 70-92) per channel over the batch, in one
+    pass and a finalize launch (dh_xbd_seg_terms_fwd).  x fp32 [B, C, H, W]: logits, the sigmoid taken in the kernel, or with
+    probs=True probabilities (what the reference's stand-alone classes take; bce reads x as logits either way); target of its
+    shape, fp32 or uint8.  dice and focal are the same kernel's forms of soft_dice_loss and FocalLoss2d for those classes.
+    Returns (loss [] = sum_c w_c sum_k weight_k term_kc, terms [C, 5] = XBD_SEG_TERMS, sums [C, 4] for xbd_seg_terms_bwd), on
+    the device."""
+    _, B, C, HW, kind = _seg_loss_args("xbd_seg_terms_fwd", x, target, channel_weights_dev)
+    dev = x.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    terms = torch.empty(C, len(XBD_SEG_TERMS), dtype=torch.float32, device=dev)
+    sums = torch.empty(C, 4, dtype=torch.float32, device=dev)
+    ws = workspace(_ws_bytes("dh_xbd_seg_terms_workspace_size", C), dev)
+    _call("dh_xbd_seg_terms_fwd", P(x), P(target), kind, int(bool(probs)), B, C, HW, P(channel_weights_dev), float(jaccard),
+          float(bce), float(mask_bceavg), float(dice), float(focal), P(sums), P(terms), P(loss), P(ws), ws.numel(), S())
+    return loss, terms, sums
+
+
+def xbd_seg_terms_bwd(x, target, sums, channel_weights_dev=None, upstream=None, jaccard=0.0, bce=0.0, mask_bceavg=0.0, dice=0.0,
+                      focal=0.0, probs=False):
+    """d loss / d x of xbd_seg_terms_fwd in one pass (dh_xbd_seg_terms_bwd): fp32 like x.  sums: the forward's third result;
+    upstream: a device scalar fp32 [1] that multiplies the gradient, or None for 1.  A zero weight costs nothing."""
+    if sums is None:
+        raise ValueError("xbd_seg_terms_bwd: sums is None; it is xbd_seg_terms_fwd's third result")
+    _, B, C, HW, kind = _seg_loss_args("xbd_seg_terms_bwd", x, target, channel_weights_dev,
+                                       (("sums", sums, 4 * x.shape[1] if torch.is_tensor(x) and x.dim() > 1 else 0),
+                                        ("upstream", upstream, 1)))
+    dx = torch.empty_like(x)
+    _call("dh_xbd_seg_terms_bwd", P(x), P(target), kind, int(bool(probs)), P(sums), P(channel_weights_dev), P(upstream),
+          float(jaccard), float(bce), float(mask_bceavg), float(dice), float(focal), B, C, HW, P(dx), S())
+    return dx
+
+
 # ---- loader of xBD_code/train_adapt.py (csrc/xbd_adapt.hip) ------------------------------------------------------
 def xbd_adapt_batch(pre_u8, post_u8, pre_mask_u8, post_label_u8, idx, origins, crop, train=True):
     """One batch of the adaptation script's TrainData / ValData in ONE launch (dh_xbd_adapt_batch_u8).  pre_u8, post_u8

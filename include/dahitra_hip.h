@@ -1096,6 +1096,59 @@ int dh_cd_tile_stitch(const float* logits, int P, int C, int h, int w, const int
 int dh_cd_view_counts(const float* logits, const unsigned char* labels, int P, int C, int h, int w, long long* counts,
                       void* stream);
 
+/* ---- xBD losses: the Lovasz, Jaccard and BCE terms of xBD_code/losses.py's ComboLoss (csrc/xbd_seg_losses.hip) --------------
+ * x fp32 [B][C][HW]; target of the same shape, fp32 (target_kind 0) or uint8 (target_kind 1); n = B * C * HW.
+ * dh_xbd_lovasz_fwd: lovasz_hinge / lovasz_sigmoid (losses.py:129-225) of every channel, and its gradient, in one call.
+ *   mode 0: hinge on logits, e = fl32(1 - x (2 t - 1)), weight max(e, 0); mode 1: e = |t - x| on probabilities x; mode 2: the same
+ *   on p = 1 / (1 + expf(-x)), the gradient taken through p (1 - p).
+ *   per_image 0: one segment per channel over the whole batch (segment c); per_image 1: one per plane (segment b * C + c), a
+ *   channel's loss the mean over its B images, an image without a valid element counting 0.
+ *   ignore: -1, or the target value (0 .. 255) whose elements are dropped: no key, no count, zero gradient.  Any other target
+ *   that is neither 0 nor 1 is dropped too and counted in bad_out [1] (int32, may be NULL).
+ *   Within a segment the elements are sorted by descending e as floats (+0 == -0), equal errors in flat index order (a stable
+ *   least-significant-digit radix sort; dropped elements last, in index order).  With G the segment's ones and c1 / c0 the ones /
+ *   zeros up to and including an element: I = G - c1, U = G + c0, g = 1 - I / U for the segment's first element, 1 / U at a
+ *   label 1, I / ((U - 1) U) at a label 0, formed in fp64 from the integers.  Segment loss = sum weight * g in fp64 through a
+ *   fixed tree.  loss_out [1] = sum_c w_c channel_loss_c with w = seg_weights_dev [C] or 1 when NULL; channel_loss_out [C];
+ *   dx_out [B][C][HW] = d loss_out / d x, every element written.  NaN inputs are outside the contract and stay in bounds.
+ * dh_xbd_lovasz_order: order_out [n] int32 = the flat indices in sorted order, segment after segment, and nothing else.
+ * workspace: dh_xbd_lovasz_workspace_size(n, segments) bytes (segments = C or B * C; *bytes is a host pointer), 16-byte aligned;
+ *   every word that is read is written first by the same call.  The launches depend on (n, segments) alone, nothing is read by the
+ *   host or allocated, no workgroup waits for another: the call can be recorded in a HIP graph.  The same bits on every call.
+ * dh_xbd_lovasz_tile: the elements a workgroup takes per pass.
+ * Refused (nothing is launched, non-zero, dh_last_error begins with xbd_lovasz): a null x, target, output or workspace, an empty
+ *   input, n > 2^30, more than 256 segments, mode outside 0 .. 2, target_kind or per_image outside {0, 1}, ignore outside
+ *   -1 .. 255, a short or misaligned workspace. */
+int dh_xbd_lovasz_tile(void);
+int dh_xbd_lovasz_workspace_size(long n, int segments, long* bytes);
+int dh_xbd_lovasz_fwd(const float* x, const void* target, int target_kind, int B, int C, long HW, int mode, int per_image,
+                      int ignore, const float* seg_weights_dev, float* loss_out, float* channel_loss_out, float* dx_out,
+                      int* bad_out, void* workspace, long workspace_bytes, void* stream);
+int dh_xbd_lovasz_order(const float* x, const void* target, int target_kind, int B, int C, long HW, int mode, int per_image,
+                        int ignore, int* order_out, void* workspace, long workspace_bytes, void* stream);
+/* The terms that need no sort, per channel over the whole batch, on s = 1 / (1 + expf(-x)) (probs 0: x are logits) or s = x
+ * (probs 1: x are probabilities, what the reference's stand-alone classes take) and t = the target's value:
+ *   jaccard      1 - (I + 1e-6) / (S + T - I + 1e-6), I = sum s t, S = sum s, T = sum t             (losses.py:36-45)
+ *   bce          mean(max(x, 0) - x t + log(1 + exp(-|x|))), x always read as a logit               (StableBCELoss, :70-80)
+ *   mask_bceavg  mean(-(t max(log s, -100) + (1 - t) max(log(1 - s), -100)))                        (MaskLoss, :82-92)
+ *   dice         1 - (2 I + 1e-6) / (S + T + 1e-6)                                                  (soft_dice_loss, :24-33)
+ *   focal        mean over t != 255 of -(1 - pt)^2 log pt, pt on s and t clamped to [1e-6, 1 - 1e-6] (FocalLoss2d, :273-289)
+ * dh_combo_loss_* stays the path of ComboLoss's dice and focal; the last two serve the stand-alone classes.
+ * fwd: one pass and a finalize launch; sums_out [C][4] = I, S, T, focal's element count (what bwd reads), terms_out [C][5] = the
+ * terms in the order above, loss_out [1] = sum_c w_c sum_k weight_k term_kc over the terms whose weight is not 0, w =
+ * chan_weights_dev [C] or 1 when NULL.  Sums in fp64 through a fixed tree.  bwd: dx [B][C][HW] = upstream * d loss_out / d x in
+ * one pass (upstream_dev a device scalar or NULL for 1); a term whose weight is 0 is not evaluated.
+ * workspace: dh_xbd_seg_terms_workspace_size(C) bytes, 8-byte aligned.
+ * Refused (nothing is launched): a null pointer, an empty input, C > 65535, target_kind or probs outside {0, 1}, a short
+ * workspace. */
+int dh_xbd_seg_terms_workspace_size(int C, long* bytes);
+int dh_xbd_seg_terms_fwd(const float* x, const void* target, int target_kind, int probs, int B, int C, long HW,
+                         const float* chan_weights_dev, float w_jaccard, float w_bce, float w_mask, float w_dice, float w_focal,
+                         float* sums_out, float* terms_out, float* loss_out, void* workspace, long workspace_bytes, void* stream);
+int dh_xbd_seg_terms_bwd(const float* x, const void* target, int target_kind, int probs, const float* sums,
+                         const float* chan_weights_dev, const float* upstream_dev, float w_jaccard, float w_bce, float w_mask,
+                         float w_dice, float w_focal, int B, int C, long HW, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
