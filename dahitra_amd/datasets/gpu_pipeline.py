@@ -1,5 +1,5 @@
-"""Pre-decoded image pairs resident in HBM + crop / flip / blur / normalise on the device (dh_augment_pairs_u8,
-dh_augment_pairs_blur_u8).
+"""Pre-decoded image pairs resident in HBM + crop / flip / blur / normalise on the device (ops.augment_pairs:
+dh_augment_pairs_u8, dh_augment_pairs_blur_u8).
 
 The reference's loader decodes two PNGs and runs PIL transforms per sample in DataLoader workers
 (datasets/CD_dataset.py:112-134, datasets/data_utils.py:55-111); at the ~7 000 pairs/s of the MI355X train step that is the
@@ -108,30 +108,23 @@ class GpuPairPipeline:
         params[:, 0], params[:, 1] = x0, y0
         if flips is not None:
             params[:, 2:] = torch.as_tensor(flips, dtype=torch.int32)
+        table = None
         if blur is not None:
             if len(blur) != n:
                 raise ValueError("blur: %d radii for %d samples" % (len(blur), n))
             table = blur_table(blur)
         dev = self.a.device
         idx = torch.as_tensor(indices, dtype=torch.int32).to(dev)
-        params = params.to(dev)
-        out_a = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
-        out_b = torch.empty_like(out_a)
-        out_l = torch.empty(n, 1, h, w, dtype=torch.uint8, device=dev)
-        if blur is None:
-            ops._call("dh_augment_pairs_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params), n, H, W,
-                      h, w, ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
-        else:
-            table = table.to(dev)
-            ops._call("dh_augment_pairs_blur_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params),
-                      ops.P(table), n, H, W, h, w, ops.P(out_a), ops.P(out_b), ops.P(out_l), ops.S())
+        out_a, out_b, out_l = ops.augment_pairs(self.a, self.b, self.l, idx, params.to(dev), h, w,
+                                                table.to(dev) if table is not None else None)
         return {'A': out_a, 'B': out_b, 'L': out_l, 'name': [self.names[i] for i in indices]}
 
     def window_batch(self, index, plan, out=None):
         """The P views of source pair `index` under `plan` (tiles.TilePlan): {'A', 'B' float32 [P, 3, h, w], 'L' uint8
-        [P, 1, h, w]}, view p cut at the plan's origin and flipped by its code -- dh_augment_pairs_u8 with the pair's index
-        repeated, one launch.  index: an int, or a device int32 tensor of one element (a recorded graph is re-aimed by writing
-        into it; it is NOT range-checked, the caller keeps it inside 0 .. len - 1).  out: a dict of such tensors to write into."""
+        [P, 1, h, w]}, view p cut at the plan's origin and flipped by its code -- ops.augment_pairs (dh_augment_pairs_u8) with the
+        pair's index repeated, one launch.  index: an int, or a device int32 tensor of one element (a recorded graph is re-aimed by writing
+        into it; it is NOT range-checked, the caller keeps it inside 0 .. len - 1).  out: a dict of such tensors to write into
+        (the wrapper checks them; nothing is allocated for the views then)."""
         S, H, W, _ = self.a.shape
         dev = self.a.device
         if (plan.H, plan.W) != (H, W):
@@ -149,23 +142,26 @@ class GpuPairPipeline:
         params = self._plan_params.get(plan)
         if params is None:
             params = self._plan_params[plan] = torch.from_numpy(plan.params()).to(dev)
-        shapes = {'A': ((P, 3, h, w), torch.float32), 'B': ((P, 3, h, w), torch.float32), 'L': ((P, 1, h, w), torch.uint8)}
         if out is None:
-            out = {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in shapes.items()}
-        for k, (s, d) in shapes.items():
-            t = out.get(k)
-            if not torch.is_tensor(t) or tuple(t.shape) != s or t.dtype != d or t.device != dev or not t.is_contiguous():
-                raise ValueError("window_batch: out[%r] is not a contiguous %s %s on %s" % (k, str(d).replace("torch.", ""), list(s), dev))
-        ops._call("dh_augment_pairs_u8", ops.P(self.a), ops.P(self.b), ops.P(self.l), ops.P(idx), ops.P(params), P, H, W,
-                  h, w, ops.P(out['A']), ops.P(out['B']), ops.P(out['L']), ops.S())
+            out = {'A': None, 'B': None, 'L': None}
+        elif not all(torch.is_tensor(out.get(k)) for k in 'ABL'):
+            raise ValueError("window_batch: out is a dict of the tensors 'A', 'B' and 'L'")
+        out['A'], out['B'], out['L'] = ops.augment_pairs(self.a, self.b, self.l, idx, params, h, w, out_a=out['A'], out_b=out['B'],
+                                                         out_l=out['L'])
         return out
 
     def batches(self, batch_size, img_size, train=True, generator=None, patch=None, drop_last=False, blur=False):
         """one epoch: shuffled with random flips (p = 0.5 each, as the reference's training augmentation) when `train`; with
         `blur` a training batch also draws one blur radius in [0, 1) per sample, after its flips (evaluation never blurs)"""
+        return self._epoch(batch_size, img_size, train, generator, patch, drop_last, blur)
+
+    def _epoch(self, batch_size, img_size, train, generator, patch, drop_last, blur, rank=0, world=1):
+        """the epoch body of `batches` and of GpuPairLoader: rank `rank` of `world` takes its shard of the one permutation"""
         S = len(self)
         order = torch.randperm(S, generator=generator).tolist() if train else list(range(S))
-        for s in range(0, S, batch_size):
+        per = S // world
+        order = order[rank * per:(rank + 1) * per]
+        for s in range(0, len(order), batch_size):
             ind = order[s:s + batch_size]
             if drop_last and len(ind) < batch_size:
                 break
@@ -191,14 +187,5 @@ class GpuPairLoader:
         return per // self.batch_size if self.drop_last else -(-per // self.batch_size)
 
     def __iter__(self):
-        S = len(self.pipe)
-        order = torch.randperm(S, generator=self.generator).tolist() if self.train else list(range(S))
-        per = S // self.world
-        order = order[self.rank * per:(self.rank + 1) * per]
-        for s in range(0, len(order), self.batch_size):
-            ind = order[s:s + self.batch_size]
-            if self.drop_last and len(ind) < self.batch_size:
-                break
-            flips = (torch.rand(len(ind), 2, generator=self.generator) > 0.5).int() if self.train else None
-            radii = torch.rand(len(ind), generator=self.generator).tolist() if self.blur else None
-            yield self.pipe.make_batch(ind, self.img_size, flips, blur=radii)
+        return self.pipe._epoch(self.batch_size, self.img_size, self.train, self.generator, None, self.drop_last, self.blur,
+                                self.rank, self.world)

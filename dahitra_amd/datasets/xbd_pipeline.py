@@ -1,4 +1,4 @@
-"""Pre-decoded xBD samples resident in HBM + TrainData / ValData.__getitem__ on the device (dh_xbd_augment_u8,
+"""Pre-decoded xBD samples resident in HBM + TrainData / ValData.__getitem__ on the device (ops.xbd_augment: dh_xbd_augment_u8,
 dh_xbd_augment_jitter_u8).
 
 The reference's xBD loader opens four 1024x1024 PNGs per sample (pre and post image, pre mask, post label) and, in training,
@@ -62,7 +62,6 @@ resident source again:
     for batch in xbd.unet_val_batches(pipe, 16, 256, indices=val_idxs): ...
 """
 import collections
-import ctypes
 import functools
 import glob
 import math
@@ -73,7 +72,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from .. import _lib, ops
+from .. import ops
 
 PRECISION_BITS = 22        # Pillow's 8-bit resize: coefficients in 2.22 fixed point (Resample.c)
 PARAM_FIELDS = ("x0", "y0", "hflip", "vflip", "resize", "top", "left", "height", "width")
@@ -201,7 +200,7 @@ def jitter_reference_u8(img_u8, order, factors):
     return img
 
 
-JITTER_WORDS = 8           # int32 words of a row of dh_xbd_augment_jitter_u8's table
+JITTER_WORDS = ops.XBD_JITTER_WORDS        # int32 words of a row of dh_xbd_augment_jitter_u8's table
 
 
 def jitter_table(jitter):
@@ -231,10 +230,7 @@ def jitter_table(jitter):
     return table
 
 
-def jitter_workspace_bytes(n, crop):
-    """bytes of dh_xbd_augment_jitter_u8's workspace for n samples of crop x crop: the device copy of the table, then one
-    partial sum of L per tile and image"""
-    return n * 2 * (JITTER_WORDS + _lib.lib().dh_xbd_augment_jitter_tiles(crop)) * 4
+jitter_workspace_bytes = ops.xbd_augment_jitter_ws_bytes
 
 
 def check_params(params, H, W, crop):
@@ -884,6 +880,14 @@ def epoch_order(n, indices):
     return order
 
 
+def _check_dilate(dilate, train=True):
+    if isinstance(dilate, bool) or not isinstance(dilate, int) or (dilate != 0 and not (3 <= dilate <= ops.XBD_MORPH_MAX_K
+                                                                                         and dilate % 2 == 1)):
+        raise ValueError("dilate: %r is neither 0 nor an odd window of 3 .. %d" % (dilate, ops.XBD_MORPH_MAX_K))
+    if dilate and not train:
+        raise ValueError("dilate: the dilated masks are training targets; the reference's ValData does not dilate (train=False)")
+
+
 class GpuXbdPipeline:
     def __init__(self, pre_u8, post_u8, pre_mask_u8, post_label_u8, files=None):
         """pre_u8, post_u8: [n_src, H, W, 3] uint8 device tensors; pre_mask_u8 (0 / 255) and post_label_u8 (0 .. 4):
@@ -931,6 +935,51 @@ class GpuXbdPipeline:
 
     def __len__(self):
         return self.pre.shape[0]
+
+    def _sources(self, indices, allow_empty=False):
+        """a batch's source indices as a list of ints; ValueError for one outside the samples (or for none at all)"""
+        ind = [int(i) for i in indices]
+        if (not ind and not allow_empty) or any(not 0 <= i < len(self) for i in ind):
+            raise ValueError("indices %r outside the %d samples" % (list(indices), len(self)))
+        return ind
+
+    def _zero_label(self, n, crop):
+        """the ONE zero `lbl_msk` every training batch of a shape shares (module docstring): read it, never write to it"""
+        if self._zero_lbl is None or self._zero_lbl.shape != (n, crop, crop):
+            self._zero_lbl = torch.zeros(n, crop, crop, dtype=torch.uint8, device=self.pre.device)
+        return self._zero_lbl
+
+    def _grown(self, attr, need):
+        """the workspace kept under `attr`, replaced by a larger one when it holds fewer than `need` bytes"""
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=self.pre.device)
+            setattr(self, attr, ws)
+        return ws
+
+    def _batch(self, img, msk, lbl, ind):
+        return {'img': img, 'msk': msk, 'lbl_msk': lbl, 'fn': [self.files[i] for i in ind]}
+
+    def _epoch_chunks(self, batch_size, crop, train, rng, indices, drop_last):
+        """the source indices of every batch of one epoch, what `batches`, `adapt_batches` and `unet_batches` share: epoch_order
+        of `indices`, shuffled with `rng` in a training epoch and nothing drawn otherwise, in slices of batch_size; drop_last
+        stops in front of a short one.  ValueError, at the first next(), for a validation crop that is not the whole image, a
+        crop that does not fit, an empty or outside index list, or a training epoch without `rng`."""
+        _, H, W, _ = self.pre.shape
+        if not train and not crop == H == W:
+            raise ValueError("a validation epoch takes whole images: crop %d is not the %dx%d image" % (crop, H, W))
+        if not 1 <= crop <= min(H, W):
+            raise ValueError("crop: %r does not fit the %dx%d images" % (crop, H, W))
+        order = epoch_order(len(self), indices)
+        if train:
+            if rng is None:
+                raise ValueError("a training epoch draws from `rng` (a random.Random)")
+            rng.shuffle(order)
+        for s in range(0, len(order), batch_size):
+            ind = order[s:s + batch_size]
+            if drop_last and len(ind) < batch_size:
+                break
+            yield ind
 
     def class_table(self):
         """[len(self), 6] int64 host array, read-only: how many pixels of every resident post-disaster label equal 0, 1, 2, 3, 4
@@ -981,7 +1030,7 @@ class GpuXbdPipeline:
         that shape: read it, never write to it in place.
         jitter: one entry per sample, None or the pair (pre, post) of draw_jitter_params results applied to the sample's two
         images (ColorJitter, train.py:139; training batches only).  None, or every entry None, is dh_xbd_augment_u8 exactly
-        as without the argument; otherwise one call of dh_xbd_augment_jitter_u8.
+        as without the argument; otherwise one call of dh_xbd_augment_jitter_u8 (ops.xbd_augment makes either).
         dilate: 0 (default) is the batch as above, with the same launches and the same bytes.  An odd k of 3 .. 31 (training
         batches only; 5 is the script's value) gives the targets xBD_code/train_unettransformer.py trains on: after the augment
         launch ONE more launch (ops.xbd_msk_dilate) replaces `msk` by the four damage channels dilated with square(k) and put
@@ -995,11 +1044,7 @@ class GpuXbdPipeline:
         validation batch, jitter rows that do not match the samples, an order that is no permutation, a factor that is not
         finite, a `dilate` that is not 0 or an odd integer of 3 .. 31, or `dilate` in a validation batch."""
         n = len(indices)
-        if isinstance(dilate, bool) or not isinstance(dilate, int) or (dilate != 0 and not (3 <= dilate <= ops.XBD_MORPH_MAX_K
-                                                                                             and dilate % 2 == 1)):
-            raise ValueError("dilate: %r is neither 0 nor an odd window of 3 .. %d" % (dilate, ops.XBD_MORPH_MAX_K))
-        if dilate and not train:
-            raise ValueError("dilate: the dilated masks are training targets; the reference's ValData does not dilate (train=False)")
+        _check_dilate(dilate, train)
         table = None
         if jitter is not None:
             if not train:
@@ -1013,37 +1058,19 @@ class GpuXbdPipeline:
         p = check_params(params, H, W, crop)
         if p.shape[0] != n:
             raise ValueError("params: %d rows for %d samples" % (p.shape[0], n))
-        if any(not 0 <= int(i) < len(self) for i in indices):
-            raise ValueError("indices %r outside the %d samples" % (list(indices), len(self)))
+        ind = self._sources(indices, allow_empty=True)          # (an empty batch is the entry's to refuse)
         coef = coef_table(p, crop)
         dev = self.pre.device
-        idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int32).to(dev)
+        idx = torch.as_tensor(ind, dtype=torch.int32).to(dev)
         p = p.contiguous().to(dev)
         coef = coef.to(dev) if coef is not None else None
-        img = torch.empty(n, 6, crop, crop, dtype=torch.float32, device=dev)
-        msk = torch.empty(n, 5, crop, crop, dtype=torch.uint8, device=dev)
-        if train:
-            if self._zero_lbl is None or self._zero_lbl.shape != (n, crop, crop):
-                self._zero_lbl = torch.zeros(n, crop, crop, dtype=torch.uint8, device=dev)
-            lbl = self._zero_lbl
-        else:
-            lbl = torch.empty(n, crop, crop, dtype=torch.uint8, device=dev)
-        if table is None:
-            ops._call("dh_xbd_augment_u8", ops.P(self.pre), ops.P(self.post), ops.P(None if train else self.pre_mask),
-                      ops.P(self.post_label), ops.P(idx), ops.P(p), ops.P(coef), n, H, W, crop, 0 if train else 1, ops.P(img),
-                      ops.P(msk), ops.P(None if train else lbl), ops.S())
-        else:
-            need = jitter_workspace_bytes(n, crop)
-            if self._jitter_ws is None or self._jitter_ws.numel() < need:
-                self._jitter_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            ws = self._jitter_ws
-            # the table is host memory: the entry checks it and copies it into the workspace before it returns
-            ops._call("dh_xbd_augment_jitter_u8", ops.P(self.pre), ops.P(self.post), ops.P(None), ops.P(self.post_label),
-                      ops.P(idx), ops.P(p), ops.P(coef), ctypes.c_void_p(table.ctypes.data), n, H, W, crop, 0, ops.P(img),
-                      ops.P(msk), ops.P(None), ops.P(ws), ws.numel(), ops.S())
+        # the jitter table is host memory: the entry checks it and copies it into the workspace before it returns
+        ws = self._grown('_jitter_ws', jitter_workspace_bytes(n, crop)) if table is not None else None
+        img, msk, lbl = ops.xbd_augment(self.pre, self.post, self.pre_mask, self.post_label, idx, p, coef, crop, train, table,
+                                        out_lbl=self._zero_label(n, crop) if train else None, ws=ws)
         if dilate:
             msk = ops.xbd_msk_dilate(msk, dilate)
-        return {'img': img, 'msk': msk, 'lbl_msk': lbl, 'fn': [self.files[int(i)] for i in indices]}
+        return self._batch(img, msk, lbl, ind)
 
     def batches(self, batch_size, crop, train=True, rng=None, jitter_gen=None, dilate=0, indices=None, drop_last=False):
         """one epoch.  train: `rng` (a random.Random) shuffles the samples, then every sample draws its parameters with
@@ -1062,19 +1089,8 @@ class GpuXbdPipeline:
         drop_last: stop in front of a batch shorter than batch_size, as the scripts' DataLoader(drop_last=True): the epoch then
         has len(indices) // batch_size batches, their steps_per_epoch."""
         _, H, W, _ = self.pre.shape
-        if dilate and not train:
-            raise ValueError("dilate: the dilated masks are training targets; the reference's ValData does not dilate (train=False)")
-        if not train and not crop == H == W:
-            raise ValueError("a validation epoch takes whole images: crop %d is not the %dx%d image" % (crop, H, W))
-        order = epoch_order(len(self), indices)
-        if train:
-            if rng is None:
-                raise ValueError("a training epoch draws from `rng` (a random.Random)")
-            rng.shuffle(order)
-        for s in range(0, len(order), batch_size):
-            ind = order[s:s + batch_size]
-            if drop_last and len(ind) < batch_size:
-                break
+        _check_dilate(dilate, train)
+        for ind in self._epoch_chunks(batch_size, crop, train, rng, indices, drop_last):
             if not train:
                 yield self.make_batch(ind, crop, None, train)
                 continue
@@ -1119,8 +1135,7 @@ class GpuXbdPipeline:
         if isinstance(crop, bool) or not isinstance(crop, (int, np.integer)) or not 1 <= crop <= min(H, W):
             raise ValueError("crop: %r does not fit the %dx%d images" % (crop, H, W))
         crop = int(crop)
-        if n == 0 or any(not 0 <= int(i) < len(self) for i in indices):
-            raise ValueError("indices %r outside the %d samples" % (list(indices), len(self)))
+        ind = self._sources(indices)
         dev = self.pre.device
         org = None
         if origins is not None:
@@ -1130,9 +1145,8 @@ class GpuXbdPipeline:
             if any(not (0 <= x0 <= W - crop and 0 <= y0 <= H - crop) for x0, y0 in rows):
                 raise ValueError("origins: a %dx%d window at one of %r leaves the %dx%d image" % (crop, crop, rows, H, W))
             org = torch.as_tensor(rows, dtype=torch.int32).reshape(n, 2).to(dev)
-        idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int32).to(dev)
-        img, msk, lbl = ops.xbd_adapt_batch(self.pre, self.post, self.pre_mask, self.post_label, idx, org, crop, train)
-        return {'img': img, 'msk': msk, 'lbl_msk': lbl, 'fn': [self.files[int(i)] for i in indices]}
+        idx = torch.as_tensor(ind, dtype=torch.int32).to(dev)
+        return self._batch(*ops.xbd_adapt_batch(self.pre, self.post, self.pre_mask, self.post_label, idx, org, crop, train), ind)
 
     def adapt_batches(self, batch_size, crop, train=True, rng=None, indices=None, drop_last=False):
         """one epoch of xBD_code/train_adapt.py's loader, make_adapt_batch's dicts.  train: `rng` (a random.Random) shuffles the
@@ -1143,26 +1157,8 @@ class GpuXbdPipeline:
         indices, drop_last: as in `batches` -- the script's epochs are adapt_batches(1, 1024, True, rng, train_idxs,
         drop_last=True) and adapt_batches(1, 1024, False, indices=val_idxs) with adapt_trainset's lists."""
         _, H, W, _ = self.pre.shape
-        if not train and not crop == H == W:
-            raise ValueError("a validation epoch takes whole images: crop %d is not the %dx%d image" % (crop, H, W))
-        if not 1 <= crop <= min(H, W):
-            raise ValueError("crop: %r does not fit the %dx%d images" % (crop, H, W))
-        order = epoch_order(len(self), indices)
-        if train:
-            if rng is None:
-                raise ValueError("a training epoch draws from `rng` (a random.Random)")
-            rng.shuffle(order)
-        for s in range(0, len(order), batch_size):
-            ind = order[s:s + batch_size]
-            if drop_last and len(ind) < batch_size:
-                break
-            origins = None
-            if train:
-                origins = []
-                for _ in ind:
-                    x0 = rng.randint(0, W - crop)
-                    y0 = rng.randint(0, H - crop)
-                    origins.append((x0, y0))
+        for ind in self._epoch_chunks(batch_size, crop, train, rng, indices, drop_last):
+            origins = [(rng.randint(0, W - crop), rng.randint(0, H - crop)) for _ in ind] if train else None     # x0, then y0
             yield self.make_adapt_batch(ind, crop, origins, train)
 
     def make_unet_batch(self, indices, crop, rows, dilate=5, colour=None):
@@ -1186,15 +1182,12 @@ class GpuXbdPipeline:
         samples, a `dilate` that is not 0 or an odd integer of 3 .. 31, or colour entries that do not match the samples or do
         not fit (check_unet_colour)."""
         n = len(indices)
-        if isinstance(dilate, bool) or not isinstance(dilate, int) or (dilate != 0 and not (3 <= dilate <= ops.XBD_MORPH_MAX_K
-                                                                                             and dilate % 2 == 1)):
-            raise ValueError("dilate: %r is neither 0 nor an odd window of 3 .. %d" % (dilate, ops.XBD_MORPH_MAX_K))
+        _check_dilate(dilate)
         _, H, W, _ = self.pre.shape
         rows = check_unet_rows(list(rows), H, W, crop)
         if len(rows) != n:
             raise ValueError("rows: %d rows for %d samples" % (len(rows), n))
-        if n == 0 or any(not 0 <= int(i) < len(self) for i in indices):
-            raise ValueError("indices %r outside the %d samples" % (list(indices), len(self)))
+        ind = self._sources(indices)
         jobs = noise = None
         if colour is not None:
             colour = check_unet_colour(list(colour), crop)
@@ -1203,21 +1196,17 @@ class GpuXbdPipeline:
             jobs, noise = unet_colour_jobs(colour, crop)
         tab = unet_warp_table(rows, crop)
         dev = self.pre.device
-        idx = torch.as_tensor([int(i) for i in indices], dtype=torch.int32).to(dev)
+        idx = torch.as_tensor(ind, dtype=torch.int32).to(dev)
         p = torch.from_numpy(unet_param_rows(rows)).to(dev)
         tab = torch.from_numpy(tab).to(dev) if tab is not None else None
         img, msk = ops.xbd_augment_warp(self.pre, self.post, self.post_label, idx, p, tab, crop)
         if jobs is not None:
-            need = ops.xbd_unet_colour_ws_bytes(len(jobs), crop)
-            if self._colour_ws is None or self._colour_ws.numel() < need:
-                self._colour_ws = torch.empty(need, dtype=torch.uint8, device=dev)
             ops.xbd_unet_colour(img, torch.from_numpy(jobs).to(dev), torch.from_numpy(noise).to(dev) if noise is not None else None,
-                                ws=self._colour_ws)
-        if self._zero_lbl is None or self._zero_lbl.shape != (n, crop, crop):
-            self._zero_lbl = torch.zeros(n, crop, crop, dtype=torch.uint8, device=dev)
+                                ws=self._grown('_colour_ws', ops.xbd_unet_colour_ws_bytes(len(jobs), crop)))
+        lbl = self._zero_label(n, crop)
         if dilate:
             msk = ops.xbd_msk_dilate(msk, dilate)
-        return {'img': img, 'msk': msk, 'lbl_msk': self._zero_lbl, 'fn': [self.files[int(i)] for i in indices]}
+        return self._batch(img, msk, lbl, ind)
 
     def unet_batches(self, batch_size, crop, rng, dilate=5, colour=False, np_rng=None, indices=None, drop_last=False):
         """one training epoch of xBD_code/train_unettransformer.py's loader: `rng` (a random.Random) shuffles the samples, then
@@ -1229,17 +1218,10 @@ class GpuXbdPipeline:
         gauss_noise draws from (the script draws from numpy's global legacy generator); without one gauss_noise stays skipped.
         indices, drop_last: as in `batches` -- the script's epoch is unet_batches(16, 256, rng, indices=train_idxs,
         drop_last=True) with unet_trainset's train_idxs."""
-        if rng is None:
-            raise ValueError("a training epoch draws from `rng` (a random.Random)")
         _, H, W, _ = self.pre.shape
-        order = epoch_order(len(self), indices)
-        rng.shuffle(order)
         self.unet_skipped = collections.Counter()
         self.unet_applied = collections.Counter()
-        for s in range(0, len(order), batch_size):
-            ind = order[s:s + batch_size]
-            if drop_last and len(ind) < batch_size:
-                break
+        for ind in self._epoch_chunks(batch_size, crop, True, rng, indices, drop_last):
             rows, colours = [], []
             for _ in ind:
                 if colour:

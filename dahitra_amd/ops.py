@@ -1887,6 +1887,75 @@ def adamw_xbd_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weig
           step, P(grad_scale_dev), S())
 
 
+# ---- arguments, outputs and workspaces of the checked wrappers below: xBD losses, loaders, evaluation, cd_* ------
+class _Args:
+    """The argument checker of the wrappers from here to cd_view_counts -- the xBD losses, loaders and evaluation, the cd_* ones;
+    xbd_val_count / xbd_val_sweep keep _xbd_val_args' checks, which convert dtypes: ValueError, before any launch, for whatever
+    the kernel cannot read as it lies.  tensor() refuses at once an argument whose type, dtype or shape does not fit,
+        "<fn>: <name> <shape> <dtype> is not <dtype> <text>",
+    and placed(), called when all of them fit, checks device and storage -- so a wrong shape shows whatever device the tensors
+    are on.  Two placement policies: a tensor that is not on the first one's GPU is a ValueError (the xBD loaders and evaluation
+    wrappers); with cpu_error=True tensors that are ALL on the CPU are a HipLibraryError (there is no CPU path) and only mixed
+    devices a ValueError (the xBD losses, xbd_class_table, cd_eval_vis, cd_tile_stitch, cd_view_counts)."""
+
+    def __init__(self, what, cpu_error=False):
+        self.what, self.cpu_error, self.checked = what, cpu_error, []
+
+    def tensor(self, name, t, dtype, fits, text=None):
+        """fits: the shape, or a predicate on the tensor; text: how the message describes it (default: the shape).  Returns t"""
+        if not torch.is_tensor(t) or t.dtype != dtype or not (fits(t) if callable(fits) else tuple(t.shape) == tuple(fits)):
+            raise ValueError("%s: %s %s %s is not %s %s" % (self.what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
+                                                            str(dtype).replace("torch.", ""), str(list(fits)) if text is None else text))
+        self.checked.append((name, t))
+        return t
+
+    def image(self, name, t, dtype):
+        """a non-empty [N, H, W] map: returns (N, H, W)"""
+        return tuple(self.tensor(name, t, dtype, lambda t: t.dim() == 3 and t.numel() > 0, "[N, H, W], not empty").shape)
+
+    def out(self, t, dtype, shape, name="out", text=None):
+        """an output buffer: the given one, checked like any argument, or a fresh tensor beside the first argument"""
+        if t is None:
+            return torch.empty(tuple(shape), dtype=dtype, device=self.checked[0][1].device)
+        return self.tensor(name, t, dtype, shape, text)
+
+    def workspace(self, ws):
+        """a caller's workspace, if one is given: uint8 of any shape (_workspace checks its size once the need is known)"""
+        if ws is not None:
+            self.tensor("ws", ws, torch.uint8, lambda t: True, "workspace")
+
+    def placed(self):
+        first_name, first = self.checked[0]
+        if self.cpu_error and not any(t.is_cuda for _, t in self.checked):
+            raise _lib.HipLibraryError("dahitra_amd %s runs on MI355X only (no CPU fallback): its tensors are on the CPU" % self.what)
+        for name, t in self.checked:
+            if not t.is_cuda or t.device != first.device:
+                if self.cpu_error:
+                    raise ValueError("%s: %s is on %s and %s on %s; the kernel takes all its tensors on one GPU"
+                                     % (self.what, name, t.device, first_name, first.device))
+                raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device"
+                                 % (self.what, name, t.device))
+            if not t.is_contiguous():
+                raise ValueError("%s: %s is not contiguous (strides %s)" % (self.what, name, t.stride()))
+
+
+def _ws_bytes(entry, *dims):
+    """what the library's size query `entry` answers for `dims`: the bytes of a kernel's workspace"""
+    n = ctypes.c_long(0)
+    if getattr(_lib.lib(), entry)(*dims, ctypes.byref(n)) != 0:
+        raise ValueError(_lib.lib().dh_last_error().decode())
+    return int(n.value)
+
+
+def _workspace(what, ws, need, device):
+    """the caller's workspace (an _Args-checked uint8 buffer) if it holds `need` 4-byte aligned bytes, or a fresh one"""
+    if ws is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if ws.numel() < need or ws.data_ptr() % 4:
+        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
+    return ws
+
+
 # ---- losses of the two xBD training scripts (csrc/xbd_script_loss.hip) -------------------------------------------
 XBD_UNET_LABELS = {"lbl_msk": 0, "damage": 1}
 # lanes of one forward grid pass (dh_xbd_unet_loss_grid_pass): that many pixels where H * W is no multiple of 4 (one pixel per
@@ -2108,7 +2177,7 @@ def xbd_adapt_batch(pre_u8, post_u8, pre_mask_u8, post_label_u8, idx, origins, c
     a.tensor("post_label_u8", post_label_u8, torch.uint8, (n_src, H, W))
     N = a.tensor("idx", idx, torch.int32, lambda t: t.dim() == 1 and t.numel() > 0, "[N], not empty").shape[0]
     if origins is not None:
-        a.tensor("origins", origins, torch.int32, (N, 2))
+        a.tensor("origins", origins, torch.int32, (N, 2), "[%d, 2]: a row per entry of idx" % N)
     a.placed()
     if isinstance(crop, bool) or not isinstance(crop, int) or not 1 <= crop <= min(H, W):
         raise ValueError("xbd_adapt_batch: crop %r does not fit the %dx%d sources" % (crop, H, W))
@@ -2241,74 +2310,6 @@ def xbd_val_sweep(logits, msk, lbl, image_hist, class_hist, thresholds, select="
             raise _lib.HipLibraryError("xbd_val_sweep runs on MI355X only (no CPU fallback)")
     _call("dh_xbd_val_sweep", P(logits.contiguous()), _vp(msk.data_ptr()), stride, P(lbl.contiguous()), B, H, W, _vp(thr.ctypes.data),
           T, XBD_VAL_SELECT[select], P(image_hist), P(class_hist), S())
-
-
-# ---- arguments, outputs and workspaces of the evaluation wrappers below --------------------------------------
-class _Args:
-    """The argument checker of the evaluation wrappers from here to cd_view_counts: ValueError, before any launch, for whatever
-    the kernel cannot read as it lies.  tensor() refuses at once an argument whose type, dtype or shape does not fit,
-        "<fn>: <name> <shape> <dtype> is not <dtype> <text>",
-    and placed(), called when all of them fit, checks device and storage -- so a wrong shape shows whatever device the tensors
-    are on.  Two placement policies: a tensor that is not on the first one's GPU is a ValueError (the xBD wrappers); with
-    cpu_error=True tensors that are ALL on the CPU are a HipLibraryError (there is no CPU path) and only mixed devices a
-    ValueError (cd_eval_vis, cd_tile_stitch, cd_view_counts)."""
-
-    def __init__(self, what, cpu_error=False):
-        self.what, self.cpu_error, self.checked = what, cpu_error, []
-
-    def tensor(self, name, t, dtype, fits, text=None):
-        """fits: the shape, or a predicate on the tensor; text: how the message describes it (default: the shape).  Returns t"""
-        if not torch.is_tensor(t) or t.dtype != dtype or not (fits(t) if callable(fits) else tuple(t.shape) == tuple(fits)):
-            raise ValueError("%s: %s %s %s is not %s %s" % (self.what, name, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t)),
-                                                            str(dtype).replace("torch.", ""), str(list(fits)) if text is None else text))
-        self.checked.append((name, t))
-        return t
-
-    def image(self, name, t, dtype):
-        """a non-empty [N, H, W] map: returns (N, H, W)"""
-        return tuple(self.tensor(name, t, dtype, lambda t: t.dim() == 3 and t.numel() > 0, "[N, H, W], not empty").shape)
-
-    def out(self, t, dtype, shape, name="out", text=None):
-        """an output buffer: the given one, checked like any argument, or a fresh tensor beside the first argument"""
-        if t is None:
-            return torch.empty(tuple(shape), dtype=dtype, device=self.checked[0][1].device)
-        return self.tensor(name, t, dtype, shape, text)
-
-    def workspace(self, ws):
-        """a caller's workspace, if one is given: uint8 of any shape (_workspace checks its size once the need is known)"""
-        if ws is not None:
-            self.tensor("ws", ws, torch.uint8, lambda t: True, "workspace")
-
-    def placed(self):
-        first_name, first = self.checked[0]
-        if self.cpu_error and not any(t.is_cuda for _, t in self.checked):
-            raise _lib.HipLibraryError("dahitra_amd %s runs on MI355X only (no CPU fallback): its tensors are on the CPU" % self.what)
-        for name, t in self.checked:
-            if not t.is_cuda or t.device != first.device:
-                if self.cpu_error:
-                    raise ValueError("%s: %s is on %s and %s on %s; the kernel takes all its tensors on one GPU"
-                                     % (self.what, name, t.device, first_name, first.device))
-                raise ValueError("%s: %s is on %s; the kernel runs on the MI355X and all its tensors on one device"
-                                 % (self.what, name, t.device))
-            if not t.is_contiguous():
-                raise ValueError("%s: %s is not contiguous (strides %s)" % (self.what, name, t.stride()))
-
-
-def _ws_bytes(entry, *dims):
-    """what the library's size query `entry` answers for `dims`: the bytes of a kernel's workspace"""
-    n = ctypes.c_long(0)
-    if getattr(_lib.lib(), entry)(*dims, ctypes.byref(n)) != 0:
-        raise ValueError(_lib.lib().dh_last_error().decode())
-    return int(n.value)
-
-
-def _workspace(what, ws, need, device):
-    """the caller's workspace (an _Args-checked uint8 buffer) if it holds `need` 4-byte aligned bytes, or a fresh one"""
-    if ws is None:
-        return torch.empty(need, dtype=torch.uint8, device=device)
-    if ws.numel() < need or ws.data_ptr() % 4:
-        raise ValueError("%s: ws holds %d bytes at offset %d, %d 4-byte aligned ones are needed" % (what, ws.numel(), ws.data_ptr() % 4, need))
-    return ws
 
 
 # ---- xBD prediction: 4-flip test-time augmentation (csrc/xbd_predict.hip) ---------------------------------
@@ -2714,6 +2715,101 @@ def xbd_class_table(labels_u8, out=None):
     return out
 
 
+# ---- device loaders: the pair loader and xBD_code/train.py's (csrc/pointwise.hip, augment_blur.hip, augment_xbd.hip) --------
+def augment_pairs(a_u8, b_u8, l_u8, idx, params, h, w, blur=None, out_a=None, out_b=None, out_l=None):
+    """One batch of the change-detection pair loader in ONE launch (dh_augment_pairs_u8; with `blur` dh_augment_pairs_blur_u8).
+    a_u8, b_u8 [S, H, W, 3] and l_u8 [S, H, W], or None for no labels: the resident uint8 sources; idx int32 [N]: the source of
+    every sample; params int32 [N, 4] = (x0, y0, hflip, vflip) of its h x w window; blur int32 [N, 2] = the (ww, fw) rows of
+    datasets/gpu_pipeline.blur_table, which checks their bounds, or None.  Returns (out_a, out_b fp32 [N, 3, h, w], out_l uint8
+    [N, 1, h, w]), the given buffers or fresh ones; out_l is None without l_u8.  ValueError for whatever does not fit, before
+    the launch; the caller range-checks idx and the windows (they are device memory)."""
+    a = _Args("augment_pairs")
+    n_src, H, W, _ = a.tensor("a_u8", a_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[3] == 3 and t.numel() > 0,
+                              "[S, H, W, 3], not empty").shape
+    a.tensor("b_u8", b_u8, torch.uint8, (n_src, H, W, 3))
+    if l_u8 is not None:
+        a.tensor("l_u8", l_u8, torch.uint8, (n_src, H, W))
+    N = a.tensor("idx", idx, torch.int32, lambda t: t.dim() == 1, "[N]").shape[0]
+    a.tensor("params", params, torch.int32, (N, 4), "[%d, 4]: a row per entry of idx" % N)
+    if blur is not None:
+        a.tensor("blur", blur, torch.int32, (N, 2), "[%d, 2]: a row per entry of idx" % N)
+    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (h, w)) or not (1 <= h <= H and 1 <= w <= W):
+        raise ValueError("augment_pairs: a %r x %r window does not fit the %dx%d sources" % (h, w, H, W))
+    h, w = int(h), int(w)
+    out_a = a.out(out_a, torch.float32, (N, 3, h, w), "out_a", "[%d, 3, %d, %d]: idx's N, h, w" % (N, h, w))
+    out_b = a.out(out_b, torch.float32, (N, 3, h, w), "out_b", "[%d, 3, %d, %d]: idx's N, h, w" % (N, h, w))
+    if l_u8 is not None:          # (the plain kernel reads l wherever it is given an out_l)
+        out_l = a.out(out_l, torch.uint8, (N, 1, h, w), "out_l", "[%d, 1, %d, %d]: idx's N, h, w" % (N, h, w))
+    elif out_l is not None:
+        raise ValueError("augment_pairs: out_l is given and l_u8 is None: there is no label to cut")
+    a.placed()
+    if blur is None:
+        _call("dh_augment_pairs_u8", P(a_u8), P(b_u8), P(l_u8), P(idx), P(params), N, H, W, h, w, P(out_a), P(out_b), P(out_l), S())
+    else:
+        _call("dh_augment_pairs_blur_u8", P(a_u8), P(b_u8), P(l_u8), P(idx), P(params), P(blur), N, H, W, h, w, P(out_a), P(out_b),
+              P(out_l), S())
+    return out_a, out_b, out_l
+
+
+XBD_JITTER_WORDS = 8             # int32 words of a row of dh_xbd_augment_jitter_u8's table
+
+
+def xbd_augment_jitter_ws_bytes(n, crop):
+    """bytes of dh_xbd_augment_jitter_u8's workspace for n samples of crop x crop: the device copy of the table, then one
+    partial sum of L per tile and image"""
+    return n * 2 * (XBD_JITTER_WORDS + _lib.lib().dh_xbd_augment_jitter_tiles(crop)) * 4
+
+
+def xbd_augment(pre_u8, post_u8, pre_mask_u8, post_label_u8, idx, params, coef, crop, train=True, jitter=None, out_img=None,
+                out_msk=None, out_lbl=None, ws=None):
+    """One batch of xBD_code/train.py's TrainData (train=True) or ValData in ONE launch (dh_xbd_augment_u8; the header states the
+    arithmetic).  pre_u8, post_u8 [n_src, H, W, 3] and pre_mask_u8, post_label_u8 [n_src, H, W]: the resident uint8 sources;
+    idx int32 [N]; params int32 [N, 9] rows in datasets/xbd_pipeline.PARAM_FIELDS order; coef int32 [N, 2, crop, 4], its
+    coef_table, or None (no sample resizes).  Returns (out_img fp32 [N, 6, crop, crop], out_msk uint8 [N, 5, crop, crop],
+    out_lbl uint8 [N, crop, crop]), the given buffers or fresh ones.  Train mode reads no pre mask and does NOT write out_lbl:
+    it is what the caller passes (the pipeline's shared zero tensor).
+    jitter: a C-contiguous int32 HOST array [N, 2, 8] (xbd_pipeline.jitter_table; train mode only) makes the call
+    dh_xbd_augment_jitter_u8 -- ColorJitter on the samples whose rows are enabled, a second launch for contrast's mean; the
+    entry checks the rows and copies them into the workspace before it returns.  ws: a uint8 device buffer of
+    xbd_augment_jitter_ws_bytes(N, crop) bytes or more for that call (default: a fresh one).
+    ValueError for whatever does not fit, before the launch; the caller range-checks idx and the rows (check_params)."""
+    what = "xbd_augment"
+    a = _Args(what)
+    n_src, H, W, _ = a.tensor("pre_u8", pre_u8, torch.uint8, lambda t: t.dim() == 4 and t.shape[3] == 3 and t.numel() > 0,
+                              "[n_src, H, W, 3], not empty").shape
+    a.tensor("post_u8", post_u8, torch.uint8, (n_src, H, W, 3))
+    a.tensor("pre_mask_u8", pre_mask_u8, torch.uint8, (n_src, H, W))
+    a.tensor("post_label_u8", post_label_u8, torch.uint8, (n_src, H, W))
+    N = a.tensor("idx", idx, torch.int32, lambda t: t.dim() == 1, "[N]").shape[0]
+    a.tensor("params", params, torch.int32, (N, 9), "[%d, 9]: a row per entry of idx" % N)
+    if isinstance(crop, bool) or not isinstance(crop, (int, np.integer)) or not 1 <= crop <= min(H, W):
+        raise ValueError("%s: crop %r does not fit the %dx%d sources" % (what, crop, H, W))
+    crop = int(crop)
+    if coef is not None:
+        a.tensor("coef", coef, torch.int32, (N, 2, crop, 4), "[%d, 2, %d, 4]: idx's N, crop" % (N, crop))
+    out_img = a.out(out_img, torch.float32, (N, 6, crop, crop), "out_img", "[%d, 6, %d, %d]: idx's N, crop" % (N, crop, crop))
+    out_msk = a.out(out_msk, torch.uint8, (N, 5, crop, crop), "out_msk", "[%d, 5, %d, %d]: idx's N, crop" % (N, crop, crop))
+    if out_lbl is not None or not train:
+        out_lbl = a.out(out_lbl, torch.uint8, (N, crop, crop), "out_lbl", "[%d, %d, %d]: idx's N, crop" % (N, crop, crop))
+    if jitter is not None:
+        if not train:
+            raise ValueError("%s: jitter belongs to the training augmentation (train=False)" % what)
+        if not (isinstance(jitter, np.ndarray) and jitter.dtype == np.int32 and jitter.shape == (N, 2, XBD_JITTER_WORDS)
+                and jitter.flags.c_contiguous):
+            raise ValueError("%s: jitter %s %s is not a C-contiguous int32 host array [%d, 2, %d]"
+                             % (what, getattr(jitter, "shape", ()), getattr(jitter, "dtype", type(jitter)), N, XBD_JITTER_WORDS))
+    a.workspace(ws)
+    a.placed()
+    src = (P(pre_u8), P(post_u8), P(None if train else pre_mask_u8), P(post_label_u8), P(idx), P(params), P(coef))
+    dst = (N, H, W, crop, 0 if train else 1, P(out_img), P(out_msk), P(None if train else out_lbl))
+    if jitter is None:
+        _call("dh_xbd_augment_u8", *src, *dst, S())
+    else:
+        ws = _workspace(what, ws, xbd_augment_jitter_ws_bytes(N, crop), pre_u8.device)
+        _call("dh_xbd_augment_jitter_u8", *src, _vp(jitter.ctypes.data), *dst, P(ws), ws.numel(), S())
+    return out_img, out_msk, out_lbl
+
+
 XBD_WARP_TILE = (32, 32)         # (TH, TW) of dh_xbd_augment_warp_u8's output tile: dh_xbd_augment_warp_tile_h / _tile_w
 XBD_WARP_PARAM_WORDS = 12        # x0, y0, vflip, rot, sx, sy, warp, chan, dR, dG, dB, 0
 
@@ -2732,7 +2828,7 @@ def xbd_augment_warp(pre_u8, post_u8, label_u8, idx, params, tab, crop, out_img=
     a.tensor("label_u8", label_u8, torch.uint8, (n_src, H, W))
     a.tensor("idx", idx, torch.int32, lambda t: t.dim() == 1 and t.numel() > 0, "[N], not empty")
     N = idx.numel()
-    a.tensor("params", params, torch.int32, (N, XBD_WARP_PARAM_WORDS))
+    a.tensor("params", params, torch.int32, (N, XBD_WARP_PARAM_WORDS), "[%d, %d]: a row per entry of idx" % (N, XBD_WARP_PARAM_WORDS))
     if tab is not None:
         a.tensor("tab", tab, torch.int32, (N, 4, crop))
     out_img = a.out(out_img, torch.float32, (N, 6, crop, crop), "out_img")

@@ -1,5 +1,5 @@
-"""What the evaluation-side wrappers of dahitra_amd.ops refuse, and the epoch loop of models/xbd.validate / validate_sweep, without
-a GPU.  A table tries one bad argument at a time on every tensor argument of every wrapper (`out` and `ws` included) and asserts
+"""What the evaluation-side and loader-side wrappers of dahitra_amd.ops refuse, and the epoch loop of models/xbd.validate /
+validate_sweep, without a GPU.  A table tries one bad argument at a time on every tensor argument of every wrapper (`out` and `ws` included) and asserts
 the exception type, that the message names the function and the argument, and that no kernel entry of the library was reached.
 The order in which two simultaneous faults are reported is deliberately not pinned."""
 import types
@@ -16,6 +16,8 @@ U8, I32, I64, F32 = torch.uint8, torch.int32, torch.int64, torch.float32
 OTHER = {U8: F32, F32: torch.float64, I32: I64, I64: I32}
 WS_BYTES = 4096          # what the stand-in library answers to every *_ws_bytes query
 CAP = 4
+CROP = 8                 # the loaders' window: it fits the sources at either size
+JITTER_TILES = 3         # what the stand-in library answers to dh_xbd_augment_jitter_tiles
 
 
 class SizesOnly:
@@ -27,6 +29,8 @@ class SizesOnly:
                 args[-1]._obj.value = WS_BYTES
                 return 0
             return size
+        if name == "dh_xbd_augment_jitter_tiles":
+            return lambda S: JITTER_TILES
         raise AssertionError("the library was touched: %s" % name)
 
 
@@ -147,6 +151,54 @@ def view_counts(alt):
     return {"logits": z(F32, P, C, h, w), "labels": z(U8, P, h, w), "counts": z(I64, P, C, C)}
 
 
+# the loaders: the resident sources at dims(alt), and a batch of 3 (alt: 4) samples, which idx sets
+def xbd_sources(alt):
+    n, H, W = dims(alt)
+    return {"pre_u8": z(U8, n, H, W, 3), "post_u8": z(U8, n, H, W, 3), "pre_mask_u8": z(U8, n, H, W), "post_label_u8": z(U8, n, H, W)}
+
+
+def augment(alt):
+    N = 4 if alt else 3
+    return {**xbd_sources(alt), "idx": z(I32, N), "params": z(I32, N, 9), "coef": z(I32, N, 2, CROP, 4),
+            "out_img": z(F32, N, 6, CROP, CROP), "out_msk": z(U8, N, 5, CROP, CROP), "out_lbl": z(U8, N, CROP, CROP)}
+
+
+def pairs(alt):
+    n, H, W = dims(alt)
+    N = 4 if alt else 3
+    return {"a_u8": z(U8, n, H, W, 3), "b_u8": z(U8, n, H, W, 3), "l_u8": z(U8, n, H, W), "idx": z(I32, N), "params": z(I32, N, 4),
+            "blur": z(I32, N, 2), "out_a": z(F32, N, 3, 4, 6), "out_b": z(F32, N, 3, 4, 6), "out_l": z(U8, N, 1, 4, 6)}
+
+
+def augment_warp(alt):
+    n, H, W = dims(alt)
+    N = 4 if alt else 3
+    return {"pre_u8": z(U8, n, H, W, 3), "post_u8": z(U8, n, H, W, 3), "label_u8": z(U8, n, H, W), "idx": z(I32, N),
+            "params": z(I32, N, ops.XBD_WARP_PARAM_WORDS), "tab": z(I32, N, 4, CROP), "out_img": z(F32, N, 6, CROP, CROP),
+            "out_msk": z(U8, N, 5, CROP, CROP)}
+
+
+def unet_colour(alt):
+    N, S = (4, 12) if alt else (3, 8)
+    return {"img": z(F32, N, 6, S, S), "jobs": z(I32, 3 if alt else 2, ops.XBD_COLOUR_JOB_WORDS), "noise": z(U8, 1, S, S, 3),
+            "ws": z(U8, WS_BYTES)}
+
+
+def adapt_batch(alt):
+    N = 4 if alt else 3
+    return {**xbd_sources(alt), "idx": z(I32, N), "origins": z(I32, N, 2)}
+
+
+def class_table(alt):
+    n, H, W = dims(alt)
+    return {"labels_u8": z(U8, n, H, W), "out": z(I32, n, len(ops.XBD_CLASS_COLUMNS))}
+
+
+def call_augment(a, **more):
+    return ops.xbd_augment(a["pre_u8"], a["post_u8"], a["pre_mask_u8"], a["post_label_u8"], a["idx"], a["params"], a["coef"], CROP,
+                           out_img=a["out_img"], out_msk=a["out_msk"], out_lbl=a["out_lbl"], **more)
+
+
 WRAPPERS = {
     "xbd_tta_pack": (tta_pack, lambda a: ops.xbd_tta_pack(a["pre_u8"], a["post_u8"], "bgr", out=a["out"])),
     "xbd_tta_merge": (tta_merge, lambda a: ops.xbd_tta_merge(a["logits"], out=a["out"])),
@@ -168,8 +220,18 @@ WRAPPERS = {
     "cd_tile_stitch": (tile_stitch, lambda a: ops.cd_tile_stitch(a["logits"], plan(False), a["out_logits"], a["out_mask"], a["label"],
                                                                  a["counts"], a["label_index"])),
     "cd_view_counts": (view_counts, lambda a: ops.cd_view_counts(a["logits"], a["labels"], a["counts"])),
+    "xbd_augment": (augment, lambda a: call_augment(a, train=False)),                      # (validation mode writes out_lbl)
+    "augment_pairs": (pairs, lambda a: ops.augment_pairs(a["a_u8"], a["b_u8"], a["l_u8"], a["idx"], a["params"], 4, 6, a["blur"],
+                                                         out_a=a["out_a"], out_b=a["out_b"], out_l=a["out_l"])),
+    "xbd_augment_warp": (augment_warp, lambda a: ops.xbd_augment_warp(a["pre_u8"], a["post_u8"], a["label_u8"], a["idx"], a["params"],
+                                                                      a["tab"], CROP, out_img=a["out_img"], out_msk=a["out_msk"])),
+    "xbd_unet_colour": (unet_colour, lambda a: ops.xbd_unet_colour(a["img"], a["jobs"], a["noise"], ws=a["ws"])),
+    "xbd_adapt_batch": (adapt_batch, lambda a: ops.xbd_adapt_batch(a["pre_u8"], a["post_u8"], a["pre_mask_u8"], a["post_label_u8"],
+                                                                   a["idx"], a["origins"], CROP)),
+    "xbd_class_table": (class_table, lambda a: ops.xbd_class_table(a["labels_u8"], out=a["out"])),
 }
-HIP_ERROR_ON_CPU = ("cd_eval_vis", "cd_tile_stitch", "cd_view_counts")      # the others refuse a CPU tensor with ValueError
+# the others refuse a CPU tensor with ValueError
+HIP_ERROR_ON_CPU = ("cd_eval_vis", "cd_tile_stitch", "cd_view_counts", "xbd_class_table")
 
 
 def strided(t):
@@ -189,6 +251,8 @@ def bad_arguments():
                 kinds += ["short"]
             if name == "label_index":                     # one element: of any rank, and never strided
                 kinds = ["non-tensor", "dtype", "disagrees"]
+            if (fn, name) == ("xbd_unet_colour", "jobs"):  # any number of jobs: no other argument has a say in it
+                kinds.remove("disagrees")
             cases += [(fn, name, kind) for kind in kinds]
     return cases
 
@@ -224,6 +288,30 @@ def test_cpu_tensors_are_refused_before_the_library_is_touched(no_library, fn):
         assert type(e.value) is _lib.HipLibraryError
     else:
         assert type(e.value) is ValueError and next(iter(args)) in str(e.value), str(e.value)
+
+
+def test_xbd_augment_checks_its_jitter_table_and_workspace(no_library, monkeypatch):
+    """the two arguments of xbd_augment's ColorJitter form, which the table's row does not take"""
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
+    args = augment(False)
+    table = np.zeros((3, 2, ops.XBD_JITTER_WORDS), dtype=np.int32)
+    need = ops.xbd_augment_jitter_ws_bytes(3, CROP)
+    assert need == 3 * 2 * (ops.XBD_JITTER_WORDS + JITTER_TILES) * 4
+    ws = z(U8, need)
+    for bad in (torch.from_numpy(table), table.astype(np.int64), table[:2], table[None], np.asfortranarray(table),
+                np.zeros((3, 2, 2 * ops.XBD_JITTER_WORDS), dtype=np.int32)[..., ::2], table.tolist()):
+        with pytest.raises(ValueError, match="xbd_augment: jitter"):
+            call_augment(args, jitter=bad, ws=ws)
+    with pytest.raises(ValueError, match="xbd_augment: jitter"):                            # a validation batch is not jittered
+        call_augment(args, jitter=table, ws=ws, train=False)
+    for bad in (np.zeros(need, dtype=np.uint8), ws.to(F32), strided(ws), ws[:need - 1]):
+        with pytest.raises(ValueError, match="xbd_augment: ws"):
+            call_augment(args, jitter=table, ws=bad)
+    for fits in (ws, z(U8, need + 1), None):
+        with pytest.raises(Reached, match="dh_xbd_augment_jitter_u8"):
+            call_augment(args, jitter=table, ws=fits)
+    with pytest.raises(Reached, match="dh_xbd_augment_u8"):                                 # no table: the plain entry
+        call_augment(args, ws=ws)
 
 
 # ---- the epoch loop of validate and validate_sweep -----------------------------------------------------------------

@@ -129,6 +129,46 @@ def test_c_abi_on_noise_equals_pillow_on_the_cropped_flipped_window(S, H, W, h, 
     assert np.array_equal(ol, pl)
 
 
+@pytest.mark.parametrize("h,w", [(16, 16), (24, 40)])
+@pytest.mark.parametrize("blur", [False, True])
+def test_wrapper_gives_the_raw_entrys_bytes(blur, h, w):
+    """ops.augment_pairs against dh_augment_pairs_u8 / dh_augment_pairs_blur_u8 on the same arguments, into fresh outputs and into
+    sentinel-filled ones: a 16 x 16 window of 24 x 40 sources and the whole image; a repeated index, every flip"""
+    from dahitra_amd import ops
+    from dahitra_amd.datasets.gpu_pipeline import blur_table
+    rng = np.random.RandomState(31)
+    dev = "cuda:0"
+    ta, tb = (torch.from_numpy(rng.randint(0, 256, (3, 24, 40, 3)).astype(np.uint8)).to(dev) for _ in range(2))
+    tl = torch.from_numpy(rng.randint(0, 2, (3, 24, 40)).astype(np.uint8)).to(dev)
+    tidx = torch.tensor([2, 0, 2], dtype=torch.int32, device=dev)
+    x0, y0 = (40 - w, 24 - h)
+    params = torch.tensor([[x0, y0, 1, 0], [x0 // 2, y0 // 2, 0, 1], [0, 0, 1, 1]], dtype=torch.int32, device=dev)
+    table = blur_table([0.31, 0.0, 0.999]).to(dev) if blur else None
+
+    def sentinels():
+        return (torch.full((3, 3, h, w), float("nan"), dtype=torch.float32, device=dev),
+                torch.full((3, 3, h, w), float("nan"), dtype=torch.float32, device=dev),
+                torch.full((3, 1, h, w), 255, dtype=torch.uint8, device=dev))
+
+    want = sentinels()
+    ops._call(*(("dh_augment_pairs_blur_u8",) if blur else ("dh_augment_pairs_u8",)), ops.P(ta), ops.P(tb), ops.P(tl), ops.P(tidx),
+              ops.P(params), *((ops.P(table),) if blur else ()), 3, 24, 40, h, w, *(ops.P(t) for t in want), ops.S())
+    torch.cuda.synchronize()
+    assert not torch.isnan(want[0]).any() and not torch.isnan(want[1]).any() and int(want[2].max()) <= 1
+    given = sentinels()
+    for got in (ops.augment_pairs(ta, tb, tl, tidx, params, h, w, table),
+                ops.augment_pairs(ta, tb, tl, tidx, params, h, w, table, out_a=given[0], out_b=given[1], out_l=given[2])):
+        torch.cuda.synchronize()
+        assert torch.equal(got[0].view(torch.int32), want[0].view(torch.int32))
+        assert torch.equal(got[1].view(torch.int32), want[1].view(torch.int32)) and torch.equal(got[2], want[2])
+    assert all(g is o for g, o in zip(got, given))
+    # without the label stack, as the header allows: the images alone
+    got = ops.augment_pairs(ta, tb, None, tidx, params, h, w, table)
+    assert torch.equal(got[0].view(torch.int32), want[0].view(torch.int32)) and got[2] is None
+    with pytest.raises(ValueError, match="out_l"):
+        ops.augment_pairs(ta, tb, None, tidx, params, h, w, table, out_l=given[2])
+
+
 def test_loader_surface():
     from dahitra_amd.datasets.gpu_pipeline import GpuPairLoader, GpuPairPipeline
     pipe = GpuPairPipeline.from_dataset_root(os.path.join(G, "levir"), "train", device="cuda:0")

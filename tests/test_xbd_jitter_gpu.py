@@ -111,6 +111,47 @@ def test_c_abi_contrast_mean_of_the_clipped_image(src):
     assert not np.array_equal(C.pil_jitter(pre, [0, 1], (1.2, 0.8, 1.0)), C.pil_jitter(pre, [1, 0], (1.2, 0.8, 1.0)))
 
 
+@pytest.mark.parametrize("S", [32, 37])
+def test_wrapper_gives_the_raw_entrys_bytes(S):
+    """ops.xbd_augment with a jitter table against dh_xbd_augment_jitter_u8 on the same arguments, into fresh outputs and into
+    sentinel-filled ones.  40 x 48 sources; S = 32 takes the vector stores, S = 37 the scalar ones; a repeated index, a sample
+    with both flips and ColorJitter, one with the box"""
+    from dahitra_amd import ops
+    from dahitra_amd.datasets.xbd_pipeline import jitter_table
+    small = C.sources(seed=13, h=40, w=48)
+    idx = [2, 0, 2]
+    rows = [[48 - S, 40 - S, 0, 0, 0, 0, 0, S, S], [2, 1, 1, 1, 0, 0, 0, S, S], [0, 3, 0, 1, 1, 4, 6, S - 7, S - 10]]
+    jitter = [None, (([0, 3, 2, 1], (1.1, 0.9, 1.2)), ([1, 0, 2, 3], (0.85, C.PINNED[1], 0.8))), None]
+    table = jitter_table(jitter)
+    (pre, post, pmask, label), tidx, p, coef = dev_tables(small, idx, rows, S)
+    assert coef is not None
+    need = ops.xbd_augment_jitter_ws_bytes(3, S)
+    want_img, want_msk = outputs(3, S)
+    ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=DEV)
+    ops._call("dh_xbd_augment_jitter_u8", ops.P(pre), ops.P(post), ops.P(None), ops.P(label), ops.P(tidx), ops.P(p), ops.P(coef),
+              ctypes.c_void_p(table.ctypes.data), 3, 40, 48, S, 0, ops.P(want_img), ops.P(want_msk), ops.P(None), ops.P(ws), need, ops.S())
+    torch.cuda.synchronize()
+    want_img, want_msk = want_img.cpu().numpy(), want_msk.cpu().numpy()
+    assert_equals_host(small, idx, rows, S, jitter, want_img, want_msk)
+
+    def same_bytes(got):
+        torch.cuda.synchronize()
+        assert np.array_equal(got[0].cpu().numpy().view(np.int32), want_img.view(np.int32))
+        assert np.array_equal(got[1].cpu().numpy(), want_msk)
+
+    fresh = ops.xbd_augment(pre, post, pmask, label, tidx, p, coef, S, True, table)
+    same_bytes(fresh)
+    assert fresh[2] is None
+    out = outputs(3, S) + (torch.full((3, S, S), 255, dtype=torch.uint8, device=DEV),)
+    given = ops.xbd_augment(pre, post, pmask, label, tidx, p, coef, S, True, table, out_img=out[0], out_msk=out[1], out_lbl=out[2],
+                            ws=torch.full((need + 4,), 0xFF, dtype=torch.uint8, device=DEV))
+    assert all(g is o for g, o in zip(given, out))
+    same_bytes(given)
+    assert bool((out[2] == 255).all()), "train mode does not write out_lbl"
+    plain = ops.xbd_augment(pre, post, pmask, label, tidx, p, coef, S, True)[0].cpu().numpy()
+    assert [np.array_equal(plain[n], want_img[n]) for n in range(3)] == [True, False, True]
+
+
 def make_pipe(src):
     from dahitra_amd.datasets.xbd_pipeline import GpuXbdPipeline
     return GpuXbdPipeline(*(torch.from_numpy(np.array(a)).to(DEV) for a in src), files=["s%d" % i for i in range(len(src[0]))])

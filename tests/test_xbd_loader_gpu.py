@@ -169,6 +169,38 @@ def test_c_abi_refuses_bad_arguments():
             call(**bad)
 
 
+@pytest.mark.parametrize("train", [True, False])
+@pytest.mark.parametrize("S", [32, 37])
+def test_wrapper_gives_the_raw_entrys_bytes(S, train):
+    """ops.xbd_augment against dh_xbd_augment_u8 on the same arguments, into fresh outputs and into sentinel-filled ones.  40 x 48
+    sources; S = 32 takes the vector stores, S = 37 the scalar ones; a repeated index, a sample with both flips, one with the box"""
+    from dahitra_amd import ops
+    from dahitra_amd.datasets.xbd_pipeline import check_params, coef_table
+    src = sources(3, 40, 48, seed=11)
+    idx = [2, 0, 2]
+    rows = [[48 - S, 40 - S, 0, 0, 0, 0, 0, S, S], [2, 1, 1, 1, 0, 0, 0, S, S], [0, 3, 0, 1, 1, 4, 6, S - 7, S - 10]]
+    want = compare(src, idx, rows, S, train)                                  # the raw entry, and equal to Pillow
+    pre, post, pmask, label = (torch.from_numpy(a).to(DEV) for a in src)
+    p = check_params(rows, 40, 48, S)
+    coef, tidx, p = coef_table(p, S).to(DEV), torch.tensor(idx, dtype=torch.int32, device=DEV), p.to(DEV)
+
+    def same_bytes(got):
+        torch.cuda.synchronize()
+        assert np.array_equal(got[0].cpu().numpy().view(np.int32), want[0].view(np.int32))
+        assert np.array_equal(got[1].cpu().numpy(), want[1])
+
+    fresh = ops.xbd_augment(pre, post, pmask, label, tidx, p, coef, S, train)
+    same_bytes(fresh)
+    assert fresh[2] is None if train else np.array_equal(fresh[2].cpu().numpy(), want[2])
+    out = (torch.full((3, 6, S, S), float("nan"), dtype=torch.float32, device=DEV),
+           torch.full((3, 5, S, S), 255, dtype=torch.uint8, device=DEV), torch.full((3, S, S), 255, dtype=torch.uint8, device=DEV))
+    given = ops.xbd_augment(pre, post, pmask, label, tidx, p, coef, S, train, out_img=out[0], out_msk=out[1], out_lbl=out[2])
+    assert all(g is o for g, o in zip(given, out))
+    same_bytes(given)
+    assert np.array_equal(out[2].cpu().numpy(), want[2])                       # train mode: still the sentinel, as the raw call's
+    assert bool((out[2] == 255).all()) == train
+
+
 EPOCH_SEED = 0          # an epoch of three samples with a resized and an unresized one (asserted where it is used)
 
 
